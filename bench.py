@@ -11,6 +11,10 @@ RCCL all-reduce of [gLambda|gMu|gDen|misfit]).  Three shots per GPU per step bec
 passes of up to three shots on three streams.  Weak scaling: every rank owns the same number of shots per step.  Inputs (model, source,
 observed data) are resident in HBM when the timed region starts.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the one 32-shot
+call of configs[2] (`call32`) and the CPU baselines (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step returned
+(misfit, gLambda, gMu, gDen, gStf) as DIR/<name>.npy.
+
 cell-update = one grid cell advanced one time step by one propagator; a fwd+adj shot is
 3 * N_c * (nSteps-1) updates with N_c = (nz+2nPml)*(nx+2nPml).
 """
@@ -253,6 +257,23 @@ def call32(workdir, args, dev, local, n_shots=32):
             "what": "one fwi_ops.backward over %d shots (configs[2]), wall time of the call, after the timed region" % n_shots}
 
 
+DUMP_BYTES_MAX = 60_000_000      # all .npy files of --dump-outputs together (a fixed sample of an array where they would be larger)
+
+
+def dump_outputs(dirname, names, tensors):
+    """float32 copies of the arrays a caller of the timed path received in its last step, as DIR/<name>.npy.  Where they would come
+    to more than DUMP_BYTES_MAX, each larger array is replaced by a fixed, seeded sample of its elements (the same indices in every
+    run of the same shape)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = [t.detach().cpu().numpy().astype(np.float32) for t in tensors]
+    cap = DUMP_BYTES_MAX // 4 // len(arrs)
+    if sum(a.size for a in arrs) * 4 > DUMP_BYTES_MAX:
+        arrs = [a if a.size <= cap else a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+                for a in arrs]
+    for n, a in zip(names, arrs):
+        np.save(os.path.join(dirname, n + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,9 +287,11 @@ def main():
     ap.add_argument("--shots-per-step", type=int, default=3,
                     help="shots each GPU processes per step (3: the forward passes of the three overlap on three streams)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="collective backend for N > 1 (nccl = RCCL)")
-    ap.add_argument("--no-call32", action="store_true", help="skip the one 32-shot call of configs[2] reported as `call32` at N = 1")
+    ap.add_argument("--no-call32", action="store_true", help="with --full: skip the one 32-shot call of configs[2] reported as `call32` at N = 1")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="library option for this run (sepfwi_set_option), e.g. bwd_fuse=2")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks on device 0 (rehearsal on a one-GPU box; use with --backend gloo)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: call32, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -346,8 +369,9 @@ def main():
         fwd_ms = bwd_ms = call_ms = 0.0
         probe_us, probe_n = 0.0, 0
         persist_steps = bwd_steps = 0
+        res = None
         for s in range(K):
-            step(s)
+            res = step(s)
             st = fwi_ops.stats(pb["para_fname"], local)
             fwd_ms += st["fwd_ms"]
             bwd_ms += st["bwd_ms"]
@@ -469,10 +493,14 @@ def main():
                 out["persistent_loop"] = {"share_of_bwd_steps_min": round(min(fr), 4) if fr else None,
                                           "share_of_bwd_steps_per_rank": [None if f is None else round(f, 4) for f in rank_loop],
                                           "why_not": {str(r): w for r, w in enumerate(rank_why) if w}}
-            if world == 1 and args.mode == "fwdadj" and not args.no_call32 and args.nz == 1000 and args.nx == 2000:
+            if args.dump_outputs and res is not None:
+                # the step's own shots own the leading rows of gStf (the rest are zeros)
+                outs = [res[0]] if args.mode == "fwd" else list(res[:4]) + [res[4][:spr]]
+                dump_outputs(args.dump_outputs, ("misfit", "gLambda", "gMu", "gDen", "gStf")[:len(outs)], outs)
+            if args.full and world == 1 and args.mode == "fwdadj" and not args.no_call32 and args.nz == 1000 and args.nx == 2000:
                 # configs[2] literally: ONE fwi_ops.backward call over 32 shots on this GPU (outside the timed region above)
                 out["call32"] = call32(os.path.join(workdir, "call32"), args, dev, local)
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 out["cpu_baseline"] = cpu_baseline(args.nz, args.nx)
             print(json.dumps(out))
     finally:

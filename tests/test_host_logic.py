@@ -275,6 +275,25 @@ def test_bench_launcher_command_line():
     assert 1024 < int(free[free.index("--master-port") + 1]) < 65536
 
 
+def test_bench_dump_outputs_are_float32_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy in float32; arrays that would come to more than DUMP_BYTES_MAX in
+    all are replaced by the same seeded sample of their elements in every run, small ones stay whole."""
+    import bench
+    small = [torch.tensor([2.5]), torch.arange(12, dtype=torch.float32).view(3, 4)]
+    bench.dump_outputs(str(tmp_path / "a"), ("misfit", "g"), small)
+    assert np.load(tmp_path / "a" / "misfit.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "a" / "g.npy"), small[1].numpy())
+    n = bench.DUMP_BYTES_MAX // 4 // 2 + 1000
+    big = [torch.tensor([1.0], dtype=torch.float64), torch.arange(n, dtype=torch.float32), torch.arange(n, dtype=torch.float32)]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), ("m", "x", "y"), big)
+    files = [tmp_path / d / (k + ".npy") for d in ("b", "c") for k in ("m", "x", "y")]
+    assert sum(os.path.getsize(f) for f in files[:3]) <= bench.DUMP_BYTES_MAX + 3 * 128
+    x, y, x2 = np.load(files[1]), np.load(files[2]), np.load(files[4])
+    assert x.dtype == np.float32 and np.load(files[0]).tolist() == [1.0]
+    assert 0 < x.size < n and np.array_equal(x, y) and np.array_equal(x, x2) and np.all(np.diff(x) > 0)
+
+
 def _module_case(tmp_path, cls_name, fields, monkeypatch):
     import sepfwi.ops as ops
     from sepfwi import modules as M
