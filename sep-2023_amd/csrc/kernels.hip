@@ -392,7 +392,8 @@ void launch_inject_batch(hipStream_t st, const Grid &g, const ShotDev *shots, in
 void launch_inject_values(hipStream_t st, const float *res, int nrec, int nSteps, const int *tgt_start, const int *ent_rec, const float *ent_w, int ntgt,
                           float *val) {
     if (ntgt <= 0 || nSteps <= 0) return;
-    hipLaunchKernelGGL(k_inject_values, dim3((ntgt + 255) / 256, nSteps), dim3(256), 0, st, res, nrec, tgt_start, ent_rec, ent_w, ntgt, val);
+    const int gy = nSteps < 32768 ? nSteps : 32768;  // (the kernel strides over the rest: a record may exceed the grid's y limit)
+    hipLaunchKernelGGL(k_inject_values, dim3((ntgt + 255) / 256, gy), dim3(256), 0, st, res, nrec, nSteps, tgt_start, ent_rec, ent_w, ntgt, val);
 }
 
 void launch_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, long long n,

@@ -175,6 +175,8 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
         inj_val_len_ = need;
     }
     launch_inject_values(st, x.res, x.nrec, par_.nSteps, d.tgt_start, d.ent_rec, d.ent_w, d.ntgt, inj_val_);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) throw HipError(std::string("k_inject_values launch failed: ") + hipGetErrorString(le));
     launches_++;
     if (it->second.tile_gen != pk_.plan_gen) {  // which tiles of the CURRENT tiling own target cells (a new tiling: rebuilt)
         InjDev &dd = it->second;
@@ -235,10 +237,10 @@ bool Session::backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L) {
     d.x_src = x.sh->x_src;
     d.lr_z = x.line.z;
     d.lr_x0 = x.line.x0;
-    d.lr_n = x.line.n;
     d.nrec = x.nrec;
     d.src_rxz = (float)x.sh->src_rxz;
     a.injp = persist_inject(c, x, st);
+    d.lr_n = a.injp ? 0 : x.line.n;  // a line that is not fused (line_fuse=0) goes through the plan: the bodies must not inject it again
     if (x.quiet && k.d_qnbr && !a.injp) {  // option quiet_skip (fused line of channels, or none): the quiet variant of the loop
         a.q.maps = x.quiet;
         a.q.nbr = k.d_qnbr;

@@ -422,3 +422,83 @@ def test_grid_seven_times_the_headline_matches_oracle(tmp_path, oracle, hip_ops)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "big_grid_vs_oracle.txt"), "w") as fp:
         fp.write("5600 x 2800 x 16 steps, 2 shots, HIP vs CPU oracle: misfit %.6e vs %.6e\n" % (float(m), ref["misfit"]) + "\n".join(lines) + "\n")
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass"])
+def test_headline_grid_general_receivers(tmp_path, hip_ops, case):
+    """Receivers that are not a fused horizontal line on the headline grid (2000 x 1000 + 32-cell layers), one shot, 400 steps, with
+    the default options: the backward pass is the persistent loop in STRIP order (the tile-size rule), and the adjoint source is
+    folded per target cell (k_inject_values) and added by the GINJ branch, across the seam of two XCD bands where the source and the
+    channels sit.  Cases: channels every third cell, a vertical fibre crossing every seam, directional channels every other cell, the
+    band-passed residual (the full-width hipFFT chain) -- against the CPU oracle (scripts/make_golden_headline_receivers.py), against
+    the two-launch step (k_inject's atomics: round-off), and against the same loop forced to edge-first order (bit for bit)."""
+    sys.path.insert(0, ROOT)
+    import scripts.make_golden_headline_receivers as mg
+    from sepfwi import utils as ft
+    G = np.load(mg.golden_path(case))
+    pb = mg.make_case(str(tmp_path), case)
+    assert mg.digest(pb) == str(G["digest"]), "problem generator drifted: regenerate with scripts/make_golden_headline_receivers.py"
+    nS, nPml, seam = pb["nSteps"], pb["nPml"], pb["seam"]
+    assert seam == int(G["seam"]) and seam in mg.seams(pb["nz_pad"], pb["nPad"])
+    # the configuration that ships at this size: the tile-size rule (session_persist.cpp) picks strip order
+    nzc, nseg = pb["nz_pad"] - pb["nPad"], (pb["nx_pad"] + 63) // 64
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    assert nzc * nseg >= 56 * 2 * ncu, (nzc, nseg, ncu)
+    # the oracle's residual is alive on both sides of the seam (fibre: channels above and below it) / of the source (a line on the seam)
+    sh = pb["survey"]["shot0"]
+    e = G["res_energy"]
+    if case == "vertical":
+        side = np.asarray(sh["z_rec"]) + nPml < seam
+    else:
+        side = np.asarray(sh["x_rec"]) < int(sh["x_src"])
+    for s in (side, ~side):
+        assert s.any() and e[s].max() >= 1e-2 * e.max(), (case, e[s].max(), e.max())
+    ids = torch.tensor([0], dtype=torch.int32)
+    lt, mt, dt_ = [t.cuda() for t in pb["lame_true"]]
+    lam, mu, den = [t.cuda() for t in pb["lame_init"]]
+    hip_ops.obscalc(lt, mt, dt_, pb["Stf"], 1, ids, pb["para_fname"])
+    ett = ft.read_shot_gather(pb["data_dir"], "ett", 0, nS)
+    out = {"segments": nzc * nseg, "ett": P.rel_l2(ett[G["channels"]], G["obs_ett"])}
+    assert out["ett"] <= 1e-4, (case, out)
+    assert abs(np.linalg.norm(ett.astype(np.float64)) - float(G["obs_ett_norm"])) <= 1e-4 * float(G["obs_ett_norm"]), case
+    res = hip_ops.backward(lam, mu, den, pb["Stf"], 1, ids, pb["para_fname"])
+    assert hip_ops.stats(pb["para_fname"], 0)["persist_steps"] == nS - 1, hip_ops.loop_status(pb["para_fname"])
+    m, gL, gM, gD, gS = [t.cpu() for t in res]
+    out["misfit"] = abs(float(m) - float(G["misfit"])) / float(G["misfit"])
+    d = int(G["decim"])
+    wins = {w: [int(v) for v in G[w]] for w in ("win_src", "win_seam")}
+    for key, g in (("gLambda", gL), ("gMu", gM), ("gDen", gD)):
+        g = g.numpy()
+        gmax = float(G[key + "_max"])
+        parts = {"dec": (g[::d, ::d], G[key + "_dec"])}
+        for w, (z0, z1, x0, x1) in wins.items():
+            parts[w] = (g[z0:z1, x0:x1], G[key + "_" + w])
+        out[key] = {p: (P.rel_l2(a, b), float(np.abs(a - b).max()) / gmax) for p, (a, b) in parts.items()}
+    out["gStf"] = P.rel_l2(gS.numpy()[0], G["gStf"])
+    # the two-launch step: the same bodies, k_inject's atomics instead of the folded values (the order of the adds differs)
+    with P.kernel_options(bwd_fuse=2):
+        two = [t.cpu() for t in hip_ops.backward(lam, mu, den, pb["Stf"], 1, ids, pb["para_fname"])]
+        assert hip_ops.stats(pb["para_fname"], 0)["persist_steps"] == 0
+    out["vs_two_launch"] = [P.rel_l2(a.numpy(), b.numpy()) for a, b in zip((gL, gM, gD), two[1:4])]
+    hip_ops.release()
+    # the same loop with only the order of each tile's segments changed (-DSEPFWI_PROBES build): strip order (the default rule) and
+    # edge-first order, the same operations per cell -- bit for bit, and bit for bit the shipped library's result
+    order = {}
+    for name, pk_order in (("strip", 2), ("edge-first", 1)):
+        with P.kernel_options(pk_order=pk_order):
+            order[name] = [t.cpu() for t in hip_ops.backward(lam, mu, den, pb["Stf"], 1, ids, pb["para_fname"])]
+            assert hip_ops.stats(pb["para_fname"], 0)["persist_steps"] == nS - 1, (name, hip_ops.loop_status(pb["para_fname"]))
+    out["edge_first_bit_identical"] = all(torch.equal(a, b) for a, b in zip(order["edge-first"], order["strip"]))
+    print("headline grid, %s: %r" % (case, out))
+    assert out["misfit"] <= 1e-4, (case, out)
+    for key in ("gLambda", "gMu", "gDen"):
+        assert float(G[key + "_max"]) > 0
+        for p, (e2, emax) in out[key].items():
+            assert e2 <= 1e-3 and emax <= 1e-3, (case, key, p, out[key])
+    assert out["gStf"] <= 1e-3, (case, out)
+    assert float(two[0]) == float(m), (case, float(two[0]), float(m))
+    assert max(out["vs_two_launch"]) <= 2e-6, (case, out["vs_two_launch"])
+    for name in ("strip", "edge-first"):
+        for k, (a, b) in enumerate(zip(order[name], (m, gL, gM, gD, gS))):
+            assert torch.equal(a, b), (case, name, k, float((a - b).abs().max()))

@@ -54,7 +54,7 @@ def test_persistent_loop_random_geometry_is_bit_identical(tmp_path, hip_ops, see
     assert np.isfinite(ref[0]).all() and np.abs(ref[4]).max() > 0, desc      # (the source gradient is alive from the first backward steps on)
 
 
-_GSEEDS = list(range(int(os.environ.get("SEPFWI_GFUZZ_N", "4"))))
+_GSEEDS = list(range(int(os.environ.get("SEPFWI_GFUZZ_N", "6"))))
 
 
 @pytest.mark.parametrize("seed", _GSEEDS)
@@ -62,13 +62,19 @@ def test_loop_general_receivers_random_geometry(tmp_path, hip_ops, seed):
     """Receivers that are not a fused line inside the persistent loop (folded adjoint source, k_bwd_persist<LMASK, GINJ>) against the
     two-launch step + k_inject on seeded random grids, layer widths and channel sets: strided, scattered with repeats and shared
     cells, a vertical fibre, directional sensitivities.  The two differ only in the order of the float adds into a cell that several
-    channels reach (k_inject's atomics have none): gradients to 5e-6, misfit exactly.  One-off sweeps: SEPFWI_GFUZZ_N=200."""
+    channels reach (k_inject's atomics have none): gradients to 5e-6, misfit exactly.  Every odd seed draws a grid of 28 672 to 40 000
+    row segments: from 56 segments per tile of an MI355X's 512 up, each tile walks its segments in strip order (session_persist.cpp's
+    tile-size rule), as at the headline size; the even seeds' grids are smaller (edge-first order).  One-off sweeps: SEPFWI_GFUZZ_N=200."""
     rng = np.random.default_rng(9000 + seed)
     nPml = int(rng.integers(6, 25))
+    big = seed % 2 == 1
     while True:
-        nz, nx = int(rng.integers(60, 600)), int(rng.integers(120, 1800))
+        if big:
+            nz, nx = int(rng.integers(150, 1300)), int(rng.integers(600, 3000))
+        else:
+            nz, nx = int(rng.integers(60, 600)), int(rng.integers(120, 1800))
         segs = (nz + 2 * nPml) * ((nx + 2 * nPml + 63) // 64)
-        if 2200 <= segs <= 12000:
+        if (28672 <= segs <= 40000) if big else (2200 <= segs <= 12000):
             break
     nSteps = int(rng.integers(150, 380))
     nshots = int(rng.integers(1, 3))
@@ -97,7 +103,10 @@ def test_loop_general_receivers_random_geometry(tmp_path, hip_ops, seed):
         got = [t.numpy().copy() for t in hip_ops.backward(lam, mu, den, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])]
         steps = hip_ops.stats(pb["para_fname"], 0)["persist_steps"]
     hip_ops.release()
-    desc = dict(seed=seed, nz=nz, nx=nx, nPml=nPml, nSteps=nSteps, nshots=nshots, kind=kind, nrec=pb["nrec"])
+    import torch
+    strip = segs >= 56 * 2 * torch.cuda.get_device_properties(0).multi_processor_count      # (the tile-size rule with 2 tiles per CU)
+    desc = dict(seed=seed, nz=nz, nx=nx, nPml=nPml, nSteps=nSteps, nshots=nshots, kind=kind, nrec=pb["nrec"], segs=segs,
+                order="strip" if strip else "edge-first")
     assert steps == nshots * (nSteps - 1), desc
     assert got[0][0] == ref[0][0], desc
     if not ref[0][0] > 0:      # (a record that ends before the wave reaches any channel: the "gradient" is rounding noise of the stencil's precursor)

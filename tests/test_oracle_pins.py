@@ -231,3 +231,37 @@ def test_directional_das_gradient_is_consistent_with_finite_differences(oracle, 
     fm = oracle.cufd(lam, mu, den - eps * d, stf, 0, ids, pb["para"], pb["survey"], obs=obs)["misfit"]
     fd, gd = (fp - fm) / (2 * eps), float((r0["gDen"] * d).sum())
     assert abs(fd - gd) <= 0.05 * abs(gd), (fd, gd)
+
+
+@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass"])
+def test_headline_receivers_goldens_match_their_problems(tmp_path, case):
+    """tests/golden/oracle_headline_receivers_<case>.npz (the GPU test tests/test_gpu_headline.py::test_headline_grid_general_receivers
+    compares against them) belong to the problems scripts/make_golden_headline_receivers.py builds today: same input digest (models,
+    source function, survey, parameter file), same seam and windows, source and channels where the generator says.  A drift of
+    tests/problems.py fails here, on the CPU, instead of first on the GPU.  The oracle is not run (4e9 cell-updates a case)."""
+    import scripts.make_golden_headline_receivers as mg
+    path = mg.golden_path(case)
+    assert os.path.getsize(path) < 1 << 20
+    G = np.load(path)
+    pb = mg.make_case(str(tmp_path), case)
+    assert mg.digest(pb) == str(G["digest"]), "problem generator drifted: regenerate with scripts/make_golden_headline_receivers.py"
+    assert pb["nSteps"] == G["gStf"].shape[0] == mg.NSTEPS
+    nzc = pb["nz_pad"] - pb["nPad"]
+    assert nzc == 1064 and pb["nx_pad"] == 2064
+    seam = int(G["seam"])
+    assert seam == pb["seam"] == round(mg.SEAM_BAND * nzc / mg.NBAND)
+    sh = pb["survey"]["shot0"]
+    n = pb["nPml"]
+    assert 0 < seam - (int(sh["z_src"]) + n) <= 2                          # the source just above the seam
+    z_rec = np.asarray(sh["z_rec"]) + n
+    if case == "vertical":
+        assert z_rec.min() < seam <= z_rec.max() and abs(int(sh["x_src"]) - int(sh["x_rec"][0])) == 20
+    else:
+        assert np.all(z_rec == seam)                                       # the line on the first row below it
+    assert "filter" in pb["para"] if case == "bandpass" else "filter" not in pb["para"]
+    for w in ("win_src", "win_seam"):
+        assert tuple(int(v) for v in G[w]) == pb[w]
+        z0, z1, x0, x1 = pb[w]
+        assert 0 <= z0 < z1 <= nzc and 0 <= x0 < x1 <= pb["nx_pad"] and G["gMu_" + w].shape == (z1 - z0, x1 - x0)
+    assert G["gLambda_dec"].shape == (-(-pb["nz_pad"] // mg.DECIM), -(-pb["nx_pad"] // mg.DECIM))
+    assert G["res_energy"].shape == (pb["nrec"],) and G["obs_ett"].shape == (G["channels"].size, pb["nSteps"])
