@@ -70,7 +70,11 @@ int sepfwi_device_count(void);
  *                Src/utilities.cu:620-641, which the reference reaches only through a source edit).  Further optional keys
  *                (INTEGRATION.md): "obs_pack_fname" -- one packed file of the survey's observed axial-strain gathers instead
  *                of four files per shot; "if_win", "filter", "if_cross_misfit", "if_src_update" -- the data-conditioning
- *                chain of Src/utilities.cu:733-1325, dormant in the reference's driver, live here for the axial-strain gathers.
+ *                chain of Src/utilities.cu:733-1325, dormant in the reference's driver, live here for the axial-strain gathers;
+ *                "das_gauge_length" [m] -- every channel records the mean axial strain over a gauge of G = L / dx cells along a
+ *                horizontal fibre (L / dz along a vertical one; directional channels take the das_fiber axis), its adjoint
+ *                source the exact transpose.  L must be a whole multiple of the spacing (SEPFWI_EJSON otherwise), every
+ *                member cell of a gauge must lie where a channel may (SEPFWI_EINVAL).  Absent or G = 1: the one-cell channel.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.

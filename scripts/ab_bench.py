@@ -3,6 +3,7 @@
 usage: python scripts/ab_bench.py --nsteps 400 --rounds 3 "bz=4,xcd_remap=0" "bz=4,xcd_remap=1" ...
 Prints per-variant forward / backward microseconds per time step (HIP events on the session stream)."""
 import argparse
+import json
 import os
 import shutil
 import sys
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--nx", type=int, default=2000)
     ap.add_argument("--shots", type=int, default=3)
     ap.add_argument("--rec-stride", type=int, default=1, help="a channel every N cells (N > 1: not a fused line -- k_inject, or the loop's general injection)")
+    ap.add_argument("--das-gauge-length", type=float, default=None, help="parameter key das_gauge_length [m]: every channel the mean strain over this gauge")
     a = ap.parse_args()
     _native._active = "probes"   # the tuning knobs exist only in the -DSEPFWI_PROBES build of the library
     _native.build(variant="probes")
@@ -38,6 +40,12 @@ def main():
     work = tempfile.mkdtemp(prefix="sepfwi_ab_")
     try:
         pb = bench.setup_problem(work, a.nz, a.nx, a.nsteps, a.shots, rec_stride=a.rec_stride)
+        if a.das_gauge_length is not None:
+            with open(pb["para_fname"]) as fp:
+                para = json.load(fp)
+            para["das_gauge_length"] = a.das_gauge_length
+            with open(pb["para_fname"], "w") as fp:
+                json.dump(para, fp)
         lt, mt, dt_ = [t.to(dev) for t in pb["lame_true"]]
         lam, mu, den = [t.to(dev) for t in pb["lame_init"]]
         ids = torch.arange(a.shots, dtype=torch.int32)

@@ -73,6 +73,14 @@ Params parse_params(const std::string &text) {
         throw std::runtime_error("parameter JSON: physical grid (nz-nPad-2*nPml, nx-2*nPml) must be at least 6x6");
     if (p.nz > 32767 || p.nx > 32767) throw std::runtime_error("parameter JSON: nz and nx must be below 32768");
     if (!(p.dz > 0 && p.dx > 0 && p.dt > 0)) throw std::runtime_error("parameter JSON: dz, dx, dt must be positive");
+    if (j.has("das_gauge_length")) {
+        const double L = j.at("das_gauge_length").as_number("das_gauge_length");
+        const double d = p.fiber ? (double)p.dz : (double)p.dx;  // the spacing along the fibre
+        const double G = L > 0 ? std::round(L / d) : 0.0;
+        if (!(G >= 1.0 && G <= 32767.0 && std::fabs(G * d - L) <= 1e-3 * d))
+            throw std::runtime_error("parameter JSON: das_gauge_length must be a positive whole multiple of the grid spacing along the fibre");
+        p.gauge = (int)G;
+    }
     return p;
 }
 

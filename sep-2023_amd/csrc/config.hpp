@@ -29,6 +29,9 @@ struct Params {
     // optional key "das_fiber": "horizontal" (default; recording_exx / res_injection_exx, libCUFD.cu:325,607) or
     // "vertical" (recording_ezz / res_injection_ezz, utilities.cu:620-641 -- in the reference a source edit)
     int fiber = 0;
+    // optional key "das_gauge_length" [m] (das_gauge.hpp): every channel records the mean axial strain over G = round(L / dx) cells
+    // along a horizontal fibre, round(L / dz) along a vertical one.  1 (absent): the one-cell channel.
+    int gauge = 1;
 };
 
 struct Shot {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "das_gauge.hpp"
 #include "fwi_types.hpp"
 
 namespace sepfwi {
@@ -95,6 +96,14 @@ void launch_inject_batch(hipStream_t st, const Grid &g, const ShotDev *shots, in
 // the residual [it][rec] folded per injection target and time step: val[it][t] = sum over the target's entries of w r[it][rec] (inject_plan.hpp)
 void launch_inject_values(hipStream_t st, const float *res, int nrec, int nSteps, const int *tgt_start, const int *ent_rec, const float *ent_w, int ntgt,
                           float *val);
+// gauge channels (das_gauge.hip; taps and adjoint plan: das_gauge.hpp): the seismogram column of a shot, its residual column injected at
+// the plan's distinct targets (no atomics), and the batched twins over the shots of a batch (side table GaugeShotDev, indexed like ShotDev)
+void launch_record_gauge(hipStream_t st, Fields f, int nrec, const int *rec, const int *tap_start, const int *tap_cell, const int *tap_field,
+                         const float *tap_w, float *d_pr, float *d_vx, float *d_vz, float *d_ett, int comps);
+void launch_inject_gauge(hipStream_t st, Fields adj, int ntgt, const float *res_t, const int *tgt_start, const int *tgt_cell, const int *tgt_field,
+                         const int *ent_rec, const float *ent_w);
+void launch_record_gauge_batch(hipStream_t st, const ShotDev *shots, const GaugeShotDev *gs, int nb, int max_nrec, size_t n, size_t data_len, int column);
+void launch_inject_gauge_batch(hipStream_t st, const ShotDev *shots, const GaugeShotDev *gs, int nb, int max_ntgt, size_t n, int it);
 void launch_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, long long n,
                      double *sumsq);
 void launch_transpose(hipStream_t st, const float *in, float *out, int rows, int cols);

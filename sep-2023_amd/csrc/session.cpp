@@ -18,6 +18,7 @@
 #include <mutex>
 #include <stdexcept>
 
+#include "das_gauge.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "host_checks.hpp"
@@ -123,6 +124,7 @@ void Session::upload_survey() {
         const int ns = (int)survey_.shots.size();
         std::vector<int> idx;
         receiver_cells(par_, survey_, g.nzc, g.nx, g.pitch, &rec_off_, &idx);
+        check_gauge_members(par_, survey_, g.nzc, g.nx);  // parameter key das_gauge_length: every member of a gauge where a channel may lie
         rec_idx_ = dalloc<int>(idx.size());
         HIP_OK(hipMemcpy(rec_idx_, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
         bool any_sens = false;
@@ -236,9 +238,14 @@ Session::~Session() {
         (void)hipFree(d.tgt_start);
         (void)hipFree(d.ent_rec);
         (void)hipFree(d.ent_w);
+        if (d.tgt_cell) (void)hipFree(d.tgt_cell);
+        if (d.tgt_field) (void)hipFree(d.tgt_field);
         if (d.tile_has) (void)hipFree(d.tile_has);
         if (d.d_args) (void)hipFree(d.d_args);
     }
+    for (auto &kv : gauge_)
+        for (void *p : {(void *)kv.second.start, (void *)kv.second.cell, (void *)kv.second.field, (void *)kv.second.w}) (void)hipFree(p);
+    if (d_gauge_) (void)hipFree(d_gauge_);
     if (inj_val_) (void)hipFree(inj_val_);
     for (void *p : allocs_) (void)hipFree(p);
     if (frame_) (void)hipFree(frame_);

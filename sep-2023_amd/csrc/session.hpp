@@ -64,12 +64,16 @@ class Session {
         float src_scale = 0.0f;
         int n_probe = 0;              // HIP-event pairs handed out in the running backward pass
     };
+    struct GaugeDev;
+    struct InjDev;
     struct ShotCtx {  // one shot of the call in the lane it runs in
         int is, id, nrec, comps;
         const Shot *sh;
         const int *rec;
         const float *stf_s, *d_obs;
         const float *sens;  // directional sensitivities of this shot's channels (device) or null
+        const GaugeDev *gauge;  // parameter key das_gauge_length (G > 1): the channels' taps (device), else null
+        const InjDev *ginj;     // ... and their adjoint plan (gradient calls)
         bool scratch;
         LineRec line;
         float *state;  // [5 fields | 8 memory variables] of this lane
@@ -98,6 +102,7 @@ class Session {
     void forward_init(const ShotCtx &x);
     void forward_step(const Call &c, const ShotCtx &x, int it, bool inl);
     void record_column(const ShotCtx &x, int column);
+    const GaugeDev &gauge_taps(const ShotCtx &x);  // a gauge shot's taps on the device, built on first use (das_gauge.hpp)
     void residual(const ShotCtx &x);
     void residual_conditioned(const Call &c, const ShotCtx &x);
     // what a forward pass leaves behind, by kind of call
@@ -107,6 +112,7 @@ class Session {
     // backward pass of one shot, stream form (libCUFD.cu:500-675)
     void backward_init(const BwdLane &L);
     void backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it);
+    void inject_column(const ShotCtx &x, const BwdLane &L, const float *res_t);
     void backward(Call &c, const ShotCtx &x);
     // the same pass as ONE persistent launch (option bwd_fuse = 4; kernels.hip k_bwd_persist)
     struct Persist;
@@ -116,6 +122,7 @@ class Session {
     bool batched_backward_persistent(Call &c, const std::vector<ShotDev> &tab, int first, int nbb);
     bool persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st);
     const InjArgs *persist_inject(const Call &c, const ShotCtx &x, hipStream_t st);
+    InjDev &inj_dev(const ShotCtx &x);
     void persist_demote(Persist &k, const std::string &why, int retry_in);
     void persist_check_pass(Persist &k);
     hipEvent_t *probe_pair(Call &c, int it);
@@ -214,6 +221,7 @@ class Session {
     // copies, built on first use) and the pass's residual folded per target cell [nSteps][ntgt]
     struct InjDev {
         int *lookup = nullptr, *tgt_start = nullptr, *ent_rec = nullptr;
+        int *tgt_cell = nullptr, *tgt_field = nullptr;  // gauge shots: per target its flat cell and field (k_inject_gauge)
         InjSeg *segs = nullptr;
         float *ent_w = nullptr;
         std::vector<int> target_segs;       // row segments (z * nseg + xs) that hold target cells
@@ -222,6 +230,16 @@ class Session {
         int ntgt = 0, tile_gen = -1;
     };
     std::map<int, InjDev> inj_;
+    // gauge channels (parameter key das_gauge_length): per shot its taps (device copies, built on first use); the batched schedule's
+    // side table of the call's shots (GaugeShotDev, indexed like d_shots_) and its host copy
+    struct GaugeDev {
+        int *start = nullptr, *cell = nullptr, *field = nullptr;
+        float *w = nullptr;
+    };
+    std::map<int, GaugeDev> gauge_;
+    GaugeShotDev *d_gauge_ = nullptr;
+    int gauge_cap_ = 0;
+    std::vector<GaugeShotDev> gauge_tab_;
     float *inj_val_ = nullptr;
     size_t inj_val_len_ = 0;
     long long persist_steps_ = 0;

@@ -34,6 +34,8 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
     const size_t n = cells_;
     const bool lf = c.opt.line_fuse != 0;
     std::vector<ShotDev> tab(c.group_size);
+    gauge_tab_.assign(c.group_size, GaugeShotDev{});
+    bool gauged = false;
     for (int is = 0; is < c.group_size; is++) {
         const ShotCtx x = batch_ctx(c, is, Bf, false);
         const BLane &LB = bl_[(is % Bf) % Bb];  // backward lane of this shot inside its sub-batch
@@ -54,13 +56,42 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
         d.lr_x0 = x.line.x0;
         d.lr_n = lf ? x.line.n : 0;
         d.comps = x.comps | ((lf && x.line.n > 0 && !(x.comps & 1)) ? 16 : 0);  // bit 16: sample the line inside k_stress
-        d.nrec = x.nrec;
+        d.nrec = x.gauge ? 0 : x.nrec;  // gauge channels: the generic receiver kernels skip the shot, the gauge twins serve it (side table)
         d.src_rxz = (float)x.sh->src_rxz;
         d.quiet = x.quiet;
         d.rec = x.rec;
         d.sens = x.sens;
+        GaugeShotDev &q = gauge_tab_[is];
+        if (x.gauge) {
+            q.nrec = x.nrec;
+            q.comps = x.comps;
+            q.rec = x.rec;
+            q.tap_start = x.gauge->start;
+            q.tap_cell = x.gauge->cell;
+            q.tap_field = x.gauge->field;
+            q.tap_w = x.gauge->w;
+            gauged = true;
+        }
+        if (x.ginj) {
+            q.ntgt = x.ginj->ntgt;
+            q.tgt_start = x.ginj->tgt_start;
+            q.tgt_cell = x.ginj->tgt_cell;
+            q.tgt_field = x.ginj->tgt_field;
+            q.ent_rec = x.ginj->ent_rec;
+            q.ent_w = x.ginj->ent_w;
+        }
     }
     HIP_OK(hipMemcpyAsync(d_shots_, tab.data(), tab.size() * sizeof(ShotDev), hipMemcpyHostToDevice, c.st));
+    if (gauged) {  // the side table of the gauge twins
+        if (c.group_size > gauge_cap_) {
+            if (d_gauge_) (void)hipFree(d_gauge_);
+            d_gauge_ = nullptr;
+            HIP_OK(dev_malloc((void **)&d_gauge_, (size_t)c.group_size * sizeof(GaugeShotDev)));
+            device_bytes_ += (long long)((size_t)(c.group_size - gauge_cap_) * sizeof(GaugeShotDev));
+            gauge_cap_ = c.group_size;
+        }
+        HIP_OK(hipMemcpyAsync(d_gauge_, gauge_tab_.data(), gauge_tab_.size() * sizeof(GaugeShotDev), hipMemcpyHostToDevice, c.st));
+    }
     HIP_OK(hipStreamSynchronize(c.st));  // `tab` and `stf_rows` are pageable host memory
     return tab;
 }
@@ -102,6 +133,11 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
             if (!(tab[is0 + k].comps & 16) && tab[is0 + k].nrec > 0) return true;
         return false;
     };
+    auto gauge_nrec = [&](int a0, int a1) {  // the most gauge channels of a shot in [a0, a1) (0: none)
+        int m = 0;
+        for (int k = a0; k < a1; k++) m = std::max(m, gauge_tab_[is0 + k].nrec);
+        return m;
+    };
     hipStream_t sub[kMaxLanes] = {};
     batch_streams(st, ns, sub);
     for (int it = 0; it <= nSteps - 2; it++)
@@ -112,6 +148,10 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
             launches_ += 2;
             if (general(a0, a1)) {  // general receivers: ONE launch samples the new state of the sub-batch's shots into column it + 1
                 launch_record_batch(sub[q], g_, d_shots_ + is0 + a0, a1 - a0, survey_.max_nrec, cells_, data_len_, it + 1);
+                launches_++;
+            }
+            if (const int gn = gauge_nrec(a0, a1)) {  // gauge channels: their twin, from the side table
+                launch_record_gauge_batch(sub[q], d_shots_ + is0 + a0, d_gauge_ + is0 + a0, a1 - a0, gn, cells_, data_len_, it + 1);
                 launches_++;
             }
         }
@@ -148,8 +188,13 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
     // An experiment that lost, kept in the -DSEPFWI_PROBES build (option pk_ms; profiles/EXPERIMENTS.md #48): the whole sub-batch as ONE
     // persistent launch (the multi-shot loop, session_persist.cpp) where every shot's channels are a fused line (or absent).  On every
     // grid that takes the batched schedule the per-step launches below are faster, also against the loop without any synchronisation.
+    auto gauge_ntgt = [&](int a0, int a1) {  // the most adjoint targets of a gauge shot in [a0, a1) (0: none)
+        int m = 0;
+        for (int k = a0; k < a1; k++) m = std::max(m, gauge_tab_[first + k].ntgt);
+        return m;
+    };
     bool lines = opt.pk_ms != 0 && opt.line_fuse != 0;
-    for (int k = 0; k < nbb; k++) lines = lines && (tab[first + k].nrec == 0 || tab[first + k].lr_n > 0);
+    for (int k = 0; k < nbb; k++) lines = lines && (tab[first + k].nrec == 0 || tab[first + k].lr_n > 0) && gauge_tab_[first + k].nrec == 0;
     const bool looped = lines && persist_prepare(pk_ms_, opt, nbb) && batched_backward_persistent(c, tab, first, nbb);
     hipStream_t sub[kMaxLanes] = {};
     if (looped) nsb = 1;
@@ -166,6 +211,10 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
             launches_ += 2;
             if (general(a0, a1)) {  // res_injection_exx / _ezz for the sub-batch's shots whose channels are not a fused line: ONE launch
                 launch_inject_batch(sub[q], g, d_shots_ + first + a0, a1 - a0, survey_.max_nrec, n, it);
+                launches_++;
+            }
+            if (const int gt = gauge_ntgt(a0, a1)) {  // gauge channels: their twin, from the side table
+                launch_inject_gauge_batch(sub[q], d_shots_ + first + a0, d_gauge_ + first + a0, a1 - a0, gt, n, it);
                 launches_++;
             }
         }

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "das_gauge.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "inject_plan.hpp"
@@ -139,32 +140,46 @@ bool Session::persist_prepare(Persist &k, const KernelOptions &opt, int nshots) 
     return true;
 }
 
+// The injection plan of a shot whose receivers are not a fused horizontal line, built once per session and shot: from its channels
+// (make_inject_plan, inject_plan.hpp) or, with a gauge length, from its taps (make_gauge_plan, das_gauge.hpp -- which also gives the
+// per-target cells of k_inject_gauge).
+Session::InjDev &Session::inj_dev(const ShotCtx &x) {
+    auto it = inj_.find(x.id);
+    if (it != inj_.end()) return it->second;
+    const Shot &sh = *x.sh;
+    const float *sens = sh.sens.empty() ? nullptr : sh.sens.data();
+    std::vector<int> tgt_cell, tgt_field;
+    const InjectPlan p = x.gauge ? make_gauge_plan(make_gauge_taps(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, par_.gauge),
+                                                   g_.nzc, g_.nx, g_.pitch, &tgt_cell, &tgt_field)
+                                 : make_inject_plan(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, g_.nzc, g_.nx);
+    InjDev d;
+    d.ntgt = p.ntgt;
+    auto up = [&](auto **dst, const auto &v) {
+        HIP_OK(dev_malloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(v[0])));
+        if (!v.empty()) HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+        device_bytes_ += (long long)(v.size() * sizeof(v[0]));
+    };
+    up(&d.lookup, p.lookup);
+    up(&d.segs, p.segs);
+    up(&d.tgt_start, p.tgt_start);
+    up(&d.ent_rec, p.ent_rec);
+    up(&d.ent_w, p.ent_w);
+    if (x.gauge) {
+        up(&d.tgt_cell, tgt_cell);
+        up(&d.tgt_field, tgt_field);
+    }
+    for (size_t sidx = 0; sidx < p.lookup.size(); sidx++)
+        if (p.lookup[sidx] >= 0) d.target_segs.push_back((int)sidx);  // (which tiles own them depends on the tiling: persist_inject)
+    return inj_.emplace(x.id, d).first->second;
+}
+
 // Adjoint source of a shot whose receivers are not a fused horizontal line (strided or scattered channels, a vertical fibre,
-// directional sensitivities): the injection plan of the shot (built once per session and shot, inject_plan.hpp) and the residual of
-// THIS pass folded per target cell and time step (one launch).  Fills a.inj; leaves it empty for a fused line or no receivers.
+// directional sensitivities, gauge channels): the injection plan of the shot (inj_dev) and the residual of THIS pass folded per target
+// cell and time step (one launch).  Fills a.inj; leaves it empty for a fused line or no receivers.
 const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStream_t st) {
     if (x.nrec == 0 || (x.line.n > 0 && c.opt.line_fuse != 0)) return nullptr;
+    inj_dev(x);  // (built on first use)
     auto it = inj_.find(x.id);
-    if (it == inj_.end()) {
-        const Shot &sh = *x.sh;
-        const InjectPlan p = make_inject_plan(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sh.sens.empty() ? nullptr : sh.sens.data(), par_.fiber != 0,
-                                              g_.dx * g_.rdz, g_.nzc, g_.nx);
-        InjDev d;
-        d.ntgt = p.ntgt;
-        auto up = [&](auto **dst, const auto &v) {
-            HIP_OK(dev_malloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(v[0])));
-            if (!v.empty()) HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-            device_bytes_ += (long long)(v.size() * sizeof(v[0]));
-        };
-        up(&d.lookup, p.lookup);
-        up(&d.segs, p.segs);
-        up(&d.tgt_start, p.tgt_start);
-        up(&d.ent_rec, p.ent_rec);
-        up(&d.ent_w, p.ent_w);
-        for (size_t sidx = 0; sidx < p.lookup.size(); sidx++)
-            if (p.lookup[sidx] >= 0) d.target_segs.push_back((int)sidx);  // (which tiles own them depends on the tiling: below)
-        it = inj_.emplace(x.id, d).first;
-    }
     const InjDev &d = it->second;
     const size_t need = (size_t)par_.nSteps * (size_t)std::max(1, d.ntgt);
     if (need > inj_val_len_) {

@@ -6,11 +6,13 @@
 //                                       session_persist.cpp
 //   run_streams                         the stream schedule of a call's shots; the batched one: session_batched.cpp
 //   write_outputs                       gradient finalisation and read-back (libCUFD.cu:710-724,775-779)
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
+#include "das_gauge.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
@@ -126,14 +128,20 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     x.d_obs = (c.if_res && with_obs) ? obs_->acquire(x.id, x.nrec, c.st) : nullptr;
     x.scratch = c.with_adj && !par_.scratch_dir_name.empty();  // libCUFD.cu:732-752
     x.comps = (c.if_res || c.to_store) ? (x.scratch ? 9 : 8) : 15;
-    // horizontal line of consecutive channels inside the computed region?
+    // horizontal line of consecutive channels inside the computed region?  (channels with a gauge length never are: they are not
+    // sampled at their own cells, so the field kernels cannot take them, and quiet_skip stays off for them)
     const Shot &sh = *x.sh;
-    bool is_line = par_.fiber == 0 && !x.sens && x.nrec > 0 && sh.z_rec[0] >= 2 && sh.z_rec[0] <= g.nzc - 3 && sh.x_rec[0] >= 3 && sh.x_rec[0] + x.nrec - 1 <= g.nx - 3;
+    const bool gauge = par_.gauge > 1 && x.nrec > 0;
+    bool is_line = !gauge && par_.fiber == 0 && !x.sens && x.nrec > 0 && sh.z_rec[0] >= 2 && sh.z_rec[0] <= g.nzc - 3 && sh.x_rec[0] >= 3 && sh.x_rec[0] + x.nrec - 1 <= g.nx - 3;
     for (int r = 1; r < x.nrec && is_line; r++) is_line = (sh.z_rec[r] == sh.z_rec[0] && sh.x_rec[r] == sh.x_rec[0] + r);
     if (is_line) {
         x.line.z = sh.z_rec[0];
         x.line.x0 = sh.x_rec[0];
         x.line.n = x.nrec;
+    }
+    if (gauge) {
+        x.gauge = &gauge_taps(x);
+        if (c.with_adj) x.ginj = &inj_dev(x);
     }
     x.quiet = quiet_wanted(c, x) ? quiet_slot(lane) : nullptr;
     use_state(x, lane ? xl_[lane].state : state_);
@@ -159,8 +167,34 @@ void Session::forward_init(const ShotCtx &x) {
 // seismogram column `column` of the shot's present state (recording*, utilities.cu:593-602,645-703)
 void Session::record_column(const ShotCtx &x, int column) {
     const size_t col = (size_t)column * x.nrec;
-    launch_record(x.st, g_, x.fld, x.nrec, x.rec, syn_of(x, 0) + col, syn_of(x, 1) + col, syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps, x.sens);
+    if (x.gauge)
+        launch_record_gauge(x.st, x.fld, x.nrec, x.rec, x.gauge->start, x.gauge->cell, x.gauge->field, x.gauge->w, syn_of(x, 0) + col, syn_of(x, 1) + col,
+                            syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps);
+    else
+        launch_record(x.st, g_, x.fld, x.nrec, x.rec, syn_of(x, 0) + col, syn_of(x, 1) + col, syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps, x.sens);
     launches_++;
+}
+
+// taps of a shot's gauge channels (das_gauge.hpp), uploaded once per session and shot
+const Session::GaugeDev &Session::gauge_taps(const ShotCtx &x) {
+    auto it = gauge_.find(x.id);
+    if (it != gauge_.end()) return it->second;
+    const Shot &sh = *x.sh;
+    const GaugeTaps t = make_gauge_taps(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sh.sens.empty() ? nullptr : sh.sens.data(), par_.fiber != 0,
+                                        g_.dx * g_.rdz, par_.gauge);
+    std::vector<int> cell(t.w.size());
+    for (size_t e = 0; e < cell.size(); e++) cell[e] = t.z[e] * g_.pitch + t.x[e];
+    GaugeDev d;
+    auto up = [&](auto **dst, const auto &v) {
+        HIP_OK(dev_malloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(v[0])));
+        if (!v.empty()) HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+        device_bytes_ += (long long)(v.size() * sizeof(v[0]));
+    };
+    up(&d.start, t.start);
+    up(&d.cell, cell);
+    up(&d.field, t.field);
+    up(&d.w, t.w);
+    return gauge_.emplace(x.id, d).first->second;
 }
 
 // one forward time step (libCUFD.cu:268-332); inl: the line of channels is sampled inside k_stress
@@ -325,16 +359,24 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
         launch_bwd_a(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, adj, L.acc);
         launch_bwd_b(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, (float)sh.src_rxz, sg, adj, L.acc, lr, ev ? ev[0] : nullptr,
                      ev ? ev[1] : nullptr);
-        if (!inj_inl) launch_inject(L.s, g, L.adj, x.nrec, x.rec, res_t, x.sens);
+        if (!inj_inl) inject_column(x, L, res_t);
         launches_ += inj_inl ? 2 : 3;
     } else {  // the reference's launch structure
         launch_velocity_rev(L.s, gs, opt, x.fld, md_, pc_, frame_t, sh.z_src, sh.x_src, (float)sh.src_rxz, sg, L.adj, L.acc);
         launch_stress_rev(L.s, gs, opt, x.fld, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, L.adj, L.acc);
         launch_velocity_adj(L.s, g, opt, L.adj, L.bm, md_, pc_);
-        launch_inject(L.s, g, L.adj, x.nrec, x.rec, res_t, x.sens);
+        inject_column(x, L, res_t);
         launch_stress_adj(L.s, g, opt, L.adj, L.bm, md_, pc_);
         launches_ += 5;
     }
+}
+
+// this step's adjoint source: res_injection_exx / _ezz per channel (k_inject), or a gauge shot's plan, one add per target (k_inject_gauge)
+void Session::inject_column(const ShotCtx &x, const BwdLane &L, const float *res_t) {
+    if (x.ginj)
+        launch_inject_gauge(L.s, L.adj, x.ginj->ntgt, res_t, x.ginj->tgt_start, x.ginj->tgt_cell, x.ginj->tgt_field, x.ginj->ent_rec, x.ginj->ent_w);
+    else
+        launch_inject(L.s, g_, L.adj, x.nrec, x.rec, res_t, x.sens);
 }
 
 // The backward pass of one shot: ONE persistent launch where the configuration allows it (session_persist.cpp), else -- or when the

@@ -35,12 +35,14 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
-            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None):
+            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
     reference only reaches by editing libCUFD.cu).  The key is written only when it is not the default, so default
-    files stay byte-identical to the reference's."""
+    files stay byte-identical to the reference's.
+    das_gauge_length (extension) [m]: every channel records the mean axial strain over this gauge along the fibre, a whole multiple
+    of the grid spacing along it (csrc/das_gauge.hpp); written only when given."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
     if if_win:
@@ -58,6 +60,10 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
         if das_fiber != "vertical":
             raise ValueError("das_fiber must be 'horizontal' or 'vertical'")
         para["das_fiber"] = das_fiber
+    if das_gauge_length is not None:
+        if not das_gauge_length > 0:
+            raise ValueError("das_gauge_length must be > 0")
+        para["das_gauge_length"] = float(das_gauge_length)
     if scratch_dir_name != "":
         para["scratch_dir_name"] = scratch_dir_name
         os.makedirs(scratch_dir_name, exist_ok=True)
