@@ -10,6 +10,9 @@ Cases (CASES below):
   vertical     a vertical fibre (ezz) in column nx/2 + 3, the source 20 columns beside it
   directional  every other cell of a horizontal line, every channel its own direction cosines
   bandpass     the channels of `stride3` with the residual band-passed (para "filter" = [3, 7, 40, 60] Hz)
+  gauge4       the channels of `stride3` with a gauge length of four cells (para "das_gauge_length" = 4 dx): even G, five members,
+               neighbouring gauges overlap, four taps per channel, targets on both sides of 64-column segment boundaries.  The oracle
+               runs the expanded member survey (tests/gauge_ref.py); observed data are the true model's gauge gathers
 
 Geometry: the source and the horizontal lines sit at one of the seams between the persistent loop's eight XCD bands (padded row
 round(b nzc / 8), persist_plan.cpp), the source two rows above it and the line on its first row below, so the wave and the
@@ -40,7 +43,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "sep-2023_amd"), os.path.join(ROOT, "te
 import problems as P  # noqa: E402
 
 NZ, NX, NPML, NSTEPS = 1000, 2000, 32, 400
-CASES = ("stride3", "vertical", "directional", "bandpass")
+CASES = ("stride3", "vertical", "directional", "bandpass", "gauge4")
+GAUGE = 4
 FILTER = [3.0, 7.0, 40.0, 60.0]
 NBAND = 8                     # XCD bands of the persistent loop on an MI355X
 SEAM_BAND = 4                 # the seam between bands 3 and 4 (mid-depth: the make_problem anomalies are there)
@@ -66,7 +70,7 @@ def geometry(case, nsteps=NSTEPS):
     seam = seams(NZ + 2 * NPML + nPad, nPad)[SEAM_BAND - 1]
     src_z, line_z = seam - 2 - NPML, seam - NPML          # unpadded rows: source in band SEAM_BAND-1, line on band SEAM_BAND's first row
     kw = dict(nz=NZ, nx=NX, nPml=NPML, nSteps=nsteps, nshots=1, hetero=True, seed=3)
-    if case in ("stride3", "bandpass"):
+    if case in ("stride3", "bandpass", "gauge4"):
         kw.update(nrec_stride=3, rec_z=line_z, src_z=src_z, src_x=[NX // 2])
     elif case == "vertical":
         kw.update(das_fiber="vertical", src_z=src_z, src_x=[NX // 2 + 3 - 20])
@@ -89,6 +93,10 @@ def make_case(workdir, case, nsteps=NSTEPS):
     pb["lame_init"] = ((lam * 1.05).contiguous(), mu, den)
     if case == "bandpass":
         pb["para"]["filter"] = FILTER
+        with open(pb["para_fname"], "w") as fp:
+            json.dump(pb["para"], fp)
+    if case == "gauge4":
+        pb["para"]["das_gauge_length"] = GAUGE * pb["para"]["dx"]
         with open(pb["para_fname"], "w") as fp:
             json.dump(pb["para"], fp)
     sh = pb["survey"]["shot0"]
@@ -125,18 +133,28 @@ def run(case, nsteps, out):
         stf = pb["Stf"].numpy()
         t0 = time.time()
         lam, mu, den = [t.numpy() for t in pb["lame_true"]]
-        obs = O.cufd(lam, mu, den, stf, 2, [0], plain, survey)["syn"]
+        if case == "gauge4":
+            import gauge_ref as R
+            obs_ett = R.forward(O, (lam, mu, den), stf, [0], para, survey, GAUGE)[0][0].astype(np.float32)
+        else:
+            obs = O.cufd(lam, mu, den, stf, 2, [0], plain, survey)["syn"]
+            obs_ett = obs[0, 3]
         print("%s observe: %.1f s" % (case, time.time() - t0), flush=True)
         t0 = time.time()
         lam, mu, den = [t.numpy() for t in pb["lame_init"]]
-        ref = O.cufd(lam, mu, den, stf, 1, [0], para, survey, obs=obs)
+        if case == "gauge4":
+            ref = R.reference(O, (lam, mu, den), stf, [0], para, survey, GAUGE, [obs_ett])
+            syn_ett = ref["gauge"][0].astype(np.float32)
+        else:
+            ref = O.cufd(lam, mu, den, stf, 1, [0], para, survey, obs=obs)
+            syn_ett = ref["syn"][0, 3]
         print("%s gradient: %.1f s, misfit %.6e" % (case, time.time() - t0, ref["misfit"]), flush=True)
         ch = channels(pb["nrec"])
-        r = obs[0, 3].astype(np.float64) - ref["syn"][0, 3].astype(np.float64)
+        r = obs_ett.astype(np.float64) - syn_ett.astype(np.float64)
         out_ = dict(misfit=np.float64(ref["misfit"]), gStf=ref["gStf"][0], digest=digest(pb), channels=ch, decim=DECIM,
                     seam=np.int64(pb["seam"]), win_src=np.array(pb["win_src"]), win_seam=np.array(pb["win_seam"]),
-                    obs_ett=obs[0, 3][ch], syn_ett=ref["syn"][0, 3][ch],
-                    obs_ett_norm=np.float64(np.linalg.norm(obs[0, 3].astype(np.float64))),
+                    obs_ett=obs_ett[ch], syn_ett=syn_ett[ch],
+                    obs_ett_norm=np.float64(np.linalg.norm(obs_ett.astype(np.float64))),
                     res_energy=(r * r).sum(axis=1))                 # per channel, unconditioned (obs - syn)
         for k in ("gLambda", "gMu", "gDen"):
             a = ref[k]

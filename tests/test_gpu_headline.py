@@ -425,13 +425,14 @@ def test_grid_seven_times_the_headline_matches_oracle(tmp_path, oracle, hip_ops)
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass"])
+@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass", "gauge4"])
 def test_headline_grid_general_receivers(tmp_path, hip_ops, case):
     """Receivers that are not a fused horizontal line on the headline grid (2000 x 1000 + 32-cell layers), one shot, 400 steps, with
     the default options: the backward pass is the persistent loop in STRIP order (the tile-size rule), and the adjoint source is
     folded per target cell (k_inject_values) and added by the GINJ branch, across the seam of two XCD bands where the source and the
     channels sit.  Cases: channels every third cell, a vertical fibre crossing every seam, directional channels every other cell, the
-    band-passed residual (the full-width hipFFT chain) -- against the CPU oracle (scripts/make_golden_headline_receivers.py), against
+    band-passed residual (the full-width hipFFT chain), the channels of the first case with a gauge length of four cells (overlapping
+    gauges, targets on both sides of the 64-column segment boundaries; the oracle ran the member survey, tests/gauge_ref.py) -- against the CPU oracle (scripts/make_golden_headline_receivers.py), against
     the two-launch step (k_inject's atomics: round-off), and against the same loop forced to edge-first order (bit for bit)."""
     sys.path.insert(0, ROOT)
     import scripts.make_golden_headline_receivers as mg
@@ -499,6 +500,9 @@ def test_headline_grid_general_receivers(tmp_path, hip_ops, case):
     assert out["gStf"] <= 1e-3, (case, out)
     assert float(two[0]) == float(m), (case, float(two[0]), float(m))
     assert max(out["vs_two_launch"]) <= 2e-6, (case, out["vs_two_launch"])
+    if case == "gauge4":     # gauge targets are distinct and get one add per step in both schedules (no atomics): bit for bit
+        for k, (a, b) in enumerate(zip((m, gL, gM, gD, gS), two)):
+            assert torch.equal(a, b), (case, "two-launch", k, float((a - b).abs().max()))
     for name in ("strip", "edge-first"):
         for k, (a, b) in enumerate(zip(order[name], (m, gL, gM, gD, gS))):
             assert torch.equal(a, b), (case, name, k, float((a - b).abs().max()))

@@ -233,7 +233,7 @@ def test_directional_das_gradient_is_consistent_with_finite_differences(oracle, 
     assert abs(fd - gd) <= 0.05 * abs(gd), (fd, gd)
 
 
-@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass"])
+@pytest.mark.parametrize("case", ["stride3", "vertical", "directional", "bandpass", "gauge4"])
 def test_headline_receivers_goldens_match_their_problems(tmp_path, case):
     """tests/golden/oracle_headline_receivers_<case>.npz (the GPU test tests/test_gpu_headline.py::test_headline_grid_general_receivers
     compares against them) belong to the problems scripts/make_golden_headline_receivers.py builds today: same input digest (models,
@@ -259,6 +259,7 @@ def test_headline_receivers_goldens_match_their_problems(tmp_path, case):
     else:
         assert np.all(z_rec == seam)                                       # the line on the first row below it
     assert "filter" in pb["para"] if case == "bandpass" else "filter" not in pb["para"]
+    assert pb["para"].get("das_gauge_length") == (mg.GAUGE * pb["para"]["dx"] if case == "gauge4" else None)
     for w in ("win_src", "win_seam"):
         assert tuple(int(v) for v in G[w]) == pb[w]
         z0, z1, x0, x1 = pb[w]
