@@ -75,6 +75,15 @@ int sepfwi_device_count(void);
  *                horizontal fibre (L / dz along a vertical one; directional channels take the das_fiber axis), its adjoint
  *                source the exact transpose.  L must be a whole multiple of the spacing (SEPFWI_EJSON otherwise), every
  *                member cell of a gauge must lie where a channel may (SEPFWI_EINVAL).  Absent or G = 1: the one-cell channel.
+ *                "misfit_w_ett" (default 1), "misfit_w_vx" (0), "misfit_w_vz" (0) -- weights of the axial-strain, vx and vz residuals:
+ *                  misfit = 0.5 sum_shots ( w_ett sum r_ett^2 + w_vx sum r_vx^2 + w_vz sum r_vz^2 ),  r_c = obs_c - syn_c
+ *                (time sample 0 forced to 0); vx / vz are sampled at the channel's own cell, the adjoint source of component c is
+ *                w_c r_c added to vx_adj / vz_adj of that cell where the strain residual enters (Src/libCUFD.cu:600-607; the
+ *                reference ships res_injection_vx / _vz, Src/utilities.cu:656-689, and never launches them: an extension that no
+ *                reference run pins).  Each weight finite and >= 0, not all zero (SEPFWI_EJSON).  Observed data of a component with a
+ *                weight come from Shot_{vx,vz,ett}{id}.bin, sepfwi_set_observed_component or calc_id 3; a component with weight 0
+ *                is never read.  misfit_w_vx / misfit_w_vz > 0 with "obs_pack_fname", and any weights other than (1, 0, 0) with a
+ *                live conditioning key, are refused (SEPFWI_EINVAL).  Absent or (1, 0, 0): bit for bit the axial-strain misfit.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.
@@ -106,6 +115,19 @@ void sepfwi_release_all(void);
  * shot until sepfwi_invalidate_observed() or sepfwi_release_all().  No file is needed for shots set this way.
  */
 int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const float *ett, int nrec, int nSteps);
+
+/*
+ * The same for one component of a joint misfit (parameter keys misfit_w_*): comp 1 (vx), 2 (vz) or 3 (ett, what
+ * sepfwi_set_observed means) -- the reference's component order, Shot_{vx,vz,ett}{id}.bin.  Any other comp: SEPFWI_EINVAL.
+ */
+int sepfwi_set_observed_component(const char *para_fname, int gpu_id, int shot_id, int comp, const float *data, int nrec, int nSteps);
+
+/*
+ * The unweighted parts 0.5 sum_shots sum r_c^2 of the last misfit or gradient call of (para_fname, gpu_id), for (vx, vz, ett) -- what
+ * a user needs to choose the weights.  The entry of a component with weight 0 is 0.  Per process, not all-reduced.  SEPFWI_EINVAL
+ * without a session.
+ */
+int sepfwi_get_misfit_parts(const char *para_fname, int gpu_id, double parts[3]);
 
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--shots", type=int, default=3)
     ap.add_argument("--rec-stride", type=int, default=1, help="a channel every N cells (N > 1: not a fused line -- k_inject, or the loop's general injection)")
     ap.add_argument("--das-gauge-length", type=float, default=None, help="parameter key das_gauge_length [m]: every channel the mean strain over this gauge")
+    ap.add_argument("--misfit-weights", default=None, help="ett,vx,vz: parameter keys misfit_w_* (a joint DAS + geophone misfit; observed data go through the store)")
     a = ap.parse_args()
     _native._active = "probes"   # the tuning knobs exist only in the -DSEPFWI_PROBES build of the library
     _native.build(variant="probes")
@@ -44,6 +45,14 @@ def main():
             with open(pb["para_fname"]) as fp:
                 para = json.load(fp)
             para["das_gauge_length"] = a.das_gauge_length
+            with open(pb["para_fname"], "w") as fp:
+                json.dump(para, fp)
+        if a.misfit_weights is not None:
+            w = [float(v) for v in a.misfit_weights.split(",")]
+            assert len(w) == 3, "--misfit-weights ett,vx,vz"
+            with open(pb["para_fname"]) as fp:
+                para = json.load(fp)
+            para.update(misfit_w_ett=w[0], misfit_w_vx=w[1], misfit_w_vz=w[2])
             with open(pb["para_fname"], "w") as fp:
                 json.dump(para, fp)
         lt, mt, dt_ = [t.to(dev) for t in pb["lame_true"]]

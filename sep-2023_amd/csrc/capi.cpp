@@ -91,6 +91,23 @@ int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const f
     });
 }
 
+int sepfwi_set_observed_component(const char *para_fname, int gpu_id, int shot_id, int comp, const float *data, int nrec, int nSteps) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (comp < 1 || comp > 3) throw std::invalid_argument("set_observed_component: comp must be 1 (vx), 2 (vz) or 3 (ett), got " + std::to_string(comp));
+        get_session(para_fname, gpu_id)->set_observed(shot_id, data, nrec, nSteps, comp);
+    });
+}
+
+int sepfwi_get_misfit_parts(const char *para_fname, int gpu_id, double parts[3]) {
+    return guarded([&] {
+        if (!para_fname || !parts) throw std::invalid_argument("bad arguments");
+        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
+        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
+        s->misfit_parts(parts);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

@@ -81,6 +81,30 @@ Params parse_params(const std::string &text) {
             throw std::runtime_error("parameter JSON: das_gauge_length must be a positive whole multiple of the grid spacing along the fibre");
         p.gauge = (int)G;
     }
+    // weights of the three residuals that can enter the misfit (geophone.hpp)
+    auto weight = [&](const char *key, float *w) {
+        if (!j.has(key)) return;
+        const double v = j.at(key).as_number(key);
+        if (!std::isfinite(v) || v < 0.0 || v > 3.0e38) throw  // (finite as a float too)
+            std::runtime_error(std::string("parameter JSON: ") + key + " must be finite and >= 0");
+        *w = (float)v;
+    };
+    weight("misfit_w_ett", &p.w_ett);
+    weight("misfit_w_vx", &p.w_vx);
+    weight("misfit_w_vz", &p.w_vz);
+    if (p.w_ett == 0.0f && p.w_vx == 0.0f && p.w_vz == 0.0f)
+        throw std::runtime_error("parameter JSON: misfit_w_ett, misfit_w_vx and misfit_w_vz must not all be zero");
+    if (p.w_vx > 0.0f || p.w_vz > 0.0f) {
+        const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : "misfit_w_vz";
+        if (!p.obs_pack_fname.empty())
+            throw std::invalid_argument(std::string("parameter file: ") + key + " > 0 together with obs_pack_fname is not supported (the packed file holds axial strain only)");
+    }
+    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update)) {
+        const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
+        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : "if_src_update"));
+        throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
+                                    " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
+    }
     return p;
 }
 

@@ -32,6 +32,11 @@ struct Params {
     // optional key "das_gauge_length" [m] (das_gauge.hpp): every channel records the mean axial strain over G = round(L / dx) cells
     // along a horizontal fibre, round(L / dz) along a vertical one.  1 (absent): the one-cell channel.
     int gauge = 1;
+    // optional keys "misfit_w_ett" / "misfit_w_vx" / "misfit_w_vz" (geophone.hpp): weights of the axial-strain, vx and vz residuals in
+    // misfit and adjoint source.  Absent or (1, 0, 0): the axial-strain misfit of the reference's driver, on the path it always took.
+    float w_ett = 1.0f, w_vx = 0.0f, w_vz = 0.0f;
+    bool joint() const { return !(w_ett == 1.0f && w_vx == 0.0f && w_vz == 0.0f); }  // the joint path (geophone.hip) serves the call
+    float weight(int comp) const { return comp == 1 ? w_vx : (comp == 2 ? w_vz : (comp == 3 ? w_ett : 0.0f)); }  // comp: 1 vx, 2 vz, 3 ett
 };
 
 struct Shot {

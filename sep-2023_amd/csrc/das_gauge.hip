@@ -65,7 +65,7 @@ __global__ void k_inject_gauge_batch(const ShotDev *__restrict__ shots, const Ga
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= q.ntgt) return;
     const ShotDev &s = shots[blockIdx.y];
-    inject_gauge_one(s.adj, s.adj + n, t, s.res + (size_t)it * (size_t)q.nrec, q.tgt_start, q.tgt_cell, q.tgt_field, q.ent_rec, q.ent_w);
+    inject_gauge_one(s.adj, s.adj + n, t, s.res + (size_t)it * (size_t)q.nres, q.tgt_start, q.tgt_cell, q.tgt_field, q.ent_rec, q.ent_w);
 }
 
 void launch_record_gauge(hipStream_t st, Fields f, int nrec, const int *rec, const int *tap_start, const int *tap_cell, const int *tap_field,

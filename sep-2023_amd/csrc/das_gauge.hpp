@@ -47,9 +47,11 @@ void check_gauge_members(const Params &par, const Survey &survey, int nzc, int n
 
 // Device-side description of one shot's gauge channels for the batched schedule (the side table of ShotDev, indexed alike).  A shot
 // without gauge channels has nrec == ntgt == 0.  Its fields, seismograms, adjoint fields and residual are those of its ShotDev entry,
-// whose own nrec is 0 for a gauge shot so that the generic receiver kernels skip it.
+// whose own nrec is 0 for a gauge shot so that the generic receiver kernels skip it.  A joint DAS + geophone misfit (geophone.hpp)
+// injects every shot through the plan part of its entry (nrec stays 0 there unless the shot has gauge channels).
 struct GaugeShotDev {
-    int nrec, ntgt, comps, pad;
+    int nrec, ntgt, comps;
+    int nres;                                              // row length of the adjoint-source array: nrec, or the concatenated length of a joint misfit (geophone.hpp)
     const int *rec;                                        // [nrec] the channels' own cells (pr / vx / vz)
     const int *tap_start, *tap_cell, *tap_field;           // taps, CSR over channels
     const float *tap_w;

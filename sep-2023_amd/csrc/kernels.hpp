@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "das_gauge.hpp"
+#include "geophone.hpp"
 #include "fwi_types.hpp"
 
 namespace sepfwi {
@@ -104,6 +105,10 @@ void launch_inject_gauge(hipStream_t st, Fields adj, int ntgt, const float *res_
                          const int *ent_rec, const float *ent_w);
 void launch_record_gauge_batch(hipStream_t st, const ShotDev *shots, const GaugeShotDev *gs, int nb, int max_nrec, size_t n, size_t data_len, int column);
 void launch_inject_gauge_batch(hipStream_t st, const ShotDev *shots, const GaugeShotDev *gs, int nb, int max_ntgt, size_t n, int it);
+// joint DAS + geophone misfit (geophone.hip): the adjoint-source array [it][C nrec] of one shot / of the shots of a batch (device table)
+// and sum r_c^2 per component (sums[comp - 1], double)
+void launch_geo_residual(hipStream_t st, const GeoResShot &q, int nSteps, double *sums);
+void launch_geo_residual_batch(hipStream_t st, const GeoResShot *shots, int nb, int max_nrec, int max_nblk, int nSteps, double *sums);
 void launch_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, long long n,
                      double *sumsq);
 void launch_transpose(hipStream_t st, const float *in, float *out, int rows, int cols);

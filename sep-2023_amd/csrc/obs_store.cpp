@@ -13,7 +13,7 @@
 
 namespace sepfwi {
 
-static const char *kEttFile = "/Shot_ett";  // libCUFD.cu:216-223,755-769
+static const char *const kCompFile[4] = {"/Shot_pr", "/Shot_vx", "/Shot_vz", "/Shot_ett"};  // libCUFD.cu:216-223,755-769
 
 int ObservedStore::max_group(size_t bytes, int want) const {
     if (budget_ <= 0 || bytes == 0) return want;
@@ -41,10 +41,12 @@ void ObservedStore::clear() {
 }
 
 void ObservedStore::forget(int shot_id) {
-    auto it = obs_.find(shot_id);
-    if (it == obs_.end()) return;
-    free_entry(it->second);
-    obs_.erase(it);
+    for (int comp = 1; comp <= 3; comp++) {
+        auto it = obs_.find(key(shot_id, comp));
+        if (it == obs_.end()) continue;
+        free_entry(it->second);
+        obs_.erase(it);
+    }
 }
 
 void ObservedStore::release_all() {
@@ -117,9 +119,9 @@ void ObservedStore::fill_from_xpose(Entry &e, int shot_id, int nrec, hipStream_t
     HIP_OK(hipStreamSynchronize(st));
 }
 
-void ObservedStore::put(int shot_id, const float *ett, int nrec, hipStream_t st) {
+void ObservedStore::put(int shot_id, const float *ett, int nrec, hipStream_t st, int comp) {
     const size_t want = want_bytes(nrec);
-    Entry &e = obs_[shot_id];
+    Entry &e = obs_[key(shot_id, comp)];
     const bool was_held = e.held;
     reset(e, want);
     e.from_memory = true;
@@ -136,9 +138,9 @@ void ObservedStore::put(int shot_id, const float *ett, int nrec, hipStream_t st)
     e.held = was_held;
 }
 
-void ObservedStore::put_device_gather(int shot_id, const float *syn_time_major, int nrec, hipStream_t st) {
+void ObservedStore::put_device_gather(int shot_id, const float *syn_time_major, int nrec, hipStream_t st, int comp) {
     const size_t want = want_bytes(nrec);
-    Entry &e = obs_[shot_id];
+    Entry &e = obs_[key(shot_id, comp)];
     const bool was_held = e.held;
     reset(e, want);
     e.from_memory = true;
@@ -180,11 +182,11 @@ long long ObservedStore::pack_offset(int shot_id, int nrec) {
     return it->second.first;
 }
 
-const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st) {
+const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st, int comp) {
     if (nrec <= 0) return nullptr;  // nothing to compare against
     const size_t want = want_bytes(nrec);
     {
-        auto im = obs_.find(shot_id);
+        auto im = obs_.find(key(shot_id, comp));
         if (im != obs_.end() && im->second.from_memory && im->second.bytes == want) {  // handed over from memory
             Entry &e = im->second;
             e.held = true;
@@ -195,9 +197,9 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st) {
     }
     // where the gather lives: the survey's packed file when the parameter file names one and it holds this shot, else the
     // shot's own Shot_ett{id}.bin (libCUFD.cu:216-223)
-    std::string fn = h_.par->data_dir_name + kEttFile + std::to_string(shot_id) + ".bin";
+    std::string fn = h_.par->data_dir_name + kCompFile[comp] + std::to_string(shot_id) + ".bin";
     long long file_off = 0;
-    if (!h_.par->obs_pack_fname.empty()) {
+    if (comp == 3 && !h_.par->obs_pack_fname.empty()) {  // (the packed file holds axial strain only)
         const long long off = pack_offset(shot_id, nrec);
         if (off >= 0) {
             fn = h_.par->obs_pack_fname;
@@ -212,7 +214,7 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st) {
     }
     if ((long long)sb.st_size < file_off + (long long)want) throw IoError("observed data '" + fn + "' is shorter than nrec*nSteps floats");
     const long long stamp = (long long)sb.st_mtim.tv_sec * 1000000000LL + sb.st_mtim.tv_nsec;
-    auto it = obs_.find(shot_id);
+    auto it = obs_.find(key(shot_id, comp));
     if (it != obs_.end() && it->second.mtime_ns == stamp && it->second.size == (long long)sb.st_size && it->second.bytes == want &&
         !it->second.from_memory) {
         Entry &e = it->second;
@@ -228,7 +230,7 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st) {
     if (fseeko(fp, (off_t)file_off, SEEK_SET) == 0) got = fread(h_.h_io, 1, want, fp);
     fclose(fp);
     if (got != want) throw IoError("short read on '" + fn + "'");
-    Entry &e = obs_[shot_id];
+    Entry &e = obs_[key(shot_id, comp)];
     reset(e, want);
     e.held = true;
     e.tick = ++clock_;

@@ -1,4 +1,5 @@
-// obs_store.hpp -- the session's store of observed axial-strain gathers.
+// obs_store.hpp -- the session's store of observed gathers: axial strain and, for a joint misfit (geophone.hpp), vx / vz,
+// keyed by (shot, component); component 1 vx, 2 vz, 3 ett (the default everywhere) as in Shot_{vx,vz,ett}{id}.bin.
 //
 // Replaces the reference's per-call fread of four files per shot (Src/libCUFD.cu:216-223): a gather is read once -- from the
 // shot's Shot_ett{id}.bin, from the survey's packed file, or handed over from memory -- transposed to the device layout
@@ -41,13 +42,13 @@ class ObservedStore {
     int max_group(size_t bytes, int want) const;
 
     // Device pointer of the shot's gather, resident and protected from eviction until release_all().  nrec <= 0: nullptr.
-    const float *acquire(int shot_id, int nrec, hipStream_t st);
+    const float *acquire(int shot_id, int nrec, hipStream_t st, int comp = 3);
     void release_all();
     // [nrec][nSteps] from memory (host or device pointer): sepfwi_set_observed
-    void put(int shot_id, const float *ett, int nrec, hipStream_t st);
+    void put(int shot_id, const float *ett, int nrec, hipStream_t st, int comp = 3);
     // the session's own modelled gather, time-major on the device: calc_id SEPFWI_CALC_OBSERVE_TO_STORE
-    void put_device_gather(int shot_id, const float *syn_time_major, int nrec, hipStream_t st);
-    void forget(int shot_id);  // its file was just rewritten
+    void put_device_gather(int shot_id, const float *syn_time_major, int nrec, hipStream_t st, int comp = 3);
+    void forget(int shot_id);  // its files were just rewritten (every component)
     void clear();
 
     long long device_bytes() const { return dev_bytes_; }
@@ -75,7 +76,8 @@ class ObservedStore {
     long long pack_offset(int shot_id, int nrec);
 
     Host h_;
-    std::map<int, Entry> obs_;
+    static int key(int shot_id, int comp) { return shot_id * 4 + comp; }
+    std::map<int, Entry> obs_;  // by key(shot, component)
     PackIndex pack_;
     long long pack_mtime_ns_ = -1, pack_size_ = -1;
     long long budget_ = 0, dev_bytes_ = 0, host_bytes_ = 0, evictions_ = 0, uploads_ = 0, clock_ = 0;

@@ -5,7 +5,8 @@
 // every call: Model (Src/Model.cu), Cpml (Src/Cpml.cu), Bnd (Src/Boundary.cu), Src_Rec (Src/Src_Rec.cu).
 // Differences by design: device state is allocated once and kept; observed data are cached
 // in HBM (time-major) instead of being re-read from four files per shot per call; only the axial-strain
-// (ett) residual -- the only one that enters misfit and adjoint source (libCUFD.cu:427,607) -- is formed.
+// (ett) residual -- the only one that enters misfit and adjoint source (libCUFD.cu:427,607) -- is formed, unless the
+// parameter keys misfit_w_* give the vx / vz residuals a weight (geophone.hpp).
 #include "session.hpp"
 
 #include <sys/stat.h>
@@ -19,6 +20,7 @@
 #include <stdexcept>
 
 #include "das_gauge.hpp"
+#include "geophone.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "host_checks.hpp"
@@ -169,6 +171,8 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     if (par.if_src_update && par.if_cross_misfit)
         throw std::invalid_argument("parameter file: if_src_update together with if_cross_misfit is not supported");
     cond_on_ = par.if_win || par.has_filter || par.if_cross_misfit || par.if_src_update;
+    joint_ = par.joint();
+    geo_ncomp_ = geo_blocks(par, geo_block_);
     HIP_OK(hipSetDevice(gpu_id_));
     HIP_OK(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
     HIP_OK(hipEventCreateWithFlags(&ev_order_, hipEventDisableTiming));
@@ -182,7 +186,9 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     const size_t dlen = (size_t)std::max(1, survey_.max_nrec) * (size_t)par.nSteps;
     data_len_ = dlen;
     syn_ = dalloc<float>(4 * dlen);  // time-major pr, vx, vz, ett
-    res_ = dalloc<float>(dlen);
+    res_len_ = dlen * (size_t)(joint_ ? geo_ncomp_ : 1);  // today's size unless the misfit is a joint one
+    res_ = dalloc<float>(res_len_);
+    if (joint_) geo_sums_ = dalloc<double>(4);
     xpose_ = dalloc<float>(dlen);
     if (cond_on_) {
         xpose2_ = dalloc<float>(dlen);
@@ -213,6 +219,8 @@ Session::~Session() {
     for (float *p : {ba_.state, ba_.syn, ba_.res, ba_.frame, ba_.bwd})
         if (p) (void)hipFree(p);
     if (d_shots_) (void)hipFree(d_shots_);
+    if (d_shots_bwd_) (void)hipFree(d_shots_bwd_);
+    if (d_geo_res_) (void)hipFree(d_geo_res_);
     if (d_stf_) (void)hipFree(d_stf_);
     for (XLane &L : xl_) {
         if (L.state) (void)hipFree(L.state);
@@ -269,8 +277,8 @@ void Session::ensure_lanes(int n_lanes, bool with_frames) {
         if (!L.state) {
             HIP_OK(dev_malloc((void **)&L.state, 13 * n * sizeof(float)));
             HIP_OK(dev_malloc((void **)&L.syn, 4 * data_len_ * sizeof(float)));
-            HIP_OK(dev_malloc((void **)&L.res, data_len_ * sizeof(float)));
-            device_bytes_ += (long long)((13 * n + 5 * data_len_) * sizeof(float));
+            HIP_OK(dev_malloc((void **)&L.res, res_len_ * sizeof(float)));
+            device_bytes_ += (long long)((13 * n + 4 * data_len_ + res_len_) * sizeof(float));
         }
         if (with_frames && !L.frame) {
             const size_t fb = (size_t)par_.nSteps * 5 * (size_t)g_.frame_len * sizeof(float);
@@ -302,7 +310,7 @@ void Session::ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots) 
     const size_t frame_lane = (size_t)par_.nSteps * 5 * (size_t)g_.frame_len;
     regrow(ba_.state, ba_.n_state, n_fwd, 13 * n);
     regrow(ba_.syn, ba_.n_syn, n_fwd, 4 * data_len_);
-    regrow(ba_.res, ba_.n_res, n_fwd, data_len_);
+    regrow(ba_.res, ba_.n_res, n_fwd, res_len_);
     if (with_frames) regrow(ba_.frame, ba_.n_frame, n_fwd, frame_lane);
     regrow(ba_.bwd, ba_.n_bwd, n_bwd, 18 * n);
     bl_.assign((size_t)std::max(ba_.n_state, 1), BLane{});
@@ -310,7 +318,7 @@ void Session::ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots) 
         BLane &L = bl_[k];
         L.state = ba_.state + (size_t)k * 13 * n;
         L.syn = ba_.syn + (size_t)k * 4 * data_len_;
-        L.res = ba_.res + (size_t)k * data_len_;
+        L.res = ba_.res + (size_t)k * res_len_;
         L.frame = k < ba_.n_frame ? ba_.frame + (size_t)k * frame_lane : nullptr;
         L.bwd = k < ba_.n_bwd ? ba_.bwd + (size_t)k * 18 * n : nullptr;
     }
@@ -335,17 +343,23 @@ void Session::drop_observed() {
     obs_->clear();
 }
 
-// Observed axial-strain gather of one shot handed over from memory ([nrec][nSteps], host or device pointer).
-void Session::set_observed(int shot_id, const float *ett, int nrec, int nSteps) {
+// Observed gather of one shot and component handed over from memory ([nrec][nSteps], host or device pointer).
+void Session::set_observed(int shot_id, const float *ett, int nrec, int nSteps, int comp) {
     std::lock_guard<std::mutex> lock(mu_);
     HIP_OK(hipSetDevice(gpu_id_));
+    if (comp < 1 || comp > 3) throw std::invalid_argument("set_observed: comp must be 1 (vx), 2 (vz) or 3 (ett), got " + std::to_string(comp));
     if (shot_id < 0 || shot_id >= (int)survey_.shots.size() || !survey_.shots[shot_id].present)
         throw std::invalid_argument("set_observed: unknown shot id " + std::to_string(shot_id));
     if (!ett || nrec != survey_.shots[shot_id].nrec || nSteps != par_.nSteps)
         throw std::invalid_argument("set_observed: data must be [nrec][nSteps] of the survey / parameter file");
     if (nrec > 0) order_after_null_stream(own_stream_);  // a HIP `ett` was produced on the caller's (default) stream
     obs_->release_all();
-    obs_->put(shot_id, ett, nrec, own_stream_);
+    obs_->put(shot_id, ett, nrec, own_stream_, comp);
+}
+
+void Session::misfit_parts(double parts[3]) {
+    std::lock_guard<std::mutex> lock(mu_);
+    for (int k = 0; k < 3; k++) parts[k] = parts_[k];
 }
 
 // Window and band-pass one [rec][it] gather in place, as the commented driver lines apply them to observed and synthetic

@@ -36,7 +36,9 @@ class Session {
     std::string loop_status();  // "" while the persistent backward loop is in use, else why not (sepfwi_loop_status)
     void drop_observed();
     // observed axial strain of one shot from memory ([nrec][nSteps] like the files; host or device pointer)
-    void set_observed(int shot_id, const float *ett, int nrec, int nSteps);
+    void set_observed(int shot_id, const float *ett, int nrec, int nSteps, int comp = 3);  // comp: 1 vx, 2 vz, 3 ett
+    // unweighted 0.5 sum_shots sum r_c^2 of the last misfit or gradient call for (vx, vz, ett); 0 for a component with weight 0
+    void misfit_parts(double parts[3]);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer
     void copy_field(int lane, int which, float *out);
@@ -68,6 +70,8 @@ class Session {
     struct InjDev;
     struct ShotCtx {  // one shot of the call in the lane it runs in
         int is, id, nrec, comps;
+        int nres;               // row length of `res`: nrec, or C nrec for a joint misfit (geophone.hpp)
+        const float *obs_c[4];  // joint misfit: the observed gathers of the active components, by component id
         const Shot *sh;
         const int *rec;
         const float *stf_s, *d_obs;
@@ -95,7 +99,9 @@ class Session {
     void use_state(ShotCtx &x, float *state) const;
     static constexpr int kQuietSlots = 4 + 64;  // one per stream lane (kMaxLanes) and batch lane (option batch_f <= 64)
     unsigned int *quiet_slot(int slot) const { return quiet_pool_ + (size_t)slot * 4 * (size_t)g_.qn; }
-    bool quiet_wanted(const Call &c, const ShotCtx &x) const { return c.opt.quiet_skip != 0 && (x.nrec == 0 || (x.line.n > 0 && c.opt.line_fuse != 0)); }
+    bool quiet_wanted(const Call &c, const ShotCtx &x) const { return c.opt.quiet_skip != 0 && !joint_ && (x.nrec == 0 || (x.line.n > 0 && c.opt.line_fuse != 0)); }
+    // the residual of a fused line enters inside the field kernels -- unless the misfit is a joint one, whose adjoint source goes through the plan
+    bool inject_inline(const Call &c, const ShotCtx &x) const { return x.line.n > 0 && c.opt.line_fuse != 0 && !joint_; }
     float *syn_of(const ShotCtx &x, int comp) const { return x.syn + (size_t)comp * data_len_; }
     bool forward_inline(const Call &c, const ShotCtx &x) const { return x.line.n > 0 && !(x.comps & 1) && c.opt.line_fuse != 0; }
     // forward pass of one shot, stream form (libCUFD.cu:268-332)
@@ -104,6 +110,8 @@ class Session {
     void record_column(const ShotCtx &x, int column);
     const GaugeDev &gauge_taps(const ShotCtx &x);  // a gauge shot's taps on the device, built on first use (das_gauge.hpp)
     void residual(const ShotCtx &x);
+    GeoResShot geo_res_shot(const ShotCtx &x) const;  // joint misfit: what the residual kernel needs of one shot (geophone.hpp)
+    void residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int nb);
     void residual_conditioned(const Call &c, const ShotCtx &x);
     // what a forward pass leaves behind, by kind of call
     void after_forward(Call &c, const ShotCtx &x);
@@ -157,6 +165,20 @@ class Session {
     long long device_bytes_ = 0;
 
     size_t cells_ = 0, data_len_ = 0;
+    // joint DAS + geophone misfit (parameter keys misfit_w_*; geophone.hpp): on?, number of active components, the column block of
+    // each in the adjoint-source array (-1: weight 0), the length of a residual buffer (data_len_ x the active components), the sums
+    // sum r_c^2 on the device (by comp - 1), the batched residual kernel's table, the backward twin of the batched schedule's shot
+    // table (no fused lines, no generic receivers: the plan serves every shot), what the last call left for sepfwi_get_misfit_parts
+    bool joint_ = false;
+    int geo_ncomp_ = 1, geo_block_[4] = {-1, -1, -1, 0};
+    size_t res_len_ = 0;
+    double *geo_sums_ = nullptr;
+    GeoResShot *d_geo_res_ = nullptr;
+    int geo_res_cap_ = 0;
+    std::vector<GeoResShot> geo_res_tab_;
+    ShotDev *d_shots_bwd_ = nullptr;
+    int shots_bwd_cap_ = 0;
+    double parts_[3] = {0.0, 0.0, 0.0};
     // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): fields + memories, frames, seismograms,
     // residual, stream, join event
     static constexpr int kMaxLanes = 4;

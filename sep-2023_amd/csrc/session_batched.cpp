@@ -73,6 +73,8 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
             gauged = true;
         }
         if (x.ginj) {
+            gauged = true;
+            q.nres = x.nres;
             q.ntgt = x.ginj->ntgt;
             q.tgt_start = x.ginj->tgt_start;
             q.tgt_cell = x.ginj->tgt_cell;
@@ -91,6 +93,17 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
             gauge_cap_ = c.group_size;
         }
         HIP_OK(hipMemcpyAsync(d_gauge_, gauge_tab_.data(), gauge_tab_.size() * sizeof(GaugeShotDev), hipMemcpyHostToDevice, c.st));
+    }
+    if (joint_ && c.with_adj) {  // the backward launches' table: no shot injects a fused line or through the generic receiver kernel
+        std::vector<ShotDev> bt = tab;
+        for (ShotDev &d : bt) d.lr_n = d.nrec = 0;
+        if (c.group_size > shots_bwd_cap_) {
+            if (d_shots_bwd_) (void)hipFree(d_shots_bwd_);
+            d_shots_bwd_ = nullptr;
+            HIP_OK(dev_malloc((void **)&d_shots_bwd_, (size_t)c.group_size * sizeof(ShotDev)));
+            shots_bwd_cap_ = c.group_size;
+        }
+        HIP_OK(hipMemcpy(d_shots_bwd_, bt.data(), bt.size() * sizeof(ShotDev), hipMemcpyHostToDevice));
     }
     HIP_OK(hipStreamSynchronize(c.st));  // `tab` and `stf_rows` are pageable host memory
     return tab;
@@ -158,7 +171,9 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
     batch_join(st, ns);
     for (int k = 0; k < nb; k++)
         if (tab[is0 + k].comps & 16) record_column(cx[k], nSteps - 1);
-    if (c.if_res)
+    if (c.if_res && joint_)
+        residual_batch(c, cx, nb);
+    else if (c.if_res)
         for (int k = 0; k < nb; k++) cond_on_ ? residual_conditioned(c, cx[k]) : residual(cx[k]);
     HIP_OK(hipEventRecord(ev_[1], st));
     fwd_steps_ += (long long)nb * (nSteps - 1);
@@ -182,9 +197,10 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
     int nsb = std::max(1, std::min(std::min(opt.batch_split, (int)kMaxLanes - 1), nbb));  // sub-batches on streams of their own, as in the forward loop
     auto general = [&](int a0, int a1) {  // a shot in [a0, a1) whose residual is not injected inside k_bwd_b?
         for (int k = a0; k < a1; k++)
-            if (tab[first + k].lr_n == 0 && tab[first + k].nrec > 0) return true;
+            if (tab[first + k].lr_n == 0 && tab[first + k].nrec > 0) return !joint_;  // (a joint misfit: the plan serves every shot)
         return false;
     };
+    const ShotDev *shots = joint_ ? d_shots_bwd_ : d_shots_;
     // An experiment that lost, kept in the -DSEPFWI_PROBES build (option pk_ms; profiles/EXPERIMENTS.md #48): the whole sub-batch as ONE
     // persistent launch (the multi-shot loop, session_persist.cpp) where every shot's channels are a fused line (or absent).  On every
     // grid that takes the batched schedule the per-step launches below are faster, also against the loop without any synchronisation.
@@ -193,7 +209,7 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
         for (int k = a0; k < a1; k++) m = std::max(m, gauge_tab_[first + k].ntgt);
         return m;
     };
-    bool lines = opt.pk_ms != 0 && opt.line_fuse != 0;
+    bool lines = opt.pk_ms != 0 && opt.line_fuse != 0 && !joint_;
     for (int k = 0; k < nbb; k++) lines = lines && (tab[first + k].nrec == 0 || tab[first + k].lr_n > 0) && gauge_tab_[first + k].nrec == 0;
     const bool looped = lines && persist_prepare(pk_ms_, opt, nbb) && batched_backward_persistent(c, tab, first, nbb);
     hipStream_t sub[kMaxLanes] = {};
@@ -205,16 +221,16 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
         if (opt.img_every > 1) gs.dt_img = (it % opt.img_every == 0) ? (float)opt.img_every * g.dt : 0.0f;
         for (int q = 0; q < nsb; q++) {
             const int a0 = (int)((long long)nbb * q / nsb), a1 = (int)((long long)nbb * (q + 1) / nsb);
-            launch_bwd_a_batch(sub[q], gs, opt, d_shots_ + first + a0, a1 - a0, md_, pc_, n, it);
-            launch_bwd_b_batch(sub[q], gs, opt, d_shots_ + first + a0, a1 - a0, md_, pc_, n, it, c.src_scale, (ev && q == 0) ? ev[0] : nullptr,
+            launch_bwd_a_batch(sub[q], gs, opt, shots + first + a0, a1 - a0, md_, pc_, n, it);
+            launch_bwd_b_batch(sub[q], gs, opt, shots + first + a0, a1 - a0, md_, pc_, n, it, c.src_scale, (ev && q == 0) ? ev[0] : nullptr,
                                (ev && q == 0) ? ev[1] : nullptr);
             launches_ += 2;
             if (general(a0, a1)) {  // res_injection_exx / _ezz for the sub-batch's shots whose channels are not a fused line: ONE launch
-                launch_inject_batch(sub[q], g, d_shots_ + first + a0, a1 - a0, survey_.max_nrec, n, it);
+                launch_inject_batch(sub[q], g, shots + first + a0, a1 - a0, survey_.max_nrec, n, it);
                 launches_++;
             }
             if (const int gt = gauge_ntgt(a0, a1)) {  // gauge channels: their twin, from the side table
-                launch_inject_gauge_batch(sub[q], d_shots_ + first + a0, d_gauge_ + first + a0, a1 - a0, gt, n, it);
+                launch_inject_gauge_batch(sub[q], shots + first + a0, d_gauge_ + first + a0, a1 - a0, gt, n, it);
                 launches_++;
             }
         }

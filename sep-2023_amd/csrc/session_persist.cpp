@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "das_gauge.hpp"
+#include "geophone.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "inject_plan.hpp"
@@ -149,7 +150,12 @@ Session::InjDev &Session::inj_dev(const ShotCtx &x) {
     const Shot &sh = *x.sh;
     const float *sens = sh.sens.empty() ? nullptr : sh.sens.data();
     std::vector<int> tgt_cell, tgt_field;
-    const InjectPlan p = x.gauge ? make_gauge_plan(make_gauge_taps(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, par_.gauge),
+    // a joint misfit (geophone.hpp): the plan of the concatenated channel list -- ett channels, vx geophones, vz geophones
+    const bool by_taps = x.gauge || joint_;
+    const InjectPlan p = joint_ ? make_gauge_plan(make_geophone_taps(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, par_.gauge,
+                                                                     geo_block_[3] >= 0, geo_block_[1] >= 0, geo_block_[2] >= 0),
+                                                  g_.nzc, g_.nx, g_.pitch, &tgt_cell, &tgt_field)
+                         : x.gauge ? make_gauge_plan(make_gauge_taps(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, par_.gauge),
                                                    g_.nzc, g_.nx, g_.pitch, &tgt_cell, &tgt_field)
                                  : make_inject_plan(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, g_.nzc, g_.nx);
     InjDev d;
@@ -164,7 +170,7 @@ Session::InjDev &Session::inj_dev(const ShotCtx &x) {
     up(&d.tgt_start, p.tgt_start);
     up(&d.ent_rec, p.ent_rec);
     up(&d.ent_w, p.ent_w);
-    if (x.gauge) {
+    if (by_taps) {
         up(&d.tgt_cell, tgt_cell);
         up(&d.tgt_field, tgt_field);
     }
@@ -177,7 +183,7 @@ Session::InjDev &Session::inj_dev(const ShotCtx &x) {
 // directional sensitivities, gauge channels): the injection plan of the shot (inj_dev) and the residual of THIS pass folded per target
 // cell and time step (one launch).  Fills a.inj; leaves it empty for a fused line or no receivers.
 const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStream_t st) {
-    if (x.nrec == 0 || (x.line.n > 0 && c.opt.line_fuse != 0)) return nullptr;
+    if (x.nrec == 0 || inject_inline(c, x)) return nullptr;
     inj_dev(x);  // (built on first use)
     auto it = inj_.find(x.id);
     const InjDev &d = it->second;
@@ -189,7 +195,7 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
         device_bytes_ += (long long)((need - inj_val_len_) * sizeof(float));
         inj_val_len_ = need;
     }
-    launch_inject_values(st, x.res, x.nrec, par_.nSteps, d.tgt_start, d.ent_rec, d.ent_w, d.ntgt, inj_val_);
+    launch_inject_values(st, x.res, x.nres, par_.nSteps, d.tgt_start, d.ent_rec, d.ent_w, d.ntgt, inj_val_);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) throw HipError(std::string("k_inject_values launch failed: ") + hipGetErrorString(le));
     launches_++;

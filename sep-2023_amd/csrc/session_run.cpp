@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "das_gauge.hpp"
+#include "geophone.hpp"
 #include "device_alloc.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
@@ -85,6 +86,7 @@ void Session::prepare_buffers(Call &c, const float *stf) {
     }
     if (c.with_adj) HIP_OK(hipMemsetAsync(acc_buf_, 0, 5 * n * sizeof(float), st));
     if (c.if_res) HIP_OK(hipMemsetAsync(scal_, 0, 4 * sizeof(double), st));
+    if (c.if_res && joint_) HIP_OK(hipMemsetAsync(geo_sums_, 0, 4 * sizeof(double), st));
     c.stf_rows.resize((size_t)c.group_size * nSteps);
     for (int i = 0; i < c.group_size; i++) {
         HIP_OK(hipMemcpy(c.stf_rows.data() + (size_t)i * nSteps, stf + (size_t)c.shot_ids[i] * nSteps, nSteps * sizeof(float), hipMemcpyDefault));
@@ -125,9 +127,14 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     x.rec = rec_idx_ + rec_off_[x.id];
     x.sens = (sens_ && !x.sh->sens.empty()) ? sens_ + 3 * (size_t)rec_off_[x.id] : nullptr;
     x.stf_s = c.stf_rows.data() + (size_t)is * par_.nSteps;
-    x.d_obs = (c.if_res && with_obs) ? obs_->acquire(x.id, x.nrec, c.st) : nullptr;
+    // the observed gathers of the components with a weight (by default the axial strain alone); one with weight 0 is never read
+    for (int comp = 1; comp <= 3; comp++)
+        x.obs_c[comp] = (c.if_res && with_obs && geo_block_[comp] >= 0) ? obs_->acquire(x.id, x.nrec, c.st, comp) : nullptr;
+    x.d_obs = x.obs_c[3];
+    x.nres = joint_ ? geo_ncomp_ * x.nrec : x.nrec;
     x.scratch = c.with_adj && !par_.scratch_dir_name.empty();  // libCUFD.cu:732-752
-    x.comps = (c.if_res || c.to_store) ? (x.scratch ? 9 : 8) : 15;
+    const int active = (geo_block_[1] >= 0 ? 2 : 0) | (geo_block_[2] >= 0 ? 4 : 0) | (geo_block_[3] >= 0 ? 8 : 0);  // 8 unless the misfit is a joint one
+    x.comps = (c.if_res || c.to_store) ? (active | (x.scratch ? 1 : 0)) : 15;
     // horizontal line of consecutive channels inside the computed region?  (channels with a gauge length never are: they are not
     // sampled at their own cells, so the field kernels cannot take them, and quiet_skip stays off for them)
     const Shot &sh = *x.sh;
@@ -139,10 +146,8 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
         x.line.x0 = sh.x_rec[0];
         x.line.n = x.nrec;
     }
-    if (gauge) {
-        x.gauge = &gauge_taps(x);
-        if (c.with_adj) x.ginj = &inj_dev(x);
-    }
+    if (gauge) x.gauge = &gauge_taps(x);
+    if ((gauge || (joint_ && x.nrec > 0)) && c.with_adj) x.ginj = &inj_dev(x);  // (a joint misfit: every shot's adjoint source goes through its plan)
     x.quiet = quiet_wanted(c, x) ? quiet_slot(lane) : nullptr;
     use_state(x, lane ? xl_[lane].state : state_);
     x.frame = lane ? xl_[lane].frame : frame_;
@@ -217,7 +222,48 @@ void Session::forward_step(const Call &c, const ShotCtx &x, int it, bool inl) {
 
 // residual + misfit of the axial-strain component (libCUFD.cu:413,418,427)
 void Session::residual(const ShotCtx &x) {
+    if (joint_) {  // geophone.hip: the weighted residuals of the active components as one array [it][C nrec], sum r_c^2 per component
+        launch_geo_residual(x.st, geo_res_shot(x), par_.nSteps, geo_sums_);
+        launches_++;
+        return;
+    }
     launch_residual(x.st, x.d_obs, syn_of(x, 3), x.res, x.nrec, (long long)x.nrec * par_.nSteps, scal_);
+    launches_++;
+}
+
+GeoResShot Session::geo_res_shot(const ShotCtx &x) const {
+    GeoResShot q{};
+    q.res = x.res;
+    q.nrec = x.nrec;
+    q.nblk = geo_ncomp_;
+    for (int comp = 1; comp <= 3; comp++) {
+        const int b = geo_block_[comp];
+        if (b < 0) continue;
+        q.obs[b] = x.obs_c[comp];
+        q.syn[b] = syn_of(x, comp);
+        q.w[b] = par_.weight(comp);
+        q.slot[b] = comp - 1;
+    }
+    return q;
+}
+
+// the joint residual of the batch's shots in ONE launch (the table is uploaded from a member: it outlives the copy)
+void Session::residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int nb) {
+    geo_res_tab_.assign((size_t)nb, GeoResShot{});
+    int max_nrec = 0;
+    for (int k = 0; k < nb; k++) {
+        geo_res_tab_[k] = geo_res_shot(cx[k]);
+        max_nrec = std::max(max_nrec, cx[k].nrec);
+    }
+    if (nb > geo_res_cap_) {
+        if (d_geo_res_) (void)hipFree(d_geo_res_);
+        d_geo_res_ = nullptr;
+        HIP_OK(dev_malloc((void **)&d_geo_res_, (size_t)nb * sizeof(GeoResShot)));
+        device_bytes_ += (long long)((size_t)(nb - geo_res_cap_) * sizeof(GeoResShot));
+        geo_res_cap_ = nb;
+    }
+    HIP_OK(hipMemcpyAsync(d_geo_res_, geo_res_tab_.data(), (size_t)nb * sizeof(GeoResShot), hipMemcpyHostToDevice, c.st));
+    launch_geo_residual_batch(c.st, d_geo_res_, nb, max_nrec, geo_ncomp_, par_.nSteps, geo_sums_);
     launches_++;
 }
 
@@ -303,9 +349,10 @@ void Session::scratch_dumps(const Call &c, const ShotCtx &x) {
 }
 
 void Session::after_forward(Call &c, const ShotCtx &x) {
-    if (c.to_store)  // calc_id 3: the modelled axial-strain gather becomes the shot's observed data, exactly as sepfwi_set_observed
-        obs_->put_device_gather(x.id, syn_of(x, 3), x.nrec, c.st);  // would install the Shot_ett file of calc_id 2
-    else if (!c.if_res)
+    if (c.to_store) {  // calc_id 3: the modelled gathers of the components with a weight (by default the axial strain alone) become the
+        for (int comp = 1; comp <= 3; comp++)  // shot's observed data, exactly as sepfwi_set_observed would install the files of calc_id 2
+            if (geo_block_[comp] >= 0) obs_->put_device_gather(x.id, syn_of(x, comp), x.nrec, c.st, comp);
+    } else if (!c.if_res)
         export_gathers(c, x);
     else if (x.scratch)
         scratch_dumps(c, x);
@@ -339,12 +386,12 @@ void Session::collect_probes(Call &c) {  // after a synchronisation of the main 
 void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it) {
     const Grid &g = g_;
     const KernelOptions &opt = c.opt;
-    const bool inj_inl = x.line.n > 0 && opt.line_fuse != 0;
+    const bool inj_inl = inject_inline(c, x);
     const Shot &sh = *x.sh;
     float *frame_t = x.frame + (size_t)it * 5 * (size_t)g.frame_len;
     float *sg = stf_grad_ + (size_t)x.is * par_.nSteps + it;
     const float amp = c.src_scale * x.stf_s[it] * par_.dt;
-    const float *res_t = x.res + (size_t)it * x.nrec;
+    const float *res_t = x.res + (size_t)it * x.nres;
     LineRec lr{};
     if (inj_inl) {
         lr = x.line;
@@ -409,7 +456,7 @@ void Session::run_streams(Call &c) {
     const int nSteps = par_.nSteps;
     int n_lanes = c.opt.pair_fwd ? c.opt.fwd_lanes : 1;
     n_lanes = std::max(1, std::min(std::min(n_lanes, c.group_size), (int)kMaxLanes));
-    if (c.if_res) n_lanes = obs_->max_group((size_t)std::max(1, survey_.max_nrec) * nSteps * sizeof(float), n_lanes);
+    if (c.if_res) n_lanes = obs_->max_group((size_t)std::max(1, survey_.max_nrec) * nSteps * sizeof(float) * (size_t)geo_ncomp_, n_lanes);
     if (n_lanes >= 2) ensure_lanes(n_lanes, c.with_adj);
     for (int is = 0; is < c.group_size;) {
         const int np = std::min(n_lanes, c.group_size - is);
@@ -472,6 +519,18 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
         double sumsq = 0.0;
         HIP_OK(hipMemcpyAsync(&sumsq, scal_, sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
+        parts_[0] = parts_[1] = 0.0;
+        parts_[2] = 0.5 * sumsq;
+        if (joint_) {  // sum r_c^2 per component (vx, vz, ett) -> the weighted misfit and the unweighted parts
+            double s[3] = {0.0, 0.0, 0.0};
+            HIP_OK(hipMemcpyAsync(s, geo_sums_, sizeof(s), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            sumsq = 0.0;
+            for (int comp = 1; comp <= 3; comp++) {
+                parts_[comp - 1] = 0.5 * s[comp - 1];
+                sumsq += (double)par_.weight(comp) * s[comp - 1];
+            }
+        }
         const float mf = (float)(0.5 * sumsq);  // libCUFD.cu:776
         HIP_OK(hipMemcpy(misfit, &mf, sizeof(float), hipMemcpyDefault));
     }
@@ -511,9 +570,12 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
 
     prepare_media(c, Lambda, Mu, Den);
     prepare_buffers(c, stf);
-    const size_t gather_bytes = (size_t)std::max(1, survey_.max_nrec) * par_.nSteps * sizeof(float);
+    // (per shot: one gather per component with a weight)
+    const size_t gather_bytes = (size_t)std::max(1, survey_.max_nrec) * par_.nSteps * sizeof(float) * (size_t)geo_ncomp_;
     if (c.if_res && obs_->budget_bytes() == 0)  // observed data of every shot of the call resident before the time loops start
-        for (int is = 0; is < group_size; is++) (void)obs_->acquire(shot_ids[is], survey_.shots[shot_ids[is]].nrec, c.st);
+        for (int is = 0; is < group_size; is++)
+            for (int comp = 1; comp <= 3; comp++)
+                if (geo_block_[comp] >= 0) (void)obs_->acquire(shot_ids[is], survey_.shots[shot_ids[is]].nrec, c.st, comp);
     obs_->release_all();
 
     // Batch sizes from the Infinity-Cache budget: a forward batch keeps 5 fields per shot + 5 media arrays resident, a backward

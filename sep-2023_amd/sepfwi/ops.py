@@ -210,6 +210,27 @@ class _FwiOps:
         _native.check(_native.lib().sepfwi_set_observed(str(para_fname).encode(), dev, int(shot_id), C.c_void_p(ett.data_ptr()),
                                                         int(ett.shape[0]), int(ett.shape[1])))
 
+    def set_observed_component(self, para_fname, shot_id, comp, data, gpu_id=0):
+        """Observed gather of one shot and component from a tensor ((nrec, nSteps) float32, CPU or HIP) instead of
+        Shot_{vx,vz,ett}{id}.bin, for a joint misfit (parameter keys misfit_w_*): comp "vx" / "vz" / "ett" or 1 / 2 / 3."""
+        comp = {"vx": 1, "vz": 2, "ett": 3}.get(comp, comp)
+        data = _f32c(data, "data")
+        if data.dim() != 2:
+            raise ValueError("data must be (nrec, nSteps)")
+        if data.is_cuda:
+            torch.cuda.current_stream(data.device).synchronize()
+        dev = self.device_override if self.device_override is not None else int(gpu_id)
+        _native.check(_native.lib().sepfwi_set_observed_component(str(para_fname).encode(), dev, int(shot_id), int(comp), C.c_void_p(data.data_ptr()),
+                                                                  int(data.shape[0]), int(data.shape[1])))
+
+    def misfit_parts(self, para_fname, gpu_id=0):
+        """{"vx", "vz", "ett"}: the unweighted 0.5 sum r_c^2 of the session's last misfit or gradient call (sepfwi_get_misfit_parts;
+        0 for a component with weight 0; this process's shots only)."""
+        parts = (C.c_double * 3)()
+        dev = self.device_override if self.device_override is not None else int(gpu_id)
+        _native.check(_native.lib().sepfwi_get_misfit_parts(str(para_fname).encode(), dev, parts))
+        return {"vx": parts[0], "vz": parts[1], "ett": parts[2]}
+
     def debug_field(self, para_fname, which, lane=0, gpu_id=0):
         """Test hook (sepfwi_debug_field): wavefield 0..4 (vz, vx, szz, sxx, sxz) / adjoint 5..9 of a forward lane as the
         last call left it, (nz - nPad, nx) float32."""

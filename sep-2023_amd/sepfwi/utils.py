@@ -35,14 +35,16 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
-            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None):
+            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
     reference only reaches by editing libCUFD.cu).  The key is written only when it is not the default, so default
     files stay byte-identical to the reference's.
     das_gauge_length (extension) [m]: every channel records the mean axial strain over this gauge along the fibre, a whole multiple
-    of the grid spacing along it (csrc/das_gauge.hpp); written only when given."""
+    of the grid spacing along it (csrc/das_gauge.hpp); written only when given.
+    misfit_weights (extension): dict with keys among "ett" / "vx" / "vz" -- the weights of the axial-strain, vx and vz residuals in
+    misfit and adjoint source (csrc/geophone.hpp; defaults ett 1, vx 0, vz 0).  Only the keys given are written."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
     if if_win:
@@ -64,6 +66,13 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
         if not das_gauge_length > 0:
             raise ValueError("das_gauge_length must be > 0")
         para["das_gauge_length"] = float(das_gauge_length)
+    if misfit_weights is not None:
+        for k, v in misfit_weights.items():
+            if k not in ("ett", "vx", "vz"):
+                raise ValueError("misfit_weights keys must be among 'ett', 'vx', 'vz'")
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError("misfit_weights values must be finite and >= 0")
+            para["misfit_w_" + k] = float(v)
     if scratch_dir_name != "":
         para["scratch_dir_name"] = scratch_dir_name
         os.makedirs(scratch_dir_name, exist_ok=True)
