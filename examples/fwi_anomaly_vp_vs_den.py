@@ -6,6 +6,7 @@ import changed: `from sepfwi import ...` instead of the reference's `FWI_ops` / 
     python examples/fwi_anomaly_vp_vs_den.py --niter 10                 # host tensors, like the reference
     python examples/fwi_anomaly_vp_vs_den.py --niter 10 --device cuda   # every tensor of the iteration in HBM
     torchrun --nproc-per-node 8 examples/fwi_anomaly_vp_vs_den.py       # shots sharded over 8 GPUs, one all-reduce
+    python examples/fwi_anomaly_vp_vs_den.py --device cuda --precond 1e-3   # L-BFGS-B on variables scaled by the pseudo-Hessian
 
 Model files of the reference are replaced by their analytic definition (homogeneous + three 16x16-cell boxes).
 The printed iterate-0 misfit is the reference's own 1.51116e4 (tests/golden/known_answers.json)."""
@@ -23,7 +24,27 @@ sys.path[:0] = [os.path.join(ROOT, "sep-2023_amd")]
 from sepfwi import dist as fdist          # noqa: E402
 from sepfwi import modules as M           # noqa: E402
 from sepfwi import utils as ft            # noqa: E402
-from sepfwi.obj_wrapper import PyTorchObjective  # noqa: E402
+from sepfwi import fwi_ops                # noqa: E402
+from sepfwi.obj_wrapper import PyTorchObjective, minimize_lbfgsb  # noqa: E402
+
+
+def pseudo_hessian_scale(fwi, Stf, Shot_ids, ngpu, para_fname, eps):
+    """One armed evaluation at the start model -> the scale vector of minimize_lbfgsb, ordered like the module's parameters:
+    per parameter (H + eps max H)^(-1/2) on the physical grid, normalised to median 1 (H: the diagonal pseudo-Hessian of the call's
+    shots mapped to Vp / Vs / Den, a source-side illumination -- an extension without a counterpart in the reference)."""
+    with torch.no_grad():
+        vp, vs, den = fwi._masked()
+        lam, mu, rho = fwi.lame(vp, vs, den)
+        out = fwi_ops.backward(lam.contiguous(), mu.contiguous(), rho.contiguous(), Stf, ngpu, Shot_ids, para_fname, pseudo_hessian=1)
+        H = ft.pseudo_hessian_vp_vs_den(*[h.to(vp.device) for h in out[5:8]], vp, vs, den)
+    z0, x0 = fwi.nPml, fwi.nPml
+    by_name = dict(zip(fwi.NAMES, H))
+    parts = []
+    for name, _ in fwi.named_parameters():
+        h = by_name[name][z0:z0 + fwi.nz_orig, x0:x0 + fwi.nx_orig].double().cpu().numpy()
+        sc = (h + eps * h.max()) ** -0.5
+        parts.append((sc / np.median(sc)).ravel())
+    return np.concatenate(parts)
 
 
 def main():
@@ -32,6 +53,8 @@ def main():
     ap.add_argument("--device", default="cpu", choices=["cpu", "cuda"], help="where the model tensors live")
     ap.add_argument("--ngpu", type=int, default=1, help="devices driven by this process (ignored under torchrun)")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--precond", type=float, default=None, metavar="EPS",
+                    help="scale the variables by (H + EPS max H)^(-1/2), H the diagonal pseudo-Hessian of the start model (default: off)")
     a = ap.parse_args()
     if "RANK" in os.environ:   # one process per GPU
         import torch.distributed as td
@@ -89,8 +112,15 @@ def main():
         if rank == 0:
             print("iterate %d: misfit %.6e" % (len(hist) - 1, obj.f), flush=True)
 
-    res = optimize.minimize(fun, obj.x0, method="L-BFGS-B", jac=jac, bounds=obj.bounds, tol=None, callback=cb,
-                            options={"gtol": 1e-16, "maxiter": a.niter, "ftol": 1e-12, "maxcor": 5, "maxfun": 1500, "maxls": 6})
+    if a.precond is not None:
+        scale = pseudo_hessian_scale(fwi, Stf, Shot_ids, a.ngpu, para_fname, a.precond)
+        if rank == 0:
+            print("preconditioner: scale min %.3e max %.3e (median 1 per parameter)" % (scale.min(), scale.max()), flush=True)
+        res = minimize_lbfgsb(fun, obj.x0, jac, bounds=obj.bounds, callback=cb, gtol=1e-16, maxiter=a.niter, ftol=1e-12, maxcor=5,
+                              maxfun=1500, maxls=6, scale=scale)
+    else:
+        res = optimize.minimize(fun, obj.x0, method="L-BFGS-B", jac=jac, bounds=obj.bounds, tol=None, callback=cb,
+                                options={"gtol": 1e-16, "maxiter": a.niter, "ftol": 1e-12, "maxcor": 5, "maxfun": 1500, "maxls": 6})
     if rank == 0:
         n = nz * nx
         dvp = res.x[:n].reshape(nz, nx) - vp0

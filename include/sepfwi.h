@@ -129,6 +129,25 @@ int sepfwi_set_observed_component(const char *para_fname, int gpu_id, int shot_i
  */
 int sepfwi_get_misfit_parts(const char *para_fname, int gpu_id, double parts[3]);
 
+/*
+ * Extension (no counterpart in the reference; no reference run pins it): the diagonal pseudo-Hessian of Shin et al. (2001), i.e. the
+ * source-side illumination per parameter, accumulated from the forward wavefield of a misfit or gradient call -- a preconditioner for
+ * the three gradients, not a Hessian.  On every forward step it with it % every == 0 (weight `every`), for the cells of the imaging
+ * condition (nPml <= z <= nz - nPad - 1 - nPml, nPml <= x <= nx - 1 - nPml), summed over the shots of the call:
+ *   hLambda = 2 (1e6 dt)^2 sum (a + b)^2,   hMu = (1e6 dt)^2 sum (4 a^2 + 4 b^2 + s^2),   hDen = dt^2 sum ((ba^2/2 Fz)^2 + (bb^2/2 Fx)^2)
+ * with a = dvz/dz, b = dvx/dx, s = dvx/dz + dvz/dx of the velocities at the start of the step, Fz = dszz/dz + dsxz/dx and
+ * Fx = dsxz/dz + dsxx/dx of the stresses after the step's stress update and source add, ba / bb the buoyancy averages of the cell:
+ * the squared forward-side factors of the three imaging conditions, each at its own staggered point (the gathers of the gradient
+ * finalisation are left out on purpose).  Zero elsewhere.  Same units as the squared gradients (MPa, kg/m^3).
+ */
+/* every >= 1 arms the session of (para_fname, gpu_id), creating it as sepfwi_set_observed does;
+   0 disarms; < 0: SEPFWI_EINVAL before anything else is touched.  Only calc_id 0 and 1 accumulate; a call that is not armed issues
+   exactly the launches it issued before.  The result is that of ONE call (never accumulated across calls). */
+int sepfwi_pseudo_hessian_arm(const char *para_fname, int gpu_id, int every);
+/* result of the most recent armed misfit / gradient call; (nz, nx) float32 each, host or device,
+   any of the three may be NULL; SEPFWI_EINVAL "no session" / "no armed call yet" */
+int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda, float *hMu, float *hDen);
+
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);
 

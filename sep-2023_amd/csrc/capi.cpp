@@ -108,6 +108,27 @@ int sepfwi_get_misfit_parts(const char *para_fname, int gpu_id, double parts[3])
     });
 }
 
+int sepfwi_pseudo_hessian_arm(const char *para_fname, int gpu_id, int every) {
+    return guarded([&] {
+        if (every < 0) throw std::invalid_argument("pseudo_hessian_arm: every must be >= 0, got " + std::to_string(every));
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (every == 0) {  // disarm: nothing to do without a session
+            if (std::shared_ptr<Session> s = find_session(para_fname, gpu_id)) s->pseudo_hessian_arm(0);
+            return;
+        }
+        get_session(para_fname, gpu_id)->pseudo_hessian_arm(every);
+    });
+}
+
+int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda, float *hMu, float *hDen) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
+        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
+        s->pseudo_hessian_get(hLambda, hMu, hDen);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

@@ -255,6 +255,9 @@ Session::~Session() {
         for (void *p : {(void *)kv.second.start, (void *)kv.second.cell, (void *)kv.second.field, (void *)kv.second.w}) (void)hipFree(p);
     if (d_gauge_) (void)hipFree(d_gauge_);
     if (inj_val_) (void)hipFree(inj_val_);
+    for (float *p : ph_set_)
+        if (p) (void)hipFree(p);
+    if (ph_out_) (void)hipFree(ph_out_);
     for (void *p : allocs_) (void)hipFree(p);
     if (frame_) (void)hipFree(frame_);
     if (stf_grad_) (void)hipFree(stf_grad_);

@@ -17,6 +17,7 @@
 #include "kernels.hpp"
 #include "obs_store.hpp"
 #include "persist_plan.hpp"
+#include "pseudo_hessian.hpp"
 
 namespace sepfwi {
 
@@ -39,6 +40,10 @@ class Session {
     void set_observed(int shot_id, const float *ett, int nrec, int nSteps, int comp = 3);  // comp: 1 vx, 2 vz, 3 ett
     // unweighted 0.5 sum_shots sum r_c^2 of the last misfit or gradient call for (vx, vz, ett); 0 for a component with weight 0
     void misfit_parts(double parts[3]);
+    // diagonal pseudo-Hessian (pseudo_hessian.hpp): every >= 1 arms the misfit / gradient calls that follow, 0 disarms; the result of
+    // the most recent armed call, dense (nz, nx) each, host or device pointers, any of them null
+    void pseudo_hessian_arm(int every);
+    void pseudo_hessian_get(float *hLambda, float *hMu, float *hDen);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer
     void copy_field(int lane, int which, float *out);
@@ -65,6 +70,7 @@ class Session {
         std::vector<float> stf_rows;  // tapered source traces of the call's shots (host)
         float src_scale = 0.0f;
         int n_probe = 0;              // HIP-event pairs handed out in the running backward pass
+        int ph_every = 0;             // > 0: the call accumulates the pseudo-Hessian on every ph_every-th forward step (armed, calc_id 0 / 1)
     };
     struct GaugeDev;
     struct InjDev;
@@ -82,6 +88,7 @@ class Session {
         LineRec line;
         float *state;  // [5 fields | 8 memory variables] of this lane
         unsigned int *quiet;  // option quiet_skip: the lane's four quiet-segment maps (forward v, forward s, adjoint v, adjoint s), or null
+        float *ph;            // armed call: the pseudo-Hessian accumulator set of the shot's stream lane, else null
         Fields fld;
         PmlMem mem;
         float *frame, *syn, *res;
@@ -145,6 +152,8 @@ class Session {
     void batch_join(hipStream_t st, int ns);
     void batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0, int nb, const std::vector<ShotCtx> &cx);
     void batched_backward(Call &c, const std::vector<ShotDev> &tab, int first, int nbb, const ShotCtx *cx);
+    void ph_begin(Call &c, int nsets);  // armed call: the accumulator sets of its lanes / sub-batch streams, zeroed on the call's stream
+    PhAcc ph_acc(const float *set) const { float *s = const_cast<float *>(set); return PhAcc{s, s + cells_, s + 2 * cells_}; }
     void write_outputs(Call &c, float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_Den, float *grad_stf);
 
     std::string para_fname_;
@@ -179,6 +188,14 @@ class Session {
     ShotDev *d_shots_bwd_ = nullptr;
     int shots_bwd_cap_ = 0;
     double parts_[3] = {0.0, 0.0, 0.0};
+    // diagonal pseudo-Hessian (pseudo_hessian.hpp): armed with this stride (0: not armed); one accumulator set [E_lam | E_mu | E_rho]
+    // per concurrently running forward lane or sub-batch stream, allocated on first use; how many the running call uses; the result
+    // of the most recent armed call, three dense (nz, nx) arrays, and whether there is one
+    int ph_every_ = 0;
+    float *ph_set_[kPhMaxSets] = {nullptr, nullptr, nullptr, nullptr};
+    int ph_nsets_ = 0;
+    float *ph_out_ = nullptr;
+    bool ph_valid_ = false;
     // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): fields + memories, frames, seismograms,
     // residual, stream, join event
     static constexpr int kMaxLanes = 4;

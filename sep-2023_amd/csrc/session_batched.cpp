@@ -157,6 +157,10 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
         for (int q = 0; q < ns; q++) {
             const int a0 = (int)((long long)nb * q / ns), a1 = (int)((long long)nb * (q + 1) / ns);
             launch_stress_fwd_batch(sub[q], g_, opt, d_shots_ + is0 + a0, a1 - a0, md_, pc_, cells_, data_len_, it, c.src_scale, c.with_adj);
+            if (c.ph_every > 0 && it % c.ph_every == 0) {  // armed: the sub-batch's shots into the set of its stream (pseudo_hessian.hpp)
+                launch_pseudo_hessian_batch(sub[q], g_, d_shots_ + is0 + a0, a1 - a0, cells_, md_, ph_acc(ph_set_[q]), (float)c.ph_every);
+                launches_++;
+            }
             launch_velocity_fwd_batch(sub[q], g_, opt, d_shots_ + is0 + a0, a1 - a0, md_, pc_, cells_);
             launches_ += 2;
             if (general(a0, a1)) {  // general receivers: ONE launch samples the new state of the sub-batch's shots into column it + 1
@@ -253,6 +257,7 @@ void Session::run_batched(Call &c, int Bf, int Bb) {
     ensure_batch(Bf, c.with_adj ? Bb : 0, c.with_adj, group_size);
     HIP_OK(hipMemcpyAsync(d_stf_, c.stf_rows.data(), (size_t)group_size * nSteps * sizeof(float), hipMemcpyHostToDevice, st));
     const std::vector<ShotDev> tab = batch_table(c, Bf, Bb);
+    if (c.ph_every > 0) ph_begin(c, std::min(std::min(c.opt.batch_split, (int)kMaxLanes - 1), Bf));  // one set per sub-batch stream
     if (c.with_adj)
         for (int k = 0; k < Bb; k++) HIP_OK(hipMemsetAsync(bl_[k].bwd + 13 * n, 0, 5 * n * sizeof(float), st));
     for (int is0 = 0; is0 < group_size; is0 += Bf) {

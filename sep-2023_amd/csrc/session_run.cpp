@@ -149,6 +149,7 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     if (gauge) x.gauge = &gauge_taps(x);
     if ((gauge || (joint_ && x.nrec > 0)) && c.with_adj) x.ginj = &inj_dev(x);  // (a joint misfit: every shot's adjoint source goes through its plan)
     x.quiet = quiet_wanted(c, x) ? quiet_slot(lane) : nullptr;
+    x.ph = c.ph_every > 0 ? ph_set_[lane] : nullptr;
     use_state(x, lane ? xl_[lane].state : state_);
     x.frame = lane ? xl_[lane].frame : frame_;
     x.syn = lane ? xl_[lane].syn : syn_;
@@ -215,6 +216,10 @@ void Session::forward_step(const Call &c, const ShotCtx &x, int it, bool inl) {
         lr.d_ett = (x.comps & 8) ? syn_of(x, 3) + c0 : nullptr;
     }
     launch_stress_fwd(x.st, g_, c.opt, x.fld, x.mem, md_, pc_, frame_t, x.sh->z_src, x.sh->x_src, amp, lr);
+    if (x.ph && it % c.ph_every == 0) {  // armed: velocities of the start of the step, stresses after update and source add (pseudo_hessian.hpp)
+        launch_pseudo_hessian(x.st, g_, x.fld, md_, ph_acc(x.ph), (float)c.ph_every);
+        launches_++;
+    }
     launch_velocity_fwd(x.st, g_, c.opt, x.fld, x.mem, md_, pc_);
     launches_ += 2;
     if (!inl) record_column(x, it + 1);
@@ -458,6 +463,7 @@ void Session::run_streams(Call &c) {
     n_lanes = std::max(1, std::min(std::min(n_lanes, c.group_size), (int)kMaxLanes));
     if (c.if_res) n_lanes = obs_->max_group((size_t)std::max(1, survey_.max_nrec) * nSteps * sizeof(float) * (size_t)geo_ncomp_, n_lanes);
     if (n_lanes >= 2) ensure_lanes(n_lanes, c.with_adj);
+    if (c.ph_every > 0) ph_begin(c, n_lanes);  // (before ev_[0]: the extra lanes start after the sets are zeroed)
     for (int is = 0; is < c.group_size;) {
         const int np = std::min(n_lanes, c.group_size - is);
         ShotCtx ctx[kMaxLanes];
@@ -497,6 +503,50 @@ void Session::run_streams(Call &c) {
     }
 }
 
+// ---- diagonal pseudo-Hessian (pseudo_hessian.hpp) ---------------------------------------------------------------------------
+// The accumulator sets of an armed call, one per forward lane (stream schedule) or sub-batch stream (batched schedule): allocated on
+// first use, zeroed on the call's stream at the start of every armed call -- the result is that call's own.
+void Session::ph_begin(Call &c, int nsets) {
+    nsets = std::max(1, std::min(nsets, (int)kPhMaxSets));
+    const size_t bytes = 3 * cells_ * sizeof(float);
+    for (int k = 0; k < nsets; k++) {
+        if (!ph_set_[k]) {
+            HIP_OK(dev_malloc((void **)&ph_set_[k], bytes));
+            device_bytes_ += (long long)bytes;
+        }
+        HIP_OK(hipMemsetAsync(ph_set_[k], 0, bytes, c.st));
+    }
+    ph_nsets_ = nsets;
+}
+
+void Session::pseudo_hessian_arm(int every) {
+    std::lock_guard<std::mutex> lock(mu_);
+    if (every < 0) throw std::invalid_argument("pseudo-Hessian: every must be >= 0");
+    if (every > 0 && par_.nPml < 2) throw std::invalid_argument("pseudo-Hessian: needs nPml >= 2 (the stencils of the interior reach two cells out)");
+    if (every > 0 && !ph_out_) {  // first arming: the result arrays and the first accumulator set
+        HIP_OK(hipSetDevice(gpu_id_));
+        const size_t out_bytes = 3 * (size_t)par_.nz * (size_t)par_.nx * sizeof(float), set_bytes = 3 * cells_ * sizeof(float);
+        HIP_OK(dev_malloc((void **)&ph_out_, out_bytes));
+        device_bytes_ += (long long)out_bytes;
+        if (!ph_set_[0]) {
+            HIP_OK(dev_malloc((void **)&ph_set_[0], set_bytes));
+            device_bytes_ += (long long)set_bytes;
+        }
+    }
+    ph_every_ = every;
+}
+
+void Session::pseudo_hessian_get(float *hLambda, float *hMu, float *hDen) {
+    std::lock_guard<std::mutex> lock(mu_);
+    if (!ph_valid_) throw std::invalid_argument("pseudo-Hessian: no armed call yet");
+    HIP_OK(hipSetDevice(gpu_id_));
+    HIP_OK(hipDeviceSynchronize());  // (a call on a caller's stream with async set may still be running)
+    const size_t dense = (size_t)par_.nz * (size_t)par_.nx;
+    float *out[3] = {hLambda, hMu, hDen};
+    for (int k = 0; k < 3; k++)
+        if (out[k]) HIP_OK(hipMemcpy(out[k], ph_out_ + (size_t)k * dense, dense * sizeof(float), hipMemcpyDefault));
+}
+
 // ---- outputs: written in place when they live on this device, staged otherwise (host memory, another GPU) ------------------
 void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_Den, float *grad_stf) {
     hipStream_t st = c.st;
@@ -514,6 +564,16 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
         if (!devL) HIP_OK(hipMemcpyAsync(grad_Lambda, oL, dense * sizeof(float), hipMemcpyDefault, st));
         if (!devM) HIP_OK(hipMemcpyAsync(grad_Mu, oM, dense * sizeof(float), hipMemcpyDefault, st));
         if (!devD) HIP_OK(hipMemcpyAsync(grad_Den, oD, dense * sizeof(float), hipMemcpyDefault, st));
+    }
+    if (c.ph_every > 0) {  // the sets summed in lane order, the constants of pseudo_hessian.hpp
+        PhSets sets{};
+        sets.nsets = ph_nsets_;
+        for (int k = 0; k < ph_nsets_; k++) sets.set[k] = ph_set_[k];
+        const double mdt = 1e6 * (double)g_.dt;
+        launch_pseudo_hessian_finalize(st, g_, sets, cells_, 2.0 * mdt * mdt, mdt * mdt, (double)g_.dt * (double)g_.dt, ph_out_, ph_out_ + dense,
+                                       ph_out_ + 2 * dense);
+        launches_++;
+        ph_valid_ = true;
     }
     if (c.if_res && misfit) {
         double sumsq = 0.0;
@@ -551,6 +611,7 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
     c.to_store = (calc_id == SEPFWI_CALC_OBSERVE_TO_STORE);  // observe, but into the HBM store instead of the four files
     c.group_size = group_size;
     c.shot_ids = shot_ids;
+    c.ph_every = c.if_res ? ph_every_ : 0;  // calc_id 2 and 3 never accumulate
     launches_ = 0;
     fwd_ms_ = bwd_ms_ = 0.0;
     probe_us_ = 0.0;

@@ -140,6 +140,21 @@ def allreduce_gradients(misfit, gL, gM, gD):
     return misfit, gL, gM, gD
 
 
+def allreduce_sum(buf):
+    """Sum one float32 buffer over ranks with ONE collective and return it (the fused [hLambda | hMu | hDen] of an armed operator
+    call, ops.backward(pseudo_hessian=k)).  In place where the backend reduces the buffer's kind of memory (RCCL: device, gloo:
+    host), through one staged copy each way otherwise.  Not part of the gradient collective's record (collective_stats)."""
+    want = "cuda" if td.get_backend() == "nccl" else "cpu"
+    buf = buf.contiguous()
+    if buf.device.type == want:
+        td.all_reduce(buf, op=td.ReduceOp.SUM)
+        return buf
+    stage = buf.to(torch.device("cuda", local_device_index()) if want == "cuda" else torch.device("cpu"))
+    td.all_reduce(stage, op=td.ReduceOp.SUM)
+    buf.copy_(stage)
+    return buf
+
+
 def barrier():
     if active():
         td.barrier()

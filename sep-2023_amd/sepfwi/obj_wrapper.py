@@ -66,7 +66,7 @@ _SETULB_SIGNATURE = "setulb(m,x,l,u,nbd,f,g,factr,pgtol,wa,iwa,task,lsave,isave,
 
 
 def minimize_lbfgsb(fun, x0, jac, bounds=None, callback=None, maxiter=15000, maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5,
-                    maxfun=15000, maxls=20):
+                    maxfun=15000, maxls=20, scale=None):
     """`optimize.minimize(fun, x0, method="L-BFGS-B", jac=jac, bounds=bounds, callback=callback, options={...})` -- what the
     reference's experiment scripts call (Main-001-FWI-Anomaly-Vp-Vs-Den.py:157-168) -- with the same compiled routine
     (`scipy.optimize._lbfgsb.setulb`) driven directly, so the iterates are the same bit for bit, but without SciPy's
@@ -74,7 +74,29 @@ def minimize_lbfgsb(fun, x0, jac, bounds=None, callback=None, maxiter=15000, max
     (new-style -> old-style -> new-style conversions and a dict look-up per variable), the one serial term of a multi-GPU
     inversion that does not shrink with the number of GPUs.  Here the bound codes are three vectorised
     numpy expressions.  `bounds`: an `optimize.Bounds` or None.  Falls back to `optimize.minimize` when there are no bounds
-    (nothing to save) or when the installed SciPy's private routine does not have the signature this driver was written for."""
+    (nothing to save) or when the installed SciPy's private routine does not have the signature this driver was written for.
+    `scale`: None, or a positive vector s (a diagonal preconditioner, e.g. (pseudo-Hessian)^(-1/2)): the routine optimises
+    y = x / s -- function and gradient are evaluated at x = s y with g_y = s g_x, the bounds are divided by s -- while the callback
+    and the result (x, jac) are in x.  With None the iterates are bit for bit those without the argument."""
+    if scale is not None:
+        s = np.asarray(scale, dtype=np.float64).ravel()
+        x0 = np.asarray(x0, dtype=np.float64).ravel()
+        if s.size != x0.size or not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError("scale must be a finite positive vector of the size of x0")
+        lb = ub = None
+        if bounds is not None:
+            lb = np.broadcast_to(np.asarray(bounds.lb, dtype=np.float64), x0.shape)
+            ub = np.broadcast_to(np.asarray(bounds.ub, dtype=np.float64), x0.shape)
+        to_x = (lambda y: s * y) if bounds is None else (lambda y: np.clip(s * y, lb, ub))   # (s (lb / s) may miss lb by an ulp)
+        res = minimize_lbfgsb(lambda y: fun(to_x(y)), x0 / s, lambda y: s * np.asarray(jac(to_x(y)), dtype=np.float64),
+                              bounds=None if bounds is None else optimize.Bounds(lb / s, ub / s),
+                              callback=None if callback is None else (lambda y: callback(to_x(y))), maxiter=maxiter, maxcor=maxcor,
+                              ftol=ftol, gtol=gtol, maxfun=maxfun, maxls=maxls)
+        res.x = to_x(res.x)
+        res.jac = np.asarray(res.jac, dtype=np.float64) / s
+        if "hess_inv" in res:
+            del res["hess_inv"]   # it is that of the scaled problem
+        return res
     options = dict(maxiter=maxiter, maxcor=maxcor, ftol=ftol, gtol=gtol, maxfun=maxfun, maxls=maxls)
     try:
         from scipy.optimize import _lbfgsb

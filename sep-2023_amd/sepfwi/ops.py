@@ -11,7 +11,9 @@ Multi-GPU:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -38,6 +40,16 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
 
 
 _DIMS_CACHE = {}
+
+# An armed call is arm -> run -> collect -> disarm on ONE session: threads that share a session (single-process ngpu > 1 with the
+# device pinned) take turns, or one would collect the other's result.
+_PH_LOCKS = {}
+_PH_GUARD = threading.Lock()
+
+
+def _ph_lock(para_fname, gpu_id):
+    with _PH_GUARD:
+        return _PH_LOCKS.setdefault((str(para_fname), int(gpu_id)), threading.Lock())
 
 
 def _para_dims(para_fname):
@@ -68,8 +80,15 @@ class _FwiOps:
         self.device_override = None   # bench/tests may pin the HIP device index
 
     # -- one cufd call on one device ------------------------------------------------------
-    def _cufd(self, calc_id, gpu_id, Lambda, Mu, Den, Stf, shot_ids, para_fname, out_device=None):
+    def _cufd(self, calc_id, gpu_id, Lambda, Mu, Den, Stf, shot_ids, para_fname, out_device=None, pseudo_hessian=0):
+        """-> (misfit, gL, gM, gD, gS); with pseudo_hessian = k > 0 (calc_id 0 / 1) the session is armed with every = k for this call
+        alone and a sixth entry follows: the fused (3, nz, nx) tensor [hLambda | hMu | hDen] of the call's shots."""
         L = _native.lib()
+        k = int(pseudo_hessian)
+        if k < 0:
+            raise ValueError("pseudo_hessian must be >= 0 (0: off, k: accumulate on every k-th forward step)")
+        if k > 0 and calc_id not in (0, 1):
+            raise ValueError("pseudo_hessian needs a misfit or gradient call")
         Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
         if Lambda.dim() != 2 or Lambda.shape != Mu.shape or Lambda.shape != Den.shape:
             raise ValueError("Lambda, Mu, Den must be 2-D tensors of one shape (nz_pad, nx_pad)")
@@ -111,14 +130,29 @@ class _FwiOps:
             torch.cuda.synchronize(Lambda.device)   # the model was produced on another GPU: finished before it is staged
         if Stf.is_cuda:
             torch.cuda.synchronize(Stf.device)      # read with a blocking copy inside the library
-        rc = L.sepfwi_cufd_stream(ptr(misfit), ptr(gL), ptr(gM), ptr(gD), ptr(gS), ptr(Lambda), ptr(Mu), ptr(Den),
-                                  ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data),
-                                  str(para_fname).encode(), stream, 0)
-        _native.check(rc)
+        fn = str(para_fname).encode()
+        H = None
+        with (_ph_lock(para_fname, gpu_id) if k > 0 else contextlib.nullcontext()):
+            if k > 0:
+                _native.check(L.sepfwi_pseudo_hessian_arm(fn, gpu_id, k))
+            try:
+                rc = L.sepfwi_cufd_stream(ptr(misfit), ptr(gL), ptr(gM), ptr(gD), ptr(gS), ptr(Lambda), ptr(Mu), ptr(Den),
+                                          ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
+                _native.check(rc)
+                if k > 0:   # ONE buffer [hLambda | hMu | hDen], the unit of the all-reduce under torch.distributed
+                    H = torch.empty((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
+                    _native.check(L.sepfwi_get_pseudo_hessian(fn, gpu_id, ptr(H[0]), ptr(H[1]), ptr(H[2])))
+            finally:
+                if k > 0:
+                    L.sepfwi_pseudo_hessian_arm(fn, gpu_id, 0)   # disarm, also on error
+        if H is not None and H.device != dev:
+            H = H.to(dev)
         if calc_id == 1 and gL.device != dev:   # single-process ngpu > 1: every block's results return to the model's device
             gL, gM, gD, misfit = gL.to(dev), gM.to(dev), gD.to(dev), misfit.to(dev)
         elif calc_id == 0 and misfit.device != dev:   # forward(): the loss follows the model too, whatever gpu_id computed it
             misfit = misfit.to(dev)
+        if k > 0:
+            return misfit, gL, gM, gD, gS, H
         return misfit, gL, gM, gD, gS
 
     def _device_for(self, t: torch.Tensor, i: int, ngpu: int = 1) -> int:
@@ -134,27 +168,40 @@ class _FwiOps:
         return i
 
     # -- reference surface -------------------------------------------------------------------
-    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname):
-        """-> [misfit(1,), gLambda, gMu, gDen, gStf]   (fwi_backward, Src/Torch_Fwi.cpp:38-104)."""
+    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0):
+        """-> [misfit(1,), gLambda, gMu, gDen, gStf]   (fwi_backward, Src/Torch_Fwi.cpp:38-104).
+        Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
+        shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
+        and ranks like the gradients; under torch.distributed through ONE more all-reduce, of the fused [hL | hM | hD] buffer).
+        With the default 0 the return value and every launch are those of the reference surface."""
+        k = int(pseudo_hessian)
+        kw = {"pseudo_hessian": k} if k else {}     # (not armed: _cufd is called exactly as the reference surface calls it)
         ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
         n = int(ids.numel())
         if _dist.active():
             lo, hi = _dist.my_block(n)
-            m, gL, gM, gD, gS_loc = self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids[lo:hi], para_fname)
+            m, gL, gM, gD, gS_loc, *H = self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids[lo:hi], para_fname, **kw)
             m, gL, gM, gD = _dist.allreduce_gradients(m, gL, gM, gD)
             gS = torch.zeros_like(_f32c(Stf, "Stf").cpu())
             if _dist.rank() == 0:   # the reference returns GPU 0's buffer only (Torch_Fwi.cpp:102-103)
                 gS[: gS_loc.shape[0]] = gS_loc
+            if k > 0:
+                return [m, gL, gM, gD, gS] + list(_dist.allreduce_sum(H[0]))
             return [m, gL, gM, gD, gS]
         ngpu = int(ngpu)
         bars = split_shots(n, ngpu)
         if ngpu == 1:
-            parts = [self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids, para_fname)]
+            parts = [self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids, para_fname, **kw)]
         else:
             with ThreadPoolExecutor(max_workers=ngpu) as ex:   # one host thread per GPU, ctypes drops the GIL
                 futs = [ex.submit(self._cufd, 1, self._device_for(Lambda, i, ngpu), Lambda, Mu, Den, Stf,
-                                  ids[bars[i]:bars[i + 1]], para_fname, Lambda.device) for i in range(ngpu)]
+                                  ids[bars[i]:bars[i + 1]], para_fname, Lambda.device, **kw) for i in range(ngpu)]
                 parts = [f.result() for f in futs]
+        if k > 0:   # the parts' pseudo-Hessians summed like the gradients
+            H = parts[0][5]
+            for p in parts[1:]:
+                H += p[5]
+            parts = [p[:5] for p in parts]
         m, gL, gM, gD, gS0 = parts[0]
         m = m.clone()                    # not a view of the fused [gL | gM | gD | misfit] buffer: a kept loss must not pin 3 nz nx floats
         for p in parts[1:]:              # sum of Torch_Fwi.cpp:96-101 (every part already sits on Lambda's device)
@@ -164,13 +211,18 @@ class _FwiOps:
             gD += p[3]
         gS = torch.zeros_like(_f32c(Stf, "Stf").cpu())   # zeros_like(th_stf), rows by local shot position
         gS[: gS0.shape[0]] = gS0
+        if k > 0:
+            return [m, gL, gM, gD, gS] + list(H)
         return [m, gL, gM, gD, gS]
 
-    def forward(self, Lambda, Mu, Den, Stf, gpu_id, Shot_ids, para_fname):
-        """-> [misfit(1,)]   (fwi_forward, Src/Torch_Fwi.cpp:12-36; calc_id 0 on device gpu_id)."""
+    def forward(self, Lambda, Mu, Den, Stf, gpu_id, Shot_ids, para_fname, *, pseudo_hessian=0):
+        """-> [misfit(1,)]   (fwi_forward, Src/Torch_Fwi.cpp:12-36; calc_id 0 on device gpu_id).
+        Extension `pseudo_hessian=k` > 0: -> [misfit, hLambda, hMu, hDen] (see backward; this call's device and shots only)."""
         ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
-        m, *_ = self._cufd(0, int(gpu_id) if self.device_override is None else self.device_override,
-                           Lambda, Mu, Den, Stf, ids, para_fname)
+        m, *rest = self._cufd(0, int(gpu_id) if self.device_override is None else self.device_override,
+                              Lambda, Mu, Den, Stf, ids, para_fname, **({"pseudo_hessian": int(pseudo_hessian)} if pseudo_hessian else {}))
+        if int(pseudo_hessian) > 0:
+            return [m] + list(rest[4])
         return [m]
 
     def obscalc(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, to_store=False):

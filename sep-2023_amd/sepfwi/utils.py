@@ -132,6 +132,21 @@ def sourceGene(f, nStep, delta_t):
     return (1.0 - 2.0 * e * tau ** 2) * np.exp(-e * tau ** 2) * 1.0e7
 
 
+def pseudo_hessian_vp_vs_den(hL, hM, hD, Vp, Vs, Den):
+    """Diagonal pseudo-Hessian of (Lambda [MPa], Mu [MPa], Den) -> that of (Vp, Vs, Den), all on the padded grid: the squared partials
+    of the map Lambda = (Vp^2 - 2 Vs^2) Den / 1e6, Mu = Vs^2 Den / 1e6 (FWI_ops.py:124-125) weight the three inputs,
+        hVp  = (2 Den Vp / 1e6)^2 hL
+        hVs  = (4 Den Vs / 1e6)^2 hL + (2 Den Vs / 1e6)^2 hM
+        hDen = ((Vp^2 - 2 Vs^2) / 1e6)^2 hL + (Vs^2 / 1e6)^2 hM + hD
+    i.e. the column sums of squares of the map's Jacobian.  Cell by cell: the sum over the replicated rim that the padding's
+    transpose applies to a gradient (padding()) is NOT applied here -- crop the physical grid out of the result.
+    -> (hVp, hVs, hDen)."""
+    hVp = (2.0 * Den * Vp / 1e6) ** 2 * hL
+    hVs = (4.0 * Den * Vs / 1e6) ** 2 * hL + (2.0 * Den * Vs / 1e6) ** 2 * hM
+    hDen = ((Vp ** 2 - 2.0 * Vs ** 2) / 1e6) ** 2 * hL + (Vs ** 2 / 1e6) ** 2 * hM + hD
+    return hVp, hVs, hDen
+
+
 def read_shot_gather(data_dir, comp, shot_id, nSteps):
     """Shot_{pr|vx|vz|ett}{id}.bin -> (nrec, nSteps) float32 (libCUFD.cu:755-769)."""
     return np.fromfile(os.path.join(data_dir, "Shot_%s%d.bin" % (comp, shot_id)), dtype=np.float32).reshape(-1, nSteps)
