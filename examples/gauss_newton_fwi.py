@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""Truncated Gauss-Newton FWI of the three-box anomaly model with DAS data (the model and survey of the reference's experiment 001,
+examples/fwi_anomaly_vp_vs_den.py) in the Lame parameters (Lambda, Mu, Den): every outer iteration solves
+    (J^T J + damping D) p = -g
+with a few matrix-free conjugate-gradient iterations (sepfwi.obj_wrapper.gauss_newton_cg over fwi_ops.gauss_newton, one Born pass and one
+backward pass per product), D the diagonal pseudo-Hessian of the same gradient call -- each parameter's block calibrated on the
+Gauss-Newton curvature -- as damping matrix and preconditioner, and takes a backtracking step on the misfit.  An extension without a counterpart in the reference, whose driver knows gradients only.
+
+    python examples/gauss_newton_fwi.py --device cuda
+    python examples/gauss_newton_fwi.py --device cuda --outer 2 --inner 3 --nsteps 600 --shot-stride 3
+
+Prints the CG residual of every inner iteration and the misfit of every outer one."""
+import argparse
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "sep-2023_amd")]
+from sepfwi import utils as ft            # noqa: E402
+from sepfwi import fwi_ops                # noqa: E402
+from sepfwi.obj_wrapper import gauss_newton_cg  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--outer", type=int, default=3, help="Gauss-Newton iterations")
+    ap.add_argument("--inner", type=int, default=4, help="conjugate-gradient iterations per Gauss-Newton iteration (cap)")
+    ap.add_argument("--rtol", type=float, default=0.1, help="relative CG residual at which an inner solve stops")
+    ap.add_argument("--damping", type=float, default=0.05, help="damping of the calibrated pseudo-Hessian D in (J^T J + damping D) p = -g")
+    ap.add_argument("--nsteps", type=int, default=1501)
+    ap.add_argument("--shot-stride", type=int, default=1, help="use every k-th of the 19 shots")
+    ap.add_argument("--device", default="cpu", choices=["cpu", "cuda"], help="where the model tensors live")
+    ap.add_argument("--workdir", default=None)
+    a = ap.parse_args()
+    dev = torch.device(a.device)
+
+    # ---- model and survey: Main-001-...py:20-73
+    nx, nz, dx, dz, dt, nt, f0, nPml = 201, 101, 20.0, 20.0, 0.002, a.nsteps, 10.0, 32
+    vp = np.ones((nz, nx), np.float32) * 4000.0
+    vs = vp / 1.732
+    rho = np.ones((nz, nx), np.float32) * 2500.0
+    vp0, vs0, rho0 = vp.copy(), vs.copy(), rho.copy()
+    vp[42:58, 42:58] += 80.0
+    vs[42:58, 92:108] -= 80.0 / 1.732
+    rho[42:58, 142:158] += 40.0
+    nPad = ft.nPad_for(nz, nPml)
+    nz_pad, nx_pad = nz + 2 * nPml + nPad, nx + 2 * nPml
+    Mask = torch.zeros((nz_pad, nx_pad), dtype=torch.float32, device=dev)
+    Mask[nPml + 4:nPml + nz, nPml:nPml + nx] = 1.0
+    ind_src_x = np.arange(10, nx - 10, 10).astype(int)[::a.shot_stride]
+    ind_src_z = np.ones_like(ind_src_x)
+    ind_rec_x = np.arange(10, nx - 10).astype(int)
+    ind_rec_z = 95 * np.ones_like(ind_rec_x)
+    work = a.workdir or os.path.join(tempfile.gettempdir(), "sepfwi_example_gauss_newton")
+    os.makedirs(work, exist_ok=True)
+    para_fname, survey_fname = os.path.join(work, "para_file.json"), os.path.join(work, "survey_file.json")
+    ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, para_fname, survey_fname, os.path.join(work, "Data"))
+    ft.surveyGen(ind_src_z, ind_src_x, ind_rec_z, ind_rec_x, survey_fname)
+    Stf = torch.tensor(ft.sourceGene(f0, nt, dt), dtype=torch.float32).repeat(len(ind_src_x), 1).to(dev)
+    ids = torch.arange(len(ind_src_x), dtype=torch.int32)
+
+    def lame(vp_, vs_, rho_):   # padded (Lambda, Mu, Den) in MPa / kg m^-3, FWI_ops.py:134-135
+        t = [torch.tensor(ft.padding_numpy_array(m, nPml, nPad), dtype=torch.float32, device=dev) for m in (vp_, vs_, rho_)]
+        return [((t[0] ** 2 - 2.0 * t[1] ** 2) * t[2] / 1e6).contiguous(), (t[1] ** 2 * t[2] / 1e6).contiguous(), t[2].contiguous()]
+
+    fwi_ops.obscalc(*lame(vp, vs, rho), Stf, 1, ids, para_fname, to_store=True)   # observed data straight into the session's store
+    m = lame(vp0, vs0, rho0)
+    misfit = lambda mm: float(fwi_ops.forward(*mm, Stf, 0, ids, para_fname)[0])
+    f0_ = None
+    for k in range(a.outer):
+        out = fwi_ops.backward(*m, Stf, 1, ids, para_fname, pseudo_hessian=1)
+        f, g, D = float(out[0]), [Mask * t for t in out[1:4]], [Mask * t for t in out[5:8]]
+        if f0_ is None:
+            f0_ = f
+            print("iterate 0: misfit %.6e" % f, flush=True)
+        hv = lambda v: [Mask * t for t in fwi_ops.gauss_newton(*m, *[Mask * x for x in v], Stf, 1, ids, para_fname)]
+        # The pseudo-Hessian leaves out the receiver side, and its three blocks are not on one scale (it is a preconditioner, not a
+        # Hessian): calibrate each block on the Gauss-Newton curvature along its own preconditioned gradient z_k = -g_k / D_k,
+        # D_k <- D_k (z_k^T H z_k) / (z_k^T D_k z_k) -- three products per outer iteration
+        dot = lambda x, y: float(sum((p.double() * q.double()).sum() for p, q in zip(x, y)))
+        for j in range(3):
+            z = [torch.zeros_like(t) for t in g]
+            z[j] = -(g[j] / D[j].clamp_min(1e-12 * float(D[j].max()))) * Mask
+            s_j = dot(z, hv(z)) / dot([z[j]], [D[j] * z[j]])
+            D[j] = D[j] * max(s_j, 0.0)
+            print("  outer %d: pseudo-Hessian block %s calibrated by %.3e" % (k + 1, ("Lambda", "Mu", "Den")[j], s_j), flush=True)
+        lam = a.damping
+        p, hist = gauss_newton_cg(hv, g, damping=lam, diag=D, maxiter=a.inner, rtol=a.rtol,
+                                  callback=lambda i, r: print("  outer %d cg %d: relative residual %.4e" % (k + 1, i, r), flush=True))
+        step, f_new = 1.0, None
+        for _ in range(6):      # backtracking on the misfit
+            f_new = misfit([mi + step * pi for mi, pi in zip(m, p)])
+            if f_new < f:
+                break
+            step *= 0.5
+        if not f_new < f:
+            print("iterate %d: no decrease along the Gauss-Newton step, stopping" % (k + 1))
+            break
+        m = [(mi + step * pi).contiguous() for mi, pi in zip(m, p)]
+        print("iterate %d: misfit %.6e   (step %.3g, %d cg iterations)" % (k + 1, f_new, step, len(hist) - 1), flush=True)
+        f = f_new
+    true, start = lame(vp, vs, rho), lame(vp0, vs0, rho0)
+    boxes = [(slice(nPml + 42, nPml + 58), slice(nPml + c, nPml + c + 16)) for c in (42, 92, 142)]    # the Vp, Vs and density boxes
+    print("done: misfit %.4e -> %.4e" % (f0_, f))
+    for name, unit, mi, ti, si in zip(("Lambda", "Mu", "Den"), ("MPa", "MPa", "kg/m^3"), m, true, start):
+        print("  %-6s update, extreme value inside the Vp / Vs / density box: %s %s   (true model: %s)" % (
+            name, " / ".join("%+.1f" % float((mi - si)[b].flatten()[(mi - si)[b].abs().argmax()]) for b in boxes), unit,
+            " / ".join("%+.1f" % float((ti - si)[b].flatten()[(ti - si)[b].abs().argmax()]) for b in boxes)))
+
+if __name__ == "__main__":
+    main()

@@ -148,6 +148,32 @@ int sepfwi_pseudo_hessian_arm(const char *para_fname, int gpu_id, int every);
    any of the three may be NULL; SEPFWI_EINVAL "no session" / "no armed call yet" */
 int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda, float *hMu, float *hDen);
 
+/*
+ * Extension (no counterpart in the reference; no reference run pins it): Born modelling and the Gauss-Newton Hessian-vector product.
+ * Given the model m = (Lambda, Mu, Den) and a perturbation v = (dLambda, dMu, dDen) -- all (nz, nx) float32, MPa / kg m^-3, host or
+ * device pointers with the conventions of sepfwi_cufd_stream -- the call propagates the scattered field next to the background field
+ * (no finite difference, no step size) and returns J v, the first-order change of every gather:
+ *   d_ett, d_vx, d_vz   each may be NULL; else the scattered gathers shot after shot in the order of shot_ids, each [nrec_i][nSteps]
+ *                       (the layout of Shot_*.bin; column it + 1 holds the state after step it, column 0 is 0).  Every receiver geometry
+ *                       and parameter key of the forward pass applies (das_fiber, directional channels, das_gauge_length).  The data-
+ *                       conditioning keys (if_win, filter, if_cross_misfit, if_src_update) do NOT alter these raw gathers.
+ *   hv_Lambda, hv_Mu, hv_Den   all NULL: J v only.  All set: overwritten with the Gauss-Newton product summed over the call's shots,
+ *                       hv = J^T W J v, W = diag(misfit_w_ett, misfit_w_vx, misfit_w_vz) of the parameter file (default (1, 0, 0)) and
+ *                       J^T the backward pass of a gradient call.  Sign and weights: hv is the gradient that sepfwi_cufd(calc_id 1) would
+ *                       return at m if the observed data were syn(m) - J v; so v^T hv >= 0 up to the inexactness of the reference's adjoint.
+ *                       (nz, nx) float32 each, host or device.  One set and the others NULL: SEPFWI_EINVAL.
+ * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, perturbation, stf or para_fname; a bad shot list; the product
+ * (hv_* set) with a live data-conditioning key -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
+ * background model only.  The session's observed data, its misfit, sepfwi_get_misfit_parts and the pseudo-Hessian state are neither
+ * read nor written; sepfwi_get_stats afterwards describes this call (fwd_ms: the Born time loops).
+ * Schedule: one shot after the other on the call's stream (hip_stream, NULL: the session's own), synchronous; the batched multi-lane
+ * schedule of sepfwi_cufd* is not used.  Option quiet_skip is ignored for this call.  The second field set (18 arrays) is allocated on
+ * the first call; a process that never calls this function launches and allocates exactly what it did before.
+ */
+int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
+                const int *shot_ids, const char *para_fname, void *hip_stream);
+
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);
 
@@ -235,8 +261,8 @@ int sepfwi_param_backward(int kind, int nz, int nx, int nPml, int nPad, const fl
                           void *hip_stream);
 
 /*
- * Test hook: wavefield `which` (0..4: vz, vx, szz, sxx, sxz; 5..9: their adjoint twins) of forward lane `lane` as the last
- * sepfwi_cufd* call on (para_fname, gpu_id) left it, dense (nz - nPad, nx) row-major float32, host or device pointer.
+ * Test hook: wavefield `which` (0..4: vz, vx, szz, sxx, sxz; 5..9: their adjoint twins; 10..14: the scattered fields of the last
+ * sepfwi_born call) of forward lane `lane` as the last sepfwi_cufd* / sepfwi_born call on (para_fname, gpu_id) left it, dense (nz - nPad, nx) row-major float32, host or device pointer.
  * After a gradient call the forward fields are the reverse-time RECONSTRUCTION run back to time step 0, i.e. they must
  * have returned to the zero initial state up to float32 round-off: the size-independent parity
  * property checked at the full 2000 x 1000 x 4000 size, where the CPU oracle cannot go.

@@ -129,6 +129,21 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
     });
 }
 
+int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
+                const int *shot_ids, const char *para_fname, void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
+        if (!dLambda || !dMu || !dDen) throw std::invalid_argument("born: dLambda, dMu and dDen must not be NULL");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        const int n_hv = (hv_Lambda ? 1 : 0) + (hv_Mu ? 1 : 0) + (hv_Den ? 1 : 0);
+        if (n_hv != 0 && n_hv != 3) throw std::invalid_argument("born: hv_Lambda, hv_Mu, hv_Den must be all NULL (J v only) or all set");
+        std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
+        s->born(d_ett, d_vx, d_vz, hv_Lambda, hv_Mu, hv_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids, (hipStream_t)hip_stream);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

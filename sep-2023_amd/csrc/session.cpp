@@ -258,6 +258,8 @@ Session::~Session() {
     for (float *p : ph_set_)
         if (p) (void)hipFree(p);
     if (ph_out_) (void)hipFree(ph_out_);
+    if (born_) (void)hipFree(born_);
+    if (born_stage_) (void)hipFree(born_stage_);
     for (void *p : allocs_) (void)hipFree(p);
     if (frame_) (void)hipFree(frame_);
     if (stf_grad_) (void)hipFree(stf_grad_);
@@ -381,9 +383,12 @@ void Session::condition_gather(hipStream_t st, float *gather, int shot_id, int n
 void Session::copy_field(int lane, int which, float *out) {
     std::lock_guard<std::mutex> lock(mu_);
     HIP_OK(hipSetDevice(gpu_id_));
-    if (!out || which < 0 || which > 9) throw std::invalid_argument("debug_field: which must be 0..9");
+    if (!out || which < 0 || which > 14) throw std::invalid_argument("debug_field: which must be 0..14");
     const float *base = nullptr;
-    if (which >= 5) {  // adjoint fields: one set per session (stream mode) or per backward lane (batched mode)
+    if (which >= 10) {  // the scattered fields of the last Born call
+        if (!born_) throw std::invalid_argument("debug_field: no Born call yet");
+        base = born_ + (size_t)(which - 10) * cells_;
+    } else if (which >= 5) {  // adjoint fields: one set per session (stream mode) or per backward lane (batched mode)
         if (last_batched_) {
             if (lane < 0 || lane >= (int)bl_.size() || !bl_[lane].bwd) throw std::invalid_argument("debug_field: no such backward lane");
             base = bl_[lane].bwd + (8 + (which - 5)) * cells_;

@@ -44,8 +44,13 @@ class Session {
     // the most recent armed call, dense (nz, nx) each, host or device pointers, any of them null
     void pseudo_hessian_arm(int every);
     void pseudo_hessian_get(float *hLambda, float *hMu, float *hDen);
+    // Born modelling and the Gauss-Newton product (session_born.cpp, sepfwi_born): the scattered gathers of v = (dLambda, dMu, dDen),
+    // shot after shot as [nrec][nSteps], each output optional; hv_* all null (J v only) or all set (J^T W J v, summed over the shots)
+    void born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+              const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
+              hipStream_t ext_stream);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
-    // by the last call, dense (nz - nPad, nx) row-major, host or device pointer
+    // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
     const Params &params() const { return par_; }
 
@@ -196,6 +201,9 @@ class Session {
     int ph_nsets_ = 0;
     float *ph_out_ = nullptr;
     bool ph_valid_ = false;
+    // Born modelling (born.hpp), allocated on the first Born call: [5 scattered fields | their 8 C-PML memories | 5 perturbed-media
+    // arrays] and the staging of a perturbation that does not live on this device
+    float *born_ = nullptr, *born_stage_ = nullptr;
     // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): fields + memories, frames, seismograms,
     // residual, stream, join event
     static constexpr int kMaxLanes = 4;

@@ -1,0 +1,164 @@
+// session_born.cpp -- Session::born: Born modelling J v and the Gauss-Newton product J^T W J v (born.hpp, sepfwi_born).
+//
+// One shot after the other on the call's stream, in lane 0 of the session (its own state, frames, gathers and residual buffer): the
+// batched multi-lane schedule of Session::run is NOT used here -- a Born pass streams twice the arrays of a forward pass, so fewer
+// shots share the cache; measuring a batched form is left for later.  Per shot:
+//   forward time loop   k_born_stress / k_born_velocity advance background and scattered field; the existing samplers (k_record,
+//                       k_record_gauge: one-cell, vertical, directional and gauge channels, vx, vz) read the SCATTERED fields
+//   gathers             transposed to [nrec][nSteps] and copied out
+//   product only        the residual buffer is filled with -(w_c dsyn_c) (k_born_residual) where a gradient call's residual kernel
+//                       would put w_c (obs_c - syn_c), and Session::backward runs as in a gradient call: persistent loop or two-launch
+//                       step, injection plans, the background's saved boundary frames
+// and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
+// state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+
+#include "born.hpp"
+#include "das_gauge.hpp"
+#include "device_alloc.hpp"
+#include "geophone.hpp"
+#include "hip_check.hpp"
+#include "kernels.hpp"
+#include "session.hpp"
+
+namespace sepfwi {
+
+static bool on_device(const void *p, int dev) {
+    if (!p) return false;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();  // plain host memory is reported as an error on some ROCm versions
+        return false;
+    }
+    return (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) && attr.device == dev;
+}
+
+void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                   const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
+                   hipStream_t ext_stream) {
+    std::lock_guard<std::mutex> lock(mu_);
+    const auto t_begin = std::chrono::steady_clock::now();
+    const bool want_hv = hv_Lambda != nullptr;
+    // refusals first: nothing is touched
+    if (want_hv && cond_on_)
+        throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit (if_win / filter / if_cross_misfit / if_src_update); "
+                                    "the scattered gathers alone are served (hv_* = NULL)");
+    for (int i = 0; i < group_size; i++) {
+        const int id = shot_ids[i];
+        if (id < 0 || id >= (int)survey_.shots.size() || !survey_.shots[id].present)
+            throw std::invalid_argument("shot id " + std::to_string(id) + " is not in the survey file");
+    }
+    HIP_OK(hipSetDevice(gpu_id_));
+    Call c;
+    c.opt = kernel_options();
+    c.opt.quiet_skip = 0;
+    c.st = ext_stream ? ext_stream : own_stream_;
+    if (!ext_stream) order_after_null_stream(c.st);
+    c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files)
+    c.group_size = group_size;
+    c.shot_ids = shot_ids;
+    hipStream_t st = c.st;
+    launches_ = 0;
+    fwd_ms_ = bwd_ms_ = 0.0;
+    probe_us_ = 0.0;
+    probe_calls_ = 0;
+    fwd_steps_ = bwd_steps_ = persist_steps_ = 0;
+    quiet_active_ = quiet_total_ = 0;
+    quiet_last_ = nullptr;
+    last_batched_ = false;
+
+    prepare_media(c, Lambda, Mu, Den);  // (the Courant guard: the background model only)
+    prepare_buffers(c, stf);
+
+    const size_t n = cells_, dense = (size_t)par_.nz * (size_t)par_.nx;
+    const int nSteps = par_.nSteps;
+    if (!born_) {
+        const size_t bytes = 18 * n * sizeof(float);
+        HIP_OK(dev_malloc((void **)&born_, bytes));
+        device_bytes_ += (long long)bytes;
+    }
+    const float *dv[3] = {dLambda, dMu, dDen};
+    for (int k = 0; k < 3; k++) {
+        if (on_device(dv[k], gpu_id_)) continue;
+        if (!born_stage_) {
+            HIP_OK(dev_malloc((void **)&born_stage_, 3 * dense * sizeof(float)));
+            device_bytes_ += (long long)(3 * dense * sizeof(float));
+        }
+        HIP_OK(hipMemcpyAsync(born_stage_ + (size_t)k * dense, dv[k], dense * sizeof(float), hipMemcpyDefault, st));
+        dv[k] = born_stage_ + (size_t)k * dense;
+    }
+    const float *mu_dense = on_device(Mu, gpu_id_) ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
+    float *dstate = born_, *dmedia = born_ + 13 * n;
+    launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
+    launches_++;
+
+    // which scattered gathers the call needs: the requested ones, and for the product the components with a weight
+    int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
+    if (want_hv) comps |= joint_ ? ((geo_block_[1] >= 0 ? 2 : 0) | (geo_block_[2] >= 0 ? 4 : 0) | (geo_block_[3] >= 0 ? 8 : 0)) : 8;
+    float *out[4] = {nullptr, d_vx, d_vz, d_ett};
+    size_t out_off = 0;
+    const BornArgs args{state_, dstate, media_, dmedia, pc_.a_z, n};
+    for (int is = 0; is < group_size; is++) {
+        ShotCtx x = make_ctx(c, is, 0, st, false);
+        x.scratch = false;
+        x.comps = comps;
+        ShotCtx xd = x;  // the samplers' view: the scattered fields
+        xd.fld = Fields{dstate, dstate + n, dstate + 2 * n, dstate + 3 * n, dstate + 4 * n};
+
+        HIP_OK(hipEventRecord(ev_[0], st));
+        forward_init(x);  // background state, column 0 of the gathers
+        HIP_OK(hipMemsetAsync(dstate, 0, 13 * n * sizeof(float), st));
+        for (int it = 0; it <= nSteps - 2; it++) {
+            float *frame_t = want_hv ? x.frame + (size_t)it * 5 * (size_t)g_.frame_len : nullptr;
+            const float amp = c.src_scale * x.stf_s[it] * par_.dt;
+            launch_born_stress(st, g_, c.opt, args, frame_t, x.sh->z_src, x.sh->x_src, amp);
+            launch_born_velocity(st, g_, c.opt, args);
+            launches_ += 2;
+            if (x.nrec > 0 && comps) record_column(xd, it + 1);
+        }
+        HIP_OK(hipEventRecord(ev_[1], st));
+        fwd_steps_ += (long long)(nSteps - 1);
+
+        const size_t cnt = (size_t)x.nrec * nSteps;
+        for (int k = 1; k <= 3 && cnt; k++) {
+            if (!out[k]) continue;
+            launch_transpose(st, syn_of(x, k), xpose_, nSteps, x.nrec);  // [it][rec] -> [rec][it]
+            HIP_OK(hipMemcpyAsync(out[k] + out_off, xpose_, cnt * sizeof(float), hipMemcpyDefault, st));
+            launches_++;
+        }
+        out_off += cnt;
+        if (want_hv && x.nrec > 0) {
+            BornRes q{};
+            q.res = x.res;
+            q.nrec = x.nrec;
+            if (joint_) {
+                q.nblk = geo_ncomp_;
+                for (int comp = 1; comp <= 3; comp++) {
+                    const int b = geo_block_[comp];
+                    if (b < 0) continue;
+                    q.dsyn[b] = syn_of(x, comp);
+                    q.w[b] = par_.weight(comp);
+                }
+            } else {
+                q.nblk = 1;
+                q.dsyn[0] = syn_of(x, 3);
+                q.w[0] = 1.0f;
+            }
+            launch_born_residual(st, q, nSteps);
+            launches_++;
+        }
+        HIP_OK(hipStreamSynchronize(st));
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
+        fwd_ms_ += ms;
+        if (want_hv) backward(c, x);  // (a shot without channels: nothing is injected, as in a gradient call)
+    }
+    if (want_hv) write_outputs(c, nullptr, hv_Lambda, hv_Mu, hv_Den, nullptr);
+    HIP_OK(hipStreamSynchronize(st));
+    total_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    last_shots_ = group_size;
+}
+
+}  // namespace sepfwi

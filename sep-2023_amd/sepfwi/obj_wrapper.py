@@ -165,3 +165,62 @@ def minimize_lbfgsb(fun, x0, jac, bounds=None, callback=None, maxiter=15000, max
     return optimize.OptimizeResult(fun=float(f), jac=g, nfev=state["nfev"], njev=state["nfev"], nit=nit, status=status,
                                    message=status_messages[task[0]] + ": " + task_messages[task[1]], x=x, success=(status == 0),
                                    hess_inv=optimize.LbfgsInvHessProduct(s[:n_corrs], y[:n_corrs]))
+
+
+def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2, callback=None):
+    """Matrix-free (preconditioned) conjugate gradients for the Gauss-Newton step:  (H + damping D) p = -g.
+
+    hessvec   callable: a tuple of tensors v -> the tuple H v (fwi_ops.gauss_newton at a fixed model; an extension without a
+              counterpart in the reference)
+    grad      the gradient g, a tuple of tensors shaped like v
+    diag      optional tuple of non-negative tensors, e.g. the diagonal pseudo-Hessian: D in the damping term AND the Jacobi
+              preconditioner M = D (zero entries -- outside the illuminated region -- are floored at 1e-12 max D); None: D = M = I
+    maxiter   fixed cap on the products; rtol: stop once |r| <= rtol |g| in the preconditioned norm sqrt(r^T M^-1 r)
+    -> (p, history): the step as a list of tensors and the relative residual before every iteration and after the last one
+    (history[0] = 1).  An iteration that meets non-positive curvature (the reference's adjoint is not exact) stops the solve with the
+    step found so far (the scaled steepest-descent direction if it is the first)."""
+    g = [t.detach() for t in grad]
+    dot = lambda a, b: float(sum((x.double() * y.double()).sum() for x, y in zip(a, b)))
+    if diag is None:
+        minv = None
+        D = None
+    else:
+        D = [d.detach().clamp_min(0) for d in diag]
+        minv = [1.0 / d.clamp_min(1e-12 * float(d.max()) if float(d.max()) > 0 else 1.0) for d in D]
+    prec = (lambda r: [t.clone() for t in r]) if minv is None else (lambda r: [a * b for a, b in zip(minv, r)])
+
+    def A(v):
+        hv = [t.detach() for t in hessvec(tuple(v))]
+        if damping:
+            hv = [h + damping * (x if D is None else D[k] * x) for k, (h, x) in enumerate(zip(hv, v))]
+        return hv
+
+    p = [torch.zeros_like(t) for t in g]
+    r = [-t for t in g]
+    z = prec(r)
+    d = [t.clone() for t in z]
+    rz = dot(r, z)
+    rz0 = rz
+    hist = [1.0]
+    if not rz0 > 0:
+        return p, hist
+    for it in range(int(maxiter)):
+        Ad = A(d)
+        curv = dot(d, Ad)
+        if not curv > 0:
+            if it == 0:
+                p = [t.clone() for t in d]
+            break
+        alpha = rz / curv
+        p = [a + alpha * b for a, b in zip(p, d)]
+        r = [a - alpha * b for a, b in zip(r, Ad)]
+        z = prec(r)
+        rz_new = dot(r, z)
+        hist.append(float(np.sqrt(max(rz_new, 0.0) / rz0)))
+        if callback is not None:
+            callback(it + 1, hist[-1])
+        if hist[-1] <= rtol:
+            break
+        d = [a + (rz_new / rz) * b for a, b in zip(z, d)]
+        rz = rz_new
+    return p, hist

@@ -249,6 +249,85 @@ class _FwiOps:
                 [f.result() for f in futs]
         return None
 
+    # -- Born modelling and the Gauss-Newton product (sepfwi_born) -------------------------------
+    def _born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, with_hv):
+        if int(ngpu) != 1:
+            raise ValueError("born / gauss_newton run on ONE GPU (ngpu = 1): the multi-GPU shot split is not implemented for them")
+        if _dist.active():
+            raise ValueError("born / gauss_newton do not run under torch.distributed: the multi-rank path is not implemented for them")
+        comp_id = {"vx": 0, "vz": 1, "ett": 2}
+        components = tuple(components)
+        for c in components:
+            if c not in comp_id:
+                raise ValueError("components must be among 'ett', 'vx', 'vz', got %r" % (c,))
+        L = _native.lib()
+        Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
+        dLambda, dMu, dDen = _f32c(dLambda, "dLambda"), _f32c(dMu, "dMu"), _f32c(dDen, "dDen")
+        if Lambda.dim() != 2 or any(t.shape != Lambda.shape for t in (Mu, Den, dLambda, dMu, dDen)):
+            raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must be 2-D tensors of one shape (nz_pad, nx_pad)")
+        if any(t.device != Lambda.device for t in (Mu, Den, dLambda, dMu, dDen)):
+            raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must live on one device")
+        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
+        dims = _para_dims(para_fname)
+        if dims is None:
+            raise ValueError("cannot read nz, nx, nSteps from the parameter file %r" % (para_fname,))
+        nz, nx, nSteps = dims
+        if tuple(Lambda.shape) != (nz, nx):
+            raise ValueError("the model and its perturbation are %s but the parameter file says (nz, nx) = (%d, %d)" % (tuple(Lambda.shape), nz, nx))
+        if Stf.dim() != 2 or Stf.shape[1] != nSteps:
+            raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
+            raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
+        import json
+        with open(para_fname) as fp:
+            survey_fname = json.loads(fp.readline())["survey_fname"]
+        with open(survey_fname) as fp:
+            survey = json.loads(fp.readline())
+        nrec = []
+        for i in ids:
+            if "shot%d" % int(i) not in survey:
+                raise ValueError("shot id %d is not in the survey file" % int(i))
+            nrec.append(len(survey["shot%d" % int(i)]["z_rec"]))
+        gpu_id = self._device_for(Lambda, 0)
+        gdev = torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+        total = int(sum(nrec)) * nSteps
+        bufs = [None, None, None]
+        for c in components:
+            bufs[comp_id[c]] = torch.zeros(max(total, 1), dtype=torch.float32, device=gdev)
+        hv = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev) if with_hv else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stream = None
+        if Lambda.is_cuda and Lambda.device.index == gpu_id:
+            cs = torch.cuda.current_stream(Lambda.device).cuda_stream
+            stream = C.c_void_p(cs) if cs else None
+        elif Lambda.is_cuda:
+            torch.cuda.synchronize(Lambda.device)
+        if Stf.is_cuda:
+            torch.cuda.synchronize(Stf.device)
+        rc = L.sepfwi_born(ptr(bufs[2]), ptr(bufs[0]), ptr(bufs[1]), ptr(hv[0]) if with_hv else None, ptr(hv[1]) if with_hv else None,
+                           ptr(hv[2]) if with_hv else None, ptr(Lambda), ptr(Mu), ptr(Den), ptr(dLambda), ptr(dMu), ptr(dDen), ptr(Stf), gpu_id,
+                           int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+        _native.check(rc)
+        out, off = [], 0
+        for n in nrec:
+            out.append({c: bufs[comp_id[c]][off:off + n * nSteps].view(n, nSteps).to(Lambda.device) for c in components})
+            off += n * nSteps
+        return out, (None if hv is None else hv.to(Lambda.device))
+
+    def born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components=("ett",)):
+        """Born modelling J v (include/sepfwi.h, sepfwi_born): the first-order change of every gather for the model perturbation
+        v = (dLambda, dMu, dDen), propagated next to the background field -- no finite difference, no step size.
+        -> a list with one dict per shot of Shot_ids, component name ("ett", "vx", "vz") -> (nrec, nSteps) float32 on the model's device.
+        One GPU only (ngpu = 1, no torch.distributed): ValueError otherwise."""
+        return self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, False)[0]
+
+    def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname):
+        """The Gauss-Newton Hessian-vector product J^T W J v, summed over Shot_ids -> (hvLambda, hvMu, hvDen), each (nz_pad, nx_pad):
+        the gradient `backward` would return at the model if the observed data were syn - J v (W: the misfit weights of the parameter
+        file).  Refused (SepFwiError, SEPFWI_EINVAL) with a live data-conditioning key.  One GPU only, as born."""
+        hv = self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, (), True)[1]
+        return hv[0], hv[1], hv[2]
+
     # -- extras --------------------------------------------------------------------------------
     def set_observed(self, para_fname, shot_id, ett, gpu_id=0):
         """Observed axial-strain gather of one shot from a tensor ((nrec, nSteps) float32, CPU or HIP) instead of
