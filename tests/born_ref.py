@@ -17,13 +17,15 @@ Perturbed media, float64 numpy from the oracle's own aMu, bA, bB (arrays [x][z])
     dlam = 1e6 dLambda, dmu = 1e6 dMu
     damu = (aMu^2 / 4) sum_k dmu_k / mu_k^2  over (z,x), (z+1,x), (z,x+1), (z+1,x+1);  0 where aMu is 0
     dba  = -(bA^2 / 2) (dDen(z+1,x) + dDen(z,x)),   dbb = -(bB^2 / 2) (dDen(z,x+1) + dDen(z,x))
-Default oracle build only (nothing fused)."""
+Either oracle build serves: both export the same kernels and helpers, and the loop run on the nvfma build (the reference binary's fused
+multiply-adds inside the kernels) is a second valid rounding of the same arithmetic -- the yardstick of the fuzz tests."""
 import ctypes as C
 
 import numpy as np
 
 from geophone_ref import _Cpml, _fp
 
+EXPORTS = ("ofwi_el_stress", "ofwi_el_velocity", "ofwi_model_average", "ofwi_cpml_init")      # what the loop needs of an oracle build
 FIELDS = ("vz", "vx", "szz", "sxx", "sxz")
 MEM_S = ("dvz_dz", "dvz_dx", "dvx_dz", "dvx_dx")          # written by the stress kernel
 MEM_V = ("dszz_dz", "dsxz_dx", "dsxz_dz", "dsxx_dx")      # written by the velocity kernel
@@ -142,12 +144,14 @@ def _shot(L, prm, media, dmedia, cz, cx, stf, z_src, x_src, z_rec, x_rec, sens, 
     return syn, dsyn
 
 
-def born(oracle, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, shot_ids, para, survey, terms=(True, True, True)):
+def born(oracle, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, shot_ids, para, survey, terms=(True, True, True), stack=True):
     """oracle.cufd's model arguments plus the perturbation (dense (nz, nx) each).  One-cell horizontal or vertical channels and
     directional ones (no gauge length: tests expand gauges into their member channels).
-    -> dict(syn, dsyn: (nshots, 4, nrec, nSteps) background and scattered gathers [pr, vx, vz, ett]; dmedia: the five arrays [x][z])."""
-    assert oracle.VARIANT == "", "born_ref restates the unfused oracle build"
+    -> dict(syn, dsyn: (nshots, 4, nrec, nSteps) background and scattered gathers [pr, vx, vz, ett]; dmedia: the five arrays [x][z]).
+    stack=False: syn and dsyn are lists with one (4, nrec, nSteps) array per shot -- the shots may then have different channel counts."""
     L = oracle.lib()
+    missing = [f for f in EXPORTS if not hasattr(L, f)]
+    assert not missing, "this oracle build does not export %s" % ", ".join(missing)
     Stf = f32(Stf)
     ids = [int(i) for i in np.asarray(shot_ids).reshape(-1)]
     nz, nx, nSteps, nPml, nPad = [int(para[k]) for k in ("nz", "nx", "nSteps", "nPoints_pml", "nPad")]
@@ -173,6 +177,8 @@ def born(oracle, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, shot_ids, para, surve
                           sens, terms)
         syn_all.append(syn)
         dsyn_all.append(dsyn)
+    if not stack:
+        return dict(syn=syn_all, dsyn=dsyn_all, dmedia=dmed)
     return dict(syn=np.stack(syn_all), dsyn=np.stack(dsyn_all), dmedia=dmed)
 
 
@@ -187,3 +193,11 @@ def perturbation(pb, seed=3, scale=0.01, only=None, model="lame_init"):
         a = P.smooth_random(rng, m.shape, -1.0, 1.0, passes=6) * scale * float(np.abs(m).mean())
         out.append(f32(a if only is None or only == k else np.zeros_like(a)))
     return out
+
+
+def born_fuzz_perturbation(pb, seed, water_rows):
+    """perturbation(pb, seed) for a fuzz draw with `water_rows` rows of water on top (0: none): dMu is zero in the water rows -- a fluid
+    stays a fluid (the harmonic mean of mu is not differentiable at mu = 0), as in test_born_reference.perturbation."""
+    v = perturbation(pb, seed=seed)
+    v[1][:int(water_rows)] = 0.0
+    return v

@@ -8,7 +8,8 @@ over those functions, with ONE addition: after the axial-strain adds of a backwa
 (where the reference's res_injection_vx / _vz would add them, Src/utilities.cu:656-689), and
     misfit = 0.5 sum_shots ( w_ett sum r_ett^2 + w_vx sum r_vx^2 + w_vz sum r_vz^2 ),   the sums in float64.
 With weights (1, 0, 0) it returns the oracle's gradients, gStf and gathers bit for bit (tests/test_geophone_reference.py): that pin
-makes it a valid stand-in.  Default oracle build only (nothing fused)."""
+makes it a valid stand-in.  That pin holds on the default build (nothing fused); on the nvfma build, which exports the same kernels, the
+loop is a second valid rounding of the same arithmetic (the yardstick of tests/test_gpu_born_fuzz.py)."""
 import ctypes as C
 
 import numpy as np
@@ -157,8 +158,10 @@ def _shot(L, prm, media, cz, cx, stf, z_src, x_src, rxz, z_rec, x_rec, sens, cal
 def cufd(oracle, Lambda, Mu, Den, Stf, calc_id, shot_ids, para, survey, obs=None, weights=(1.0, 0.0, 0.0)):
     """The oracle's cufd call (oracle.cufd's arguments; no conditioning, no adj_src) with weights = (w_ett, w_vx, w_vz).
     -> dict(misfit, parts {vx, vz, ett: 0.5 sum r_c^2, float64}, gLambda, gMu, gDen, gStf, syn, res)."""
-    assert oracle.VARIANT == "", "geophone_ref restates the unfused oracle build"
     L = oracle.lib()
+    missing = [f for f in ("ofwi_el_stress", "ofwi_el_velocity", "ofwi_el_stress_adj", "ofwi_el_velocity_adj", "ofwi_model_average", "ofwi_cpml_init",
+                           "ofwi_bnd_len", "ofwi_bnd_map") if not hasattr(L, f)]
+    assert not missing, "this oracle build does not export %s" % ", ".join(missing)
     L.ofwi_bnd_len.restype = C.c_int
     f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
     Lambda, Mu, Den, Stf = f32(Lambda), f32(Mu), f32(Den), f32(Stf)

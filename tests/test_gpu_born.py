@@ -274,3 +274,172 @@ def test_refusals_are_error_codes(tmp_path, hip_ops):
         assert np.abs(plain[c]).max() > 0 and np.array_equal(plain[c], cond[c]), c
     hv = hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])      # the session still works
     assert all(torch.isfinite(h).all() and h.abs().max() > 0 for h in hv)
+
+
+# ---- water, kernel structures, the pseudo-Hessian, img_every --------------------------------------------------------------------
+def product_against_the_oracle(oracle, oracle_nvfma, pb, v, hv, water, tag):
+    """hv (three numpy arrays) against the oracle's gradient at obs = syn - J v formed from born_ref on the CPU, on both oracle builds:
+    the bound and the yardstick of tests/test_gpu_born_fuzz.py (those of tests/test_gpu_fuzz.py)."""
+    import test_gpu_born_fuzz as BF
+    b = dict(G=0, vertical=False, weights=None)
+    m = [t.numpy() for t in pb["lame_init"]]
+    sides = []
+    for lib in (oracle, oracle_nvfma):
+        syn, dsyn, _ = BF.born_side(lib, pb, pb["survey"], b, m, v)
+        sides.append(BF.shifted_gradient(lib, pb, pb["survey"], b, m, syn, dsyn))
+    ref, alt = sides
+    cond_g = 4.0 * 2.0 ** -24 * float(np.sqrt(ref["E"] / ref["misfit"]))
+    l2 = lambda a: float(np.linalg.norm(np.asarray(a, np.float64)))
+    for name, g in zip(BF.GRADS, hv):
+        r, a = ref[name], alt[name]
+        print("gauss-newton %s hv%s: rel-L2 deviation from the oracle's gradient at obs = syn - J v %.2e (the two oracle builds %.2e, cond_g %.1e)"
+              % (tag, name[1:], l2(g - r) / l2(r), l2(a - r) / l2(r), cond_g))
+    for name, g in zip(BF.GRADS, hv):
+        r, a = ref[name], alt[name]
+        assert np.isfinite(g).all() and l2(r) > 0, (tag, name)
+        assert l2(g - r) <= (1e-3 + cond_g) * l2(r) + 3.0 * l2(a - r), (tag, name)
+        if water:   # below a water layer the image is held on its own (against the larger of its own norm and 3 % of the whole image's)
+            yard = max(l2(r[water:]), 3e-2 * l2(r))
+            assert l2(g[water:] - r[water:]) <= (1e-3 + cond_g) * yard + 3.0 * l2(a[water:] - r[water:]), (tag, name, "below the water")
+
+
+def test_water_layer_50x90(tmp_path, oracle, oracle_nvfma, hip_ops):
+    """Problem W of tests/test_born_reference.py: 22 rows of water (mu = 0) on top, the source in the water, the fibre below the sea
+    bed; dMu = 0 in the water.  The gathers against the reference; the scattered sxz is exactly 0 wherever one of the four mu taps of
+    its average is a fluid cell (the am != 0 guard of k_born_media next to the average rebuilt on the fly); the product against the
+    oracle's gradient at shifted data."""
+    import test_born_reference as TB
+    pb, w = TB.make(tmp_path, "W")
+    v = TB.perturbation(pb, w)
+    hip_ops.release()
+    close(gpu_born(hip_ops, pb, v), ref_born(oracle, pb, v), "50x90 water")
+    sxz = hip_ops.debug_field(pb["para_fname"], 14).numpy()
+    mu = np.pad(pb["lame_init"][1].numpy(), ((0, 1), (0, 1)), mode="edge")
+    nzc, nx = sxz.shape
+    fluid = (mu[:nzc, :nx] == 0) | (mu[1:nzc + 1, :nx] == 0) | (mu[:nzc, 1:nx + 1] == 0) | (mu[1:nzc + 1, 1:nx + 1] == 0)
+    assert fluid[:w].all() and not fluid[w:].any()
+    assert np.isfinite(sxz).all() and np.abs(sxz[~fluid]).max() > 0
+    assert not np.any(sxz[fluid]), "scattered sxz in the water: %.3e" % np.abs(sxz[fluid]).max()
+    hv = hip_ops.gauss_newton(*[t.cuda() for t in pb["lame_init"]], *[torch.from_numpy(a).cuda() for a in v], pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
+    product_against_the_oracle(oracle, oracle_nvfma, pb, v, [h.cpu().numpy() for h in hv], w, "50x90 water")
+
+
+def _born_bits(hip_ops, pb, v, fn):
+    """gathers, the five background fields after the last shot's last step, hv -- of one session under the options in force"""
+    m = [t.cuda() for t in pb["lame_init"]]
+    tv = [torch.from_numpy(a).cuda() for a in v]
+    got = gpu_born(hip_ops, pb, v, para_fname=fn)
+    fields = [hip_ops.debug_field(fn, k) for k in range(5)]
+    hv = [t.cpu() for t in hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], fn)]
+    return got, fields, hv
+
+
+def test_kernel_structures_give_the_default_structure_s_bits(probes_lib, hip_ops, prob_a):
+    """bz in {1, 4, 8}, xcd_remap = 0 and rk_lazy = 0 change which thread updates which cell and when a C-PML coefficient is loaded,
+    not one operation on a value: Born gathers, background fields and the product equal the default structure's bit for bit (all on
+    the probes build of the library, which alone exposes these options).
+    rho_fly = 0 and amu_fly = 0 read the stored averages instead of rebuilding them (for mu another rounding): there the background
+    equals a plain forward pass under the same option bit for bit, and the gathers meet the tolerance against the reference."""
+    pb, v, ref = prob_a
+    fn, _ = write_para(pb, "structures")
+    m = [t.cuda() for t in pb["lame_init"]]
+    tv = [torch.from_numpy(a).cuda() for a in v]
+    with P.kernel_options():
+        assert all(probes_lib.sepfwi_get_option(k.encode()) == P.OPTION_DEFAULTS[k] for k in ("bz", "xcd_remap", "rk_lazy", "rho_fly", "amu_fly"))
+        base = _born_bits(hip_ops, pb, v, fn)
+    assert all(f.abs().max() > 0 for f in base[1]) and all(h.abs().max() > 0 for h in base[2])
+    for opts in (dict(bz=1), dict(bz=4), dict(bz=8), dict(xcd_remap=0), dict(rk_lazy=0)):
+        with P.kernel_options(**opts):
+            assert all(probes_lib.sepfwi_get_option(k.encode()) == val for k, val in opts.items()), (opts, "the option is not in force")
+            got, fields, hv = _born_bits(hip_ops, pb, v, fn)
+        for c in COMPS:
+            assert np.array_equal(got[c], base[0][c]), (opts, c)
+        for k in range(5):
+            assert torch.equal(fields[k], base[1][k]), (opts, "background field %d" % k)
+        for k in range(3):
+            assert torch.equal(hv[k], base[2][k]), (opts, "hv %d" % k)
+    hip_ops.obscalc(*[t.cuda() for t in pb["lame_true"]], pb["Stf"], 1, pb["Shot_ids"], fn, to_store=True)
+    last = pb["Shot_ids"][-1:].clone()
+    for opts in (dict(rho_fly=0), dict(amu_fly=0)):
+        with P.kernel_options(batch=0, **opts):
+            assert all(probes_lib.sepfwi_get_option(k.encode()) == val for k, val in opts.items()), (opts, "the option is not in force")
+            hip_ops.forward(*m, pb["Stf"], 0, last, fn)
+            plain = [hip_ops.debug_field(fn, k) for k in range(5)]
+            got = gpu_born(hip_ops, pb, v, para_fname=fn)
+            for k in range(5):
+                assert plain[k].abs().max() > 0 and torch.equal(hip_ops.debug_field(fn, k), plain[k]), (opts, "background field %d" % k)
+        close(got, ref, "50x90 %r" % (opts,))
+        if "amu_fly" in opts:   # (the stored average is the double-precision one, the rebuilt one uses the hardware reciprocal; the stored
+            # buoyancies are the rebuilt ones' bits, so rho_fly = 0 changes where a value comes from and not the value)
+            assert any(not np.array_equal(got[c], base[0][c]) for c in COMPS), (opts, "the option changed nothing: it was not in force")
+
+
+def test_born_calls_leave_the_pseudo_hessian_untouched(hip_ops, prob_a):
+    """The pseudo-Hessian of an armed gradient call, read again after a Born call and a product: the bits it had (a Born pass runs the
+    forward body, which is also what accumulates the pseudo-Hessian when it is armed)."""
+    from sepfwi import _native
+    pb, v, _ = prob_a
+    hip_ops.release()
+    fn = pb["para_fname"]
+    m = [t.cuda() for t in pb["lame_init"]]
+    tv = [torch.from_numpy(a).cuda() for a in v]
+    hip_ops.obscalc(*[t.cuda() for t in pb["lame_true"]], pb["Stf"], 1, pb["Shot_ids"], fn, to_store=True)
+    out = hip_ops.backward(*m, pb["Stf"], 1, pb["Shot_ids"], fn, pseudo_hessian=2)
+    before = [h.cpu() for h in out[5:8]]
+    assert len(before) == 3 and all(h.abs().max() > 0 for h in before)
+
+    def read():
+        H = torch.empty((3,) + tuple(m[0].shape), dtype=torch.float32)
+        _native.check(_native.lib().sepfwi_get_pseudo_hessian(fn.encode(), 0, *[C.c_void_p(H[k].data_ptr()) for k in range(3)]))
+        return H
+
+    assert all(torch.equal(a, b) for a, b in zip(read(), before))
+    hip_ops.born(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], fn, components=COMPS)
+    assert all(torch.equal(a, b) for a, b in zip(read(), before)), "after the Born call"
+    hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], fn)
+    assert all(torch.equal(a, b) for a, b in zip(read(), before)), "after the product"
+    again = hip_ops.backward(*m, pb["Stf"], 1, pb["Shot_ids"], fn, pseudo_hessian=2)
+    assert all(torch.equal(a.cpu(), b) for a, b in zip(again[5:8], before)) and all(torch.equal(a.cpu(), b.cpu()) for a, b in zip(again[:4], out[:4]))
+
+
+def test_gauss_newton_product_with_img_every_2(hip_ops, prob_a):
+    """5: img_every = 2 (the imaging condition on every second step) -- the product is the gradient `backward` returns at shifted data
+    under the same option, and not the one of img_every = 1."""
+    pb, v, _ = prob_a
+    hip_ops.release()
+    m = [t.cuda() for t in pb["lame_init"]]
+    tv = [torch.from_numpy(a).cuda() for a in v]
+    every = [t.cpu().numpy() for t in hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])]
+    with P.kernel_options(img_every=2):
+        dev, bound, _ = gn_against_backward(hip_ops, pb, v, (1.0, 0.0, 0.0), "img2")
+        second = [t.cpu().numpy() for t in hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])]
+    assert max(dev) <= bound, (dev, bound)
+    assert all(not np.array_equal(a, b) for a, b in zip(second, every)), "img_every = 2 changed nothing: the option was not in force"
+    hip_ops.release()
+
+
+def test_quiet_skip_is_ignored_by_born_calls_after_a_quiet_misfit_call(hip_ops, prob_a):
+    """quiet_skip = 1: a plain misfit call on the fused channel line leaves quiet maps in the session (quiet_total > 0).  Born
+    modelling and the product of the SAME session under the same option then ignore the option -- the scattered field has no quiet
+    maps, and the product's backward half must not consult stale or empty ones: gathers and hv equal, bit for bit, those of a fresh
+    session that never saw the option."""
+    pb, v, _ = prob_a
+    fn, _ = write_para(pb, "quiet")
+    m = [t.cuda() for t in pb["lame_init"]]
+    tv = [torch.from_numpy(a).cuda() for a in v]
+    hip_ops.release()
+    with P.kernel_options(quiet_skip=1):
+        hip_ops.obscalc(*[t.cuda() for t in pb["lame_true"]], pb["Stf"], 1, pb["Shot_ids"], fn, to_store=True)
+        hip_ops.forward(*m, pb["Stf"], 0, pb["Shot_ids"], fn)
+        assert hip_ops.stats(fn)["quiet_total"] > 0, "the misfit call did not run with quiet maps: the test would compare nothing"
+        quiet = gpu_born(hip_ops, pb, v, para_fname=fn)
+        hv_quiet = [t.cpu() for t in hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], fn)]
+    hip_ops.release()
+    with P.kernel_options(quiet_skip=0):
+        plain = gpu_born(hip_ops, pb, v, para_fname=fn)
+        hv_plain = [t.cpu() for t in hip_ops.gauss_newton(*m, *tv, pb["Stf"], 1, pb["Shot_ids"], fn)]
+    for c in COMPS:
+        assert np.abs(plain[c]).max() > 0 and np.array_equal(quiet[c], plain[c]), c
+    for k in range(3):
+        assert hv_plain[k].abs().max() > 0 and torch.equal(hv_quiet[k], hv_plain[k]), "hv %d" % k
+    hip_ops.release()
