@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--shot-stride", type=int, default=1, help="use every k-th of the 19 shots")
     ap.add_argument("--device", default="cpu", choices=["cpu", "cuda"], help="where the model tensors live")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--exact-adjoint", action="store_true",
+                    help="the CG operator uses the exact discrete adjoint (fwi_ops.gauss_newton(exact=True)): symmetric and non-negative on Omega")
     a = ap.parse_args()
     dev = torch.device(a.device)
 
@@ -77,7 +79,7 @@ def main():
         if f0_ is None:
             f0_ = f
             print("iterate 0: misfit %.6e" % f, flush=True)
-        hv = lambda v: [Mask * t for t in fwi_ops.gauss_newton(*m, *[Mask * x for x in v], Stf, 1, ids, para_fname)]
+        hv = lambda v: [Mask * t for t in fwi_ops.gauss_newton(*m, *[Mask * x for x in v], Stf, 1, ids, para_fname, exact=a.exact_adjoint)]
         # The pseudo-Hessian leaves out the receiver side, and its three blocks are not on one scale (it is a preconditioner, not a
         # Hessian): calibrate each block on the Gauss-Newton curvature along its own preconditioned gradient z_k = -g_k / D_k,
         # D_k <- D_k (z_k^T H z_k) / (z_k^T D_k z_k) -- three products per outer iteration

@@ -174,6 +174,36 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
                 const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
                 const int *shot_ids, const char *para_fname, void *hip_stream);
 
+/*
+ * Extension (no counterpart in the reference; no reference run pins it): the exact discrete adjoint.  J^T as the transpose of the
+ * forward operator that sepfwi_born linearises -- coefficients, 1/K and a of the C-PML inside the transposed stencils, residual column
+ * nSteps-1 injected, no edge tests in the finalisation (csrc/exact_adjoint.hpp) -- so that <J v, w> = <v, J^T w> to float32 rounding.
+ * The reference's backward pass stays the default of every other call, bit for bit.  Results live on
+ *   Omega = rows nPml+1 ... nz-nPad-nPml-1, columns nPml+1 ... nx-nPml-1 of the padded (nz, nx) grid
+ * (the physical interior without its first row and first column) and are 0 elsewhere.  The mode follows from the inputs:
+ *   w_* set (any of w_ett, w_vx, w_vz), dLambda = dMu = dDen = NULL
+ *       g = J^T w, no weights and no sign.  w has the layout of sepfwi_born's d_*: [nrec_i][nSteps] shot after shot in the order of
+ *       shot_ids; column 0 is ignored.  A component needs a weight in the parameter file (misfit_w_*; ett by default): the session
+ *       injects only those.  misfit is untouched.
+ *   dLambda, dMu, dDen all set, w_* all NULL
+ *       g = P J^T W J P v, P the restriction to Omega (v is read on Omega only), W as sepfwi_born takes it; the background forward pass
+ *       is shared between J and J^T.  Symmetric and non-negative.  misfit is untouched.
+ *   neither set
+ *       g is the exact gradient on Omega of the session's misfit 1/2 sum_c w_c |obs_c - syn_c|^2 (all columns), and *misfit (may be
+ *       NULL) is that value, as sepfwi_cufd(calc_id 1) reports it.
+ * Every receiver geometry and parameter key of the forward pass applies (das_fiber, directional channels, das_gauge_length, misfit_w_*).
+ * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
+ * shot list; a live data-conditioning key; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  No
+ * gradient of the source time function is returned.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
+ * are read but never written; sepfwi_get_stats afterwards describes this call.  Schedule: one shot after the other on the call's
+ * stream, synchronous, two launches and one injection per backward time step; the persistent backward loop and the batched schedule
+ * are not used (sepfwi_loop_status says so), options img_every and quiet_skip are not consulted.  A process that never calls this
+ * function launches and allocates exactly what it did before.
+ */
+int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                         const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
+                         const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream);
+
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);
 

@@ -144,6 +144,27 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
     });
 }
 
+int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                         const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
+                         const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
+        if (!g_Lambda || !g_Mu || !g_Den) throw std::invalid_argument("adjoint_exact: g_Lambda, g_Mu and g_Den must not be NULL");
+        const int n_v = (dLambda ? 1 : 0) + (dMu ? 1 : 0) + (dDen ? 1 : 0);
+        if (n_v != 0 && n_v != 3) throw std::invalid_argument("adjoint_exact: dLambda, dMu, dDen must be all NULL or all set");
+        const bool have_w = w_ett || w_vx || w_vz;
+        if (n_v == 3 && have_w) throw std::invalid_argument("adjoint_exact: either v (the product) or w (J^T w), not both");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
+        if (n_v == 3)
+            s->born(nullptr, nullptr, nullptr, g_Lambda, g_Mu, g_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids,
+                    (hipStream_t)hip_stream, true);
+        else
+            s->adjoint_exact(misfit, g_Lambda, g_Mu, g_Den, w_ett, w_vx, w_vz, Lambda, Mu, Den, stf, group_size, shot_ids, (hipStream_t)hip_stream);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

@@ -1,0 +1,299 @@
+// exact_adjoint.hip -- the kernels of the exact discrete adjoint (exact_adjoint.hpp).  A translation unit of its own: the field kernels
+// (kernels.hip) are untouched.
+//
+// k_exact_a / k_exact_b keep the pairing, the launch shape and the cell mapping of k_bwd_a / k_bwd_b (one wave per 64-column row
+// segment, my_cell) and call the reverse-time bodies (velocity_body<false>, stress_body<false, false>, kernels_bodies.hpp: the same
+// inline code compiled with the same flags) unchanged, so reconstruction, frame restore and the five raw imaging accumulators are those
+// of a gradient call.  The two adjoint bodies are new: the exact transposes of stress_body<true> and velocity_body<true>, split into
+// LOAD (every tap, issued before the reverse-time body's first store) and APPLY (own-cell stores, adjoint memories) like the bodies
+// they stand in for.
+#include <hip/hip_runtime.h>
+
+#include "device_common.hpp"
+#include "exact_adjoint.hpp"
+
+namespace sepfwi {
+#include "kernels_device.hpp"
+#include "kernels_bodies.hpp"
+
+namespace {
+
+__device__ __forceinline__ Fields x_fields(float *b, size_t n) { return Fields{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
+__device__ __forceinline__ PmlMem x_mem(float *b, size_t n) { return PmlMem{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n}; }
+__device__ __forceinline__ Media x_media(const float *b, size_t n) { return Media{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n}; }
+__device__ __forceinline__ ImgAcc x_acc(float *b, size_t n) { return ImgAcc{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
+__device__ __forceinline__ PmlCoef x_coef(const float *cz, int nzc, int nx) {
+    const float *cx = cz + 6 * nzc;
+    return PmlCoef{cz, cz + nzc, cz + 2 * nzc, cz + 3 * nzc, cz + 4 * nzc, cz + 5 * nzc, cx, cx + nx, cx + 2 * nx, cx + 3 * nx, cx + 4 * nx, cx + 5 * nx};
+}
+
+// the x strips of the forward kernels: el_stress.cu:61,77 and el_velocity.cu:56,71 (one column narrower on the right)
+__device__ __forceinline__ bool strip_xs(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml - 1; }
+__device__ __forceinline__ bool strip_xv(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml; }
+__device__ __forceinline__ bool on_region(const Grid &g, int z, int x) { return !(z < 2 || z > g.nzc - 3 || x < 2 || x > g.nx - 3); }
+
+// What a forward cell (profile index k, flat index j) hands back to the field it differenced: e / K + a P inside its strip, e outside
+__device__ __forceinline__ float pml_tap(bool in, float e, const float *__restrict__ rK, const float *__restrict__ a, const float *P, int k, size_t j) {
+    return in ? e * rK[k] + a[k] * P[j] : e;
+}
+
+// ---------------------------------------------------------------------------------------------
+// V^T: adjoint stresses from the adjoint velocities (transpose of velocity_body<true>)
+// ---------------------------------------------------------------------------------------------
+struct VtIn {
+    bool on;
+    float szz, sxx, sxz, uz, ux, us;
+};
+__device__ __forceinline__ VtIn exact_vt_load(const Grid &g, const Cell &c, const Fields &a, const PmlMem &m, const Media &md, const PmlCoef &pc) {
+    VtIn q;
+    const int z = c.z, x = c.x, P = g.pitch;
+    q.on = on_region(g, z, x);
+    if (!q.on) return q;
+    const size_t i = c.i;
+    q.szz = a.szz[i];
+    q.sxx = a.sxx[i];
+    q.sxz = a.sxz[i];
+    auto fz = [&](size_t j) { return md.byc_a[j] * a.vz[j] * g.dt; };
+    auto fx = [&](size_t j) { return md.byc_b[j] * a.vx[j] * g.dt; };
+    float e1[4], e3[4], e2[4], e4[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        {   // z taps z-2 .. z+1 (D-z) of fz: the forward cell differenced szz with D+z, memory dszz_dz, half profiles
+            const int zt = z + k - 2;
+            const size_t j = i + (size_t)((long long)(k - 2) * P);
+            e1[k] = pml_tap(in_pml_z(g, zt), fz(j), pc.rK_zh, pc.a_zh, m.dszz_dz, zt, j);
+        }
+        {   // z taps z-1 .. z+2 (D+z) of fx: sxz differenced with D-z, memory dsxz_dz
+            const int zt = z + k - 1;
+            const size_t j = i + (size_t)((long long)(k - 1) * P);
+            e3[k] = pml_tap(in_pml_z(g, zt), fx(j), pc.rK_z, pc.a_z, m.dsxz_dz, zt, j);
+        }
+        {   // x taps x-1 .. x+2 (D+x) of fz: sxz differenced with D-x, memory dsxz_dx
+            const int xt = x + k - 1;
+            const size_t j = i + k - 1;
+            e2[k] = pml_tap(strip_xv(g, xt), fz(j), pc.rK_x, pc.a_x, m.dsxz_dx, xt, j);
+        }
+        {   // x taps x-2 .. x+1 (D-x) of fx: sxx differenced with D+x, memory dsxx_dx, half profiles
+            const int xt = x + k - 2;
+            const size_t j = i + k - 2;
+            e4[k] = pml_tap(strip_xv(g, xt), fx(j), pc.rK_xh, pc.a_xh, m.dsxx_dx, xt, j);
+        }
+    }
+    q.uz = -dminus(e1[0], e1[1], e1[2], e1[3], g.rdz);
+    q.ux = -dminus(e4[0], e4[1], e4[2], e4[3], g.rdx);
+    q.us = -dplus(e2[0], e2[1], e2[2], e2[3], g.rdx) - dplus(e3[0], e3[1], e3[2], e3[3], g.rdz);
+    return q;
+}
+__device__ __forceinline__ void exact_vt_apply(const VtIn &q, const Grid &g, const Cell &c, const Fields &a, const PmlMem &m, const Media &md,
+                                               const PmlCoef &pc) {
+    if (!q.on) return;
+    const int z = c.z, x = c.x;
+    const size_t i = c.i;
+    const float szz = q.szz + q.uz, sxx = q.sxx + q.ux, sxz = q.sxz + q.us;
+    a.szz[i] = szz;
+    a.sxx[i] = sxx;
+    a.sxz[i] = sxz;
+    const bool pz = in_pml_z(g, z), px = strip_xs(g, x);
+    if (pz || px) {  // the adjoint memories of the stress update, on its own strips: P <- b P + e
+        const float lam = md.lam[i], l2m = lam + 2.0f * md.mu[i];
+        const float e3 = md.ave_mu[i] * sxz * g.dt;
+        if (pz) {
+            m.dvz_dz[i] = pc.b_z[z] * m.dvz_dz[i] + (l2m * szz + lam * sxx) * g.dt;
+            m.dvx_dz[i] = pc.b_zh[z] * m.dvx_dz[i] + e3;
+        }
+        if (px) {
+            m.dvx_dx[i] = pc.b_x[x] * m.dvx_dx[i] + (lam * szz + l2m * sxx) * g.dt;
+            m.dvz_dx[i] = pc.b_xh[x] * m.dvz_dx[i] + e3;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// S^T: adjoint velocities from the adjoint stresses (transpose of stress_body<true>)
+// ---------------------------------------------------------------------------------------------
+struct StIn {
+    bool on;
+    float vz, vx, uz, ux;
+};
+__device__ __forceinline__ StIn exact_st_load(const Grid &g, const Cell &c, const Fields &a, const PmlMem &m, const Media &md, const PmlCoef &pc) {
+    StIn q;
+    const int z = c.z, x = c.x, P = g.pitch;
+    q.on = on_region(g, z, x);
+    if (!q.on) return q;
+    const size_t i = c.i;
+    q.vz = a.vz[i];
+    q.vx = a.vx[i];
+    auto e1 = [&](size_t j) { const float lam = md.lam[j]; return ((lam + 2.0f * md.mu[j]) * a.szz[j] + lam * a.sxx[j]) * g.dt; };
+    auto e2 = [&](size_t j) { const float lam = md.lam[j]; return (lam * a.szz[j] + (lam + 2.0f * md.mu[j]) * a.sxx[j]) * g.dt; };
+    auto e3 = [&](size_t j) { return md.ave_mu[j] * a.sxz[j] * g.dt; };
+    float g1[4], g2[4], g3[4], g4[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        {   // z taps z-1 .. z+2 (D+z) of e1: vz differenced with D-z, memory dvz_dz
+            const int zt = z + k - 1;
+            const size_t j = i + (size_t)((long long)(k - 1) * P);
+            g1[k] = pml_tap(in_pml_z(g, zt), e1(j), pc.rK_z, pc.a_z, m.dvz_dz, zt, j);
+        }
+        {   // z taps z-2 .. z+1 (D-z) of e3: vx differenced with D+z, memory dvx_dz, half profiles
+            const int zt = z + k - 2;
+            const size_t j = i + (size_t)((long long)(k - 2) * P);
+            g3[k] = pml_tap(in_pml_z(g, zt), e3(j), pc.rK_zh, pc.a_zh, m.dvx_dz, zt, j);
+        }
+        {   // x taps x-1 .. x+2 (D+x) of e2: vx differenced with D-x, memory dvx_dx
+            const int xt = x + k - 1;
+            const size_t j = i + k - 1;
+            g2[k] = pml_tap(strip_xs(g, xt), e2(j), pc.rK_x, pc.a_x, m.dvx_dx, xt, j);
+        }
+        {   // x taps x-2 .. x+1 (D-x) of e3: vz differenced with D+x, memory dvz_dx, half profiles
+            const int xt = x + k - 2;
+            const size_t j = i + k - 2;
+            g4[k] = pml_tap(strip_xs(g, xt), e3(j), pc.rK_xh, pc.a_xh, m.dvz_dx, xt, j);
+        }
+    }
+    q.uz = -dplus(g1[0], g1[1], g1[2], g1[3], g.rdz) - dminus(g4[0], g4[1], g4[2], g4[3], g.rdx);
+    q.ux = -dplus(g2[0], g2[1], g2[2], g2[3], g.rdx) - dminus(g3[0], g3[1], g3[2], g3[3], g.rdz);
+    return q;
+}
+__device__ __forceinline__ void exact_st_apply(const StIn &q, const Grid &g, const Cell &c, const Fields &a, const PmlMem &m, const Media &md,
+                                               const PmlCoef &pc) {
+    if (!q.on) return;
+    const int z = c.z, x = c.x;
+    const size_t i = c.i;
+    const float vz = q.vz + q.uz, vx = q.vx + q.ux;
+    a.vz[i] = vz;
+    a.vx[i] = vx;
+    const bool pz = in_pml_z(g, z), px = strip_xv(g, x);
+    if (pz || px) {  // the adjoint memories of the velocity update, on its own strips: Q <- b Q + f
+        const float fz = md.byc_a[i] * vz * g.dt, fx = md.byc_b[i] * vx * g.dt;
+        if (pz) {
+            m.dszz_dz[i] = pc.b_zh[z] * m.dszz_dz[i] + fz;
+            m.dsxz_dz[i] = pc.b_z[z] * m.dsxz_dz[i] + fx;
+        }
+        if (px) {
+            m.dsxz_dx[i] = pc.b_x[x] * m.dsxz_dx[i] + fz;
+            m.dsxx_dx[i] = pc.b_xh[x] * m.dsxx_dx[i] + fx;
+        }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(MAXT) void k_exact_a(Grid g, ExactArgs b, const float *__restrict__ frame_t) {
+    const Fields f = x_fields(b.fields, b.n), adj = x_fields(b.adj, b.n);
+    const PmlMem m = x_mem(b.mem, b.n);
+    const Media md = x_media(b.media, b.n);
+    const ImgAcc acc = x_acc(b.acc, b.n);
+    const PmlCoef pc = x_coef(b.cz, g.nzc, g.nx);
+    const Cell c = my_cell(g);
+    const VtIn q = exact_vt_load(g, c, adj, m, md, pc);  // (in flight together with the reverse-velocity loads)
+    velocity_body<false>(g, c, f, m, md, pc, frame_t, -1, -1, 0.0f, nullptr, adj, AccG{acc});
+    exact_vt_apply(q, g, c, adj, m, md, pc);
+}
+
+__global__ __launch_bounds__(MAXT) void k_exact_b(Grid g, ExactArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp,
+                                                  int adjoint_only) {
+    const Fields f = x_fields(b.fields, b.n), adj = x_fields(b.adj, b.n);
+    const PmlMem m = x_mem(b.mem, b.n);
+    const Media md = x_media(b.media, b.n);
+    const ImgAcc acc = x_acc(b.acc, b.n);
+    const PmlCoef pc = x_coef(b.cz, g.nzc, g.nx);
+    const Cell c = my_cell(g);
+    const StIn q = exact_st_load(g, c, adj, m, md, pc);
+    if (!adjoint_only)  // launch-uniform
+        stress_body<false, false>(g, c, f, m, md, pc, frame_t, zx_src >> 16, zx_src & 0xffff, src_amp, adj, AccG{acc}, LineRec{});
+    exact_st_apply(q, g, c, adj, m, md, pc);
+}
+
+// The transposes of k_born_media's maps on Omega (exact_adjoint.hpp), in the launch shape of k_finalize_gradients: dense (nz, nx) outputs.
+__global__ void k_exact_finalize(Grid g, Media md, ImgAcc acc, float *__restrict__ gLam, float *__restrict__ gMu, float *__restrict__ gDen) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int z = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= g.nx || z >= g.nz) return;
+    const size_t o = (size_t)z * g.nx + x;
+    float gl = 0.0f, gm = 0.0f, gd = 0.0f;
+    if (z >= g.nPml + 1 && z <= g.zmax && x >= g.nPml + 1 && x <= g.xmax) {
+        const size_t i = (size_t)z * g.pitch + x, P = (size_t)g.pitch;
+        gl = (float)((double)acc.lam[i] * 1e6);
+        const double mu = md.mu[i];
+        double s = 0.0;
+        const size_t p4[4] = {i, i - P, i - 1, i - P - 1};  // the four staggered corners whose harmonic mean holds this cell
+        for (int k = 0; k < 4; k++) {
+            const double am = md.ave_mu[p4[k]];
+            if (am != 0.0) s += am * am * 0.25 * (double)acc.xz[p4[k]];  // (a zero average: a fluid corner, its derivative is 0)
+        }
+        gm = (float)(((double)acc.mu[i] + (mu != 0.0 ? s / (mu * mu) : 0.0)) * 1e6);
+        const double a0 = md.byc_a[i], a1 = md.byc_a[i - P], b0 = md.byc_b[i], b1 = md.byc_b[i - 1];
+        gd = (float)(-0.5 * (a0 * a0 * (double)acc.a[i] + a1 * a1 * (double)acc.a[i - P] + b0 * b0 * (double)acc.b[i] + b1 * b1 * (double)acc.b[i - 1]));
+    }
+    gLam[o] = gl;
+    gMu[o] = gm;
+    gDen[o] = gd;
+}
+
+__global__ void k_exact_mask(Grid g, float *__restrict__ v, int k, size_t dense) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int z = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= g.nx || z >= g.nz) return;
+    if (z >= g.nPml + 1 && z <= g.zmax && x >= g.nPml + 1 && x <= g.xmax) return;
+    for (int a = 0; a < k; a++) v[(size_t)a * dense + (size_t)z * g.nx + x] = 0.0f;
+}
+
+__global__ void k_exact_residual(ExactRes q, int nSteps) {
+    const int b = blockIdx.y;  // gridDim.y = q.nblk
+    const float *__restrict__ w = q.w[b];
+    float *__restrict__ res = q.res + (size_t)b * (size_t)q.nrec;
+    const int nrec = q.nrec;
+    const size_t row = (size_t)q.nblk * (size_t)nrec;
+    const long long n = (long long)nrec * (long long)nSteps;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+        const long long it = k / nrec;
+        const int r = (int)(k - it * nrec);
+        res[(size_t)it * row + r] = (it == 0 || !w) ? 0.0f : -w[(size_t)r * (size_t)nSteps + (size_t)it];
+    }
+}
+
+// the tiling of the backward field kernels (kernels.hip tiled(), fly bit 1): the reverse-time bodies take the paths of a gradient call
+static Grid exact_tiled(const Grid &g0, const KernelOptions &o) {
+    Grid g = g0;
+    g.bz = o.bz;
+    g.qr = 1;
+    g.gx = (g.nx + BX - 1) / BX;
+    g.gy = (g.nzc + g.bz - 1) / g.bz;
+    g.xcd_remap = o.xcd_remap;
+    g.rho_fly = (o.rho_fly >> 1) & 1;
+    g.amu_fly = (o.amu_fly >> 1) & 1;
+    g.rk_lazy = o.rk_lazy;
+    const int nb = g.gx * g.gy;
+    g.nblk = g.xcd_remap ? ((nb + 7) / 8) * 8 : nb;
+    return g;
+}
+
+void launch_exact_a(hipStream_t st, const Grid &g0, const KernelOptions &o, const ExactArgs &b, const float *frame_t) {
+    const Grid g = exact_tiled(g0, o);
+    hipLaunchKernelGGL(k_exact_a, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t);
+}
+
+void launch_exact_b(hipStream_t st, const Grid &g0, const KernelOptions &o, const ExactArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
+                    bool adjoint_only) {
+    const Grid g = exact_tiled(g0, o);
+    const int zx = adjoint_only ? 0 : (z_src << 16) | x_src;
+    hipLaunchKernelGGL(k_exact_b, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, zx, src_amp, adjoint_only ? 1 : 0);
+}
+
+void launch_exact_finalize(hipStream_t st, const Grid &g, Media md, ImgAcc acc, float *gLam, float *gMu, float *gDen) {
+    hipLaunchKernelGGL(k_exact_finalize, dim3((g.nx + 63) / 64, (g.nz + 3) / 4), dim3(64, 4), 0, st, g, md, acc, gLam, gMu, gDen);
+}
+
+void launch_exact_mask(hipStream_t st, const Grid &g, float *v, int k, size_t dense) {
+    hipLaunchKernelGGL(k_exact_mask, dim3((g.nx + 63) / 64, (g.nz + 3) / 4), dim3(64, 4), 0, st, g, v, k, dense);
+}
+
+void launch_exact_residual(hipStream_t st, const ExactRes &q, int nSteps) {
+    if (q.nrec <= 0 || q.nblk <= 0) return;
+    const long long n = (long long)q.nrec * nSteps;
+    const long long want = (n + 255) / 256;
+    const int bx = want > 1024 ? 1024 : want < 1 ? 1 : (int)want;
+    hipLaunchKernelGGL(k_exact_residual, dim3(bx, q.nblk), dim3(256), 0, st, q, nSteps);
+}
+
+}  // namespace sepfwi

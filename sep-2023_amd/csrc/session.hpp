@@ -48,7 +48,13 @@ class Session {
     // shot after shot as [nrec][nSteps], each output optional; hv_* all null (J v only) or all set (J^T W J v, summed over the shots)
     void born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
               const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
-              hipStream_t ext_stream);
+              hipStream_t ext_stream, bool exact = false);
+    // The exact discrete adjoint (exact_adjoint.hpp, session_exact.cpp, sepfwi_adjoint_exact): g = J^T w for the caller's w (any of
+    // w_ett, w_vx, w_vz set; gathers as born() writes them), or, with all of them null, the exact gradient on Omega of the session's
+    // misfit and the misfit itself.  (The product P J^T W J P v is born(..., exact = true).)
+    void adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                       const float *Lambda, const float *Mu, const float *Den, const float *stf, int group_size, const int *shot_ids,
+                       hipStream_t ext_stream);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
@@ -134,6 +140,9 @@ class Session {
     void backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it);
     void inject_column(const ShotCtx &x, const BwdLane &L, const float *res_t);
     void backward(Call &c, const ShotCtx &x);
+    // the exact transposed time loop of one shot and its finalisation on Omega (session_exact.cpp); the persistent loop is not used
+    void backward_exact(Call &c, const ShotCtx &x);
+    void write_outputs_exact(Call &c, float *g_Lambda, float *g_Mu, float *g_Den);
     // the same pass as ONE persistent launch (option bwd_fuse = 4; kernels.hip k_bwd_persist)
     struct Persist;
     bool persist_ready(const Call &c, const ShotCtx &x);
@@ -229,6 +238,7 @@ class Session {
     float *d_stf_ = nullptr;
     size_t d_stf_len_ = 0;
     bool last_batched_ = false;
+    bool last_exact_ = false;  // the last call's backward passes were exact ones (loop_status)
     float *state_ = nullptr, *media_ = nullptr, *acc_buf_ = nullptr, *in_stage_ = nullptr, *grad_stage_ = nullptr;
     float *frame_ = nullptr, *syn_ = nullptr, *res_ = nullptr, *xpose_ = nullptr, *stf_grad_ = nullptr, *h_io_ = nullptr;
     double *scal_ = nullptr;

@@ -11,6 +11,8 @@
 //                       step, injection plans, the background's saved boundary frames
 // and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
 // state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
+// exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
+// finalisation the exact one on Omega (exact_adjoint.hpp) -- the product P J^T W J P v, symmetric and non-negative.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -18,6 +20,7 @@
 #include "born.hpp"
 #include "das_gauge.hpp"
 #include "device_alloc.hpp"
+#include "exact_adjoint.hpp"
 #include "geophone.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
@@ -37,7 +40,7 @@ static bool on_device(const void *p, int dev) {
 
 void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
-                   hipStream_t ext_stream) {
+                   hipStream_t ext_stream, bool exact) {
     std::lock_guard<std::mutex> lock(mu_);
     const auto t_begin = std::chrono::steady_clock::now();
     const bool want_hv = hv_Lambda != nullptr;
@@ -68,6 +71,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     quiet_active_ = quiet_total_ = 0;
     quiet_last_ = nullptr;
     last_batched_ = false;
+    last_exact_ = exact && want_hv;
 
     prepare_media(c, Lambda, Mu, Den);  // (the Courant guard: the background model only)
     prepare_buffers(c, stf);
@@ -81,13 +85,17 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     }
     const float *dv[3] = {dLambda, dMu, dDen};
     for (int k = 0; k < 3; k++) {
-        if (on_device(dv[k], gpu_id_)) continue;
+        if (!exact && on_device(dv[k], gpu_id_)) continue;  // (the exact product reads v on Omega only: it masks a copy)
         if (!born_stage_) {
             HIP_OK(dev_malloc((void **)&born_stage_, 3 * dense * sizeof(float)));
             device_bytes_ += (long long)(3 * dense * sizeof(float));
         }
         HIP_OK(hipMemcpyAsync(born_stage_ + (size_t)k * dense, dv[k], dense * sizeof(float), hipMemcpyDefault, st));
         dv[k] = born_stage_ + (size_t)k * dense;
+    }
+    if (exact) {
+        launch_exact_mask(st, g_, born_stage_, 3, dense);
+        launches_++;
     }
     const float *mu_dense = on_device(Mu, gpu_id_) ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
     float *dstate = born_, *dmedia = born_ + 13 * n;
@@ -153,9 +161,15 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         float ms = 0.f;
         HIP_OK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
         fwd_ms_ += ms;
-        if (want_hv) backward(c, x);  // (a shot without channels: nothing is injected, as in a gradient call)
+        if (want_hv && exact)
+            backward_exact(c, x);
+        else if (want_hv)
+            backward(c, x);  // (a shot without channels: nothing is injected, as in a gradient call)
     }
-    if (want_hv) write_outputs(c, nullptr, hv_Lambda, hv_Mu, hv_Den, nullptr);
+    if (want_hv && exact)
+        write_outputs_exact(c, hv_Lambda, hv_Mu, hv_Den);
+    else if (want_hv)
+        write_outputs(c, nullptr, hv_Lambda, hv_Mu, hv_Den, nullptr);
     HIP_OK(hipStreamSynchronize(st));
     total_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     last_shots_ = group_size;

@@ -223,6 +223,7 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
 
 std::string Session::loop_status() {
     std::lock_guard<std::mutex> lock(mu_);
+    if (last_exact_) return "the exact adjoint runs two launches per time step: the persistent loop is not used (exact_adjoint.hpp)";
     const Persist &k = last_batched_ ? pk_ms_ : pk_;  // the schedule of the last call: multi-shot loop (batched) or one loop per shot (streams)
     if (k.state < 0) return "not considered yet (no gradient call, bwd_fuse != 4, or shots whose channels are not fused lines in a batched call)";
     return k.state == 1 ? std::string() : k.why;

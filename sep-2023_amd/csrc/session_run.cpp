@@ -612,6 +612,7 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
     c.group_size = group_size;
     c.shot_ids = shot_ids;
     c.ph_every = c.if_res ? ph_every_ : 0;  // calc_id 2 and 3 never accumulate
+    last_exact_ = false;
     launches_ = 0;
     fwd_ms_ = bwd_ms_ = 0.0;
     probe_us_ = 0.0;

@@ -168,13 +168,21 @@ class _FwiOps:
         return i
 
     # -- reference surface -------------------------------------------------------------------
-    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0):
+    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0, exact_adjoint=False):
         """-> [misfit(1,), gLambda, gMu, gDen, gStf]   (fwi_backward, Src/Torch_Fwi.cpp:38-104).
+        Extension `exact_adjoint=True` (include/sepfwi.h, sepfwi_adjoint_exact): the same list, the gradients being the exact ones of
+        the misfit on Omega (0 outside) and gStf ZEROS -- the exact pass forms no gradient of the source time function.  One GPU, not
+        together with pseudo_hessian.
         Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
         shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
         and ranks like the gradients; under torch.distributed through ONE more all-reduce, of the fused [hL | hM | hD] buffer).
         With the default 0 the return value and every launch are those of the reference surface."""
         k = int(pseudo_hessian)
+        if exact_adjoint:
+            if k:
+                raise ValueError("exact_adjoint and pseudo_hessian cannot be combined in one call")
+            m, gL, gM, gD = self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname)
+            return [m, gL, gM, gD, torch.zeros_like(_f32c(Stf, "Stf").cpu())]
         kw = {"pseudo_hessian": k} if k else {}     # (not armed: _cufd is called exactly as the reference surface calls it)
         ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
         n = int(ids.numel())
@@ -321,12 +329,103 @@ class _FwiOps:
         One GPU only (ngpu = 1, no torch.distributed): ValueError otherwise."""
         return self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, False)[0]
 
-    def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname):
+    def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, exact=False):
         """The Gauss-Newton Hessian-vector product J^T W J v, summed over Shot_ids -> (hvLambda, hvMu, hvDen), each (nz_pad, nx_pad):
         the gradient `backward` would return at the model if the observed data were syn - J v (W: the misfit weights of the parameter
-        file).  Refused (SepFwiError, SEPFWI_EINVAL) with a live data-conditioning key.  One GPU only, as born."""
+        file).  Refused (SepFwiError, SEPFWI_EINVAL) with a live data-conditioning key.  One GPU only, as born.
+        exact=True (include/sepfwi.h, sepfwi_adjoint_exact): J^T is the exact transpose of J instead of the reference's backward pass,
+        and the product is P J^T W J P v with P the restriction to Omega (the physical interior without its first row and column; v is
+        read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding.  The default leaves every bit as
+        it was."""
+        if exact:
+            return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=(dLambda, dMu, dDen))[1:]
         hv = self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, (), True)[1]
         return hv[0], hv[1], hv[2]
+
+    # -- the exact discrete adjoint (sepfwi_adjoint_exact) ----------------------------------------
+    def _adjoint_exact(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=None, w=None):
+        """-> (misfit(1,), gLambda, gMu, gDen) on the model's device.  v: (dLambda, dMu, dDen) for the product; w: one dict per shot,
+        component name -> (nrec, nSteps), for J^T w; neither: the exact gradient of the session's misfit.  The shot split is _born's."""
+        if int(ngpu) != 1:
+            raise ValueError("the exact adjoint runs on ONE GPU (ngpu = 1): the multi-GPU shot split is not implemented for it")
+        if _dist.active():
+            raise ValueError("the exact adjoint does not run under torch.distributed: the multi-rank path is not implemented for it")
+        L = _native.lib()
+        Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
+        if Lambda.dim() != 2 or Mu.shape != Lambda.shape or Den.shape != Lambda.shape:
+            raise ValueError("Lambda, Mu, Den must be 2-D tensors of one shape (nz_pad, nx_pad)")
+        if Mu.device != Lambda.device or Den.device != Lambda.device:
+            raise ValueError("Lambda, Mu, Den must live on one device")
+        if v is not None:
+            v = [_f32c(t, n) for t, n in zip(v, ("dLambda", "dMu", "dDen"))]
+            if any(t.shape != Lambda.shape for t in v):
+                raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must be 2-D tensors of one shape (nz_pad, nx_pad)")
+            if any(t.device != Lambda.device for t in v):
+                raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must live on one device")
+        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
+        dims = _para_dims(para_fname)
+        if dims is None:
+            raise ValueError("cannot read nz, nx, nSteps from the parameter file %r" % (para_fname,))
+        nz, nx, nSteps = dims
+        if tuple(Lambda.shape) != (nz, nx):
+            raise ValueError("the model is %s but the parameter file says (nz, nx) = (%d, %d)" % (tuple(Lambda.shape), nz, nx))
+        if Stf.dim() != 2 or Stf.shape[1] != nSteps:
+            raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
+            raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
+        gpu_id = self._device_for(Lambda, 0)
+        gdev = torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+        wbuf = {"ett": None, "vx": None, "vz": None}
+        if w is not None:
+            import json
+            with open(para_fname) as fp:
+                survey_fname = json.loads(fp.readline())["survey_fname"]
+            with open(survey_fname) as fp:
+                survey = json.loads(fp.readline())
+            w = list(w)
+            if len(w) != ids.size:
+                raise ValueError("w must hold one dict of gathers per shot of Shot_ids")
+            comps = sorted({c for d in w for c in d})
+            if not comps or any(c not in wbuf for c in comps):
+                raise ValueError("w: components must be among 'ett', 'vx', 'vz', and at least one must be given")
+            for c in comps:
+                rows = []
+                for i, d in zip(ids, w):
+                    if "shot%d" % int(i) not in survey:
+                        raise ValueError("shot id %d is not in the survey file" % int(i))
+                    nrec = len(survey["shot%d" % int(i)]["z_rec"])
+                    t = d.get(c)
+                    t = torch.zeros((nrec, nSteps), dtype=torch.float32) if t is None else _f32c(torch.as_tensor(t), "w[%r]" % c)
+                    if tuple(t.shape) != (nrec, nSteps):
+                        raise ValueError("w[%r] of shot %d must be (nrec, nSteps) = (%d, %d), got %s" % (c, int(i), nrec, nSteps, tuple(t.shape)))
+                    rows.append(t.to(gdev).reshape(-1))
+                wbuf[c] = torch.cat(rows) if rows else torch.zeros(1, dtype=torch.float32, device=gdev)
+        g = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
+        misfit = torch.zeros(1, dtype=torch.float32)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stream = None
+        if Lambda.is_cuda and Lambda.device.index == gpu_id:
+            cs = torch.cuda.current_stream(Lambda.device).cuda_stream
+            stream = C.c_void_p(cs) if cs else None
+            torch.cuda.current_stream(Lambda.device).synchronize()   # (w was assembled on this stream; the library may run on its own)
+        elif Lambda.is_cuda:
+            torch.cuda.synchronize(Lambda.device)
+        if Stf.is_cuda:
+            torch.cuda.synchronize(Stf.device)
+        vp = [ptr(t) for t in v] if v is not None else [None, None, None]
+        rc = L.sepfwi_adjoint_exact(ptr(misfit), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(wbuf["ett"]), ptr(wbuf["vx"]), ptr(wbuf["vz"]), *vp,
+                                    ptr(Lambda), ptr(Mu), ptr(Den), ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data),
+                                    str(para_fname).encode(), stream)
+        _native.check(rc)
+        g = g.to(Lambda.device)
+        return misfit.to(Lambda.device), g[0], g[1], g[2]
+
+    def born_adjoint(self, Lambda, Mu, Den, w, Stf, ngpu, Shot_ids, para_fname):
+        """J^T w with the exact discrete adjoint (include/sepfwi.h, sepfwi_adjoint_exact): w is a list with one dict per shot of
+        Shot_ids, component name ("ett", "vx", "vz") -> (nrec, nSteps) float32 -- what `born` returns.  No weights, no sign; column 0
+        is ignored; a component needs a weight in the parameter file (ett by default).  -> (gLambda, gMu, gDen), each (nz_pad, nx_pad),
+        non-zero on Omega only.  One GPU only, as born."""
+        return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, w=w)[1:]
 
     # -- extras --------------------------------------------------------------------------------
     def set_observed(self, para_fname, shot_id, ett, gpu_id=0):
