@@ -1,4 +1,5 @@
 // born.hip -- the kernels of Born modelling (born.hpp).  A translation unit of its own: the field kernels (kernels.hip) are untouched.
+// Bundle unpacking (kernels_device.hpp) and the launch tiling (tiled(), kernels.hpp) are the field kernels' own.
 //
 // k_born_stress / k_born_velocity have the launch shape and the cell mapping of k_stress / k_velocity (one wave per 64-column row
 // segment, my_cell).  Each advances the BACKGROUND by calling the forward body (stress_body / velocity_body, kernels_bodies.hpp: the
@@ -17,14 +18,11 @@ namespace sepfwi {
 
 namespace {
 
-__device__ __forceinline__ Fields b_fields(float *b, size_t n) { return Fields{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
+// The eight C-PML memories of a state bundle [5 fields | 8 memories].  Kept beside the kernels, like the region and strip tests
+// written out in them: mem_of(b + 5 n, n), on_region and strip_xs / strip_xv (kernels_device.hpp) say the same, but with them the
+// compiler schedules k_born_stress / k_born_velocity differently, and their instruction text is held fixed.
 __device__ __forceinline__ PmlMem b_mem(float *b, size_t n) {
     return PmlMem{b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n, b + 9 * n, b + 10 * n, b + 11 * n, b + 12 * n};
-}
-__device__ __forceinline__ Media b_media(const float *b, size_t n) { return Media{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n}; }
-__device__ __forceinline__ PmlCoef b_coef(const float *cz, int nzc, int nx) {
-    const float *cx = cz + 6 * nzc;
-    return PmlCoef{cz, cz + nzc, cz + 2 * nzc, cz + 3 * nzc, cz + 4 * nzc, cz + 5 * nzc, cx, cx + nx, cx + 2 * nx, cx + 3 * nx, cx + 4 * nx, cx + 5 * nx};
 }
 
 // the four velocity derivatives of the stress update at cell i (the expressions of stress_body)
@@ -59,10 +57,10 @@ __device__ __forceinline__ VelD velocity_derivs(const Grid &g, const Fields &f, 
 
 template <bool SAVE>
 __global__ __launch_bounds__(MAXT) void k_born_stress(Grid g, BornArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp) {
-    const Fields f = b_fields(b.state, b.n), df = b_fields(b.dstate, b.n);
+    const Fields f = fields_of(b.state, b.n), df = fields_of(b.dstate, b.n);
     const PmlMem m = b_mem(b.state, b.n), dm = b_mem(b.dstate, b.n);
-    const Media md = b_media(b.media, b.n);
-    const PmlCoef pc = b_coef(b.cz, g.nzc, g.nx);
+    const Media md = media_of(b.media, b.n);
+    const PmlCoef pc = coef_of(b.cz, b.cz + 6 * g.nzc, g.nzc, g.nx);
     const Cell c = my_cell(g);
     const int z = c.z, x = c.x;
     const size_t i = c.i;
@@ -126,10 +124,10 @@ __global__ __launch_bounds__(MAXT) void k_born_stress(Grid g, BornArgs b, float 
 }
 
 __global__ __launch_bounds__(MAXT) void k_born_velocity(Grid g, BornArgs b) {
-    const Fields f = b_fields(b.state, b.n), df = b_fields(b.dstate, b.n);
+    const Fields f = fields_of(b.state, b.n), df = fields_of(b.dstate, b.n);
     const PmlMem m = b_mem(b.state, b.n), dm = b_mem(b.dstate, b.n);
-    const Media md = b_media(b.media, b.n);
-    const PmlCoef pc = b_coef(b.cz, g.nzc, g.nx);
+    const Media md = media_of(b.media, b.n);
+    const PmlCoef pc = coef_of(b.cz, b.cz + 6 * g.nzc, g.nzc, g.nx);
     const Cell c = my_cell(g);
     const int z = c.z, x = c.x;
     const size_t i = c.i;
@@ -214,45 +212,14 @@ __global__ void k_born_media(Grid g, const float *__restrict__ Mu_in, const floa
     dbb[i] = b_d;
 }
 
-__global__ void k_born_residual(BornRes q, int nSteps) {
-    const int b = blockIdx.y;  // gridDim.y = q.nblk
-    const float *__restrict__ d = q.dsyn[b];
-    float *__restrict__ res = q.res + (size_t)b * (size_t)q.nrec;
-    const float w = q.w[b];
-    const int nrec = q.nrec;
-    const size_t row = (size_t)q.nblk * (size_t)nrec;
-    const long long n = (long long)nrec * (long long)nSteps;
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
-        const long long it = k / nrec;
-        const int r = (int)(k - it * nrec);
-        res[(size_t)it * row + r] = (it == 0) ? 0.0f : -(w * d[k]);
-    }
-}
-
-// the tiling of the forward field kernels (kernels.hip tiled(), fly bit 0): the background must take the paths of a plain forward pass
-static Grid born_tiled(const Grid &g0, const KernelOptions &o) {
-    Grid g = g0;
-    g.bz = o.bz;
-    g.qr = 1;
-    g.gx = (g.nx + BX - 1) / BX;
-    g.gy = (g.nzc + g.bz - 1) / g.bz;
-    g.xcd_remap = o.xcd_remap;
-    g.rho_fly = o.rho_fly & 1;
-    g.amu_fly = o.amu_fly & 1;
-    g.rk_lazy = o.rk_lazy;
-    const int nb = g.gx * g.gy;
-    g.nblk = g.xcd_remap ? ((nb + 7) / 8) * 8 : nb;
-    return g;
-}
-
 void launch_born_stress(hipStream_t st, const Grid &g0, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp) {
-    const Grid g = born_tiled(g0, o);
+    const Grid g = tiled(g0, o, 0);  // the forward kernels' tiling: the background takes the paths of a plain forward pass
     auto k = frame_t ? k_born_stress<true> : k_born_stress<false>;
     hipLaunchKernelGGL(k, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, (z_src << 16) | x_src, src_amp);
 }
 
 void launch_born_velocity(hipStream_t st, const Grid &g0, const KernelOptions &o, const BornArgs &b) {
-    const Grid g = born_tiled(g0, o);
+    const Grid g = tiled(g0, o, 0);  // the forward kernels' tiling: the background takes the paths of a plain forward pass
     hipLaunchKernelGGL(k_born_velocity, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b);
 }
 
@@ -260,14 +227,6 @@ void launch_born_media(hipStream_t st, const Grid &g, const float *Mu_in, const 
                        float *dmedia, size_t n) {
     hipLaunchKernelGGL(k_born_media, dim3((g.nx + 63) / 64, (g.nz + 3) / 4), dim3(64, 4), 0, st, g, Mu_in, dLam_in, dMu_in, dDen_in, md, dmedia,
                        dmedia + n, dmedia + 2 * n, dmedia + 3 * n, dmedia + 4 * n);
-}
-
-void launch_born_residual(hipStream_t st, const BornRes &q, int nSteps) {
-    if (q.nrec <= 0 || q.nblk <= 0) return;
-    const long long n = (long long)q.nrec * nSteps;
-    const long long want = (n + 255) / 256;
-    const int bx = want > 1024 ? 1024 : want < 1 ? 1 : (int)want;
-    hipLaunchKernelGGL(k_born_residual, dim3(bx, q.nblk), dim3(256), 0, st, q, nSteps);
 }
 
 }  // namespace sepfwi

@@ -20,7 +20,8 @@
 // Bytes per cell and step by arrays streamed (interior): stress 5 fields read + 3 written twice over (64) + lam, mu, dlam, dmu, damu (20)
 // = 84 against 2 x 40 of two forward stress updates; velocity 5 + 2 twice over (56) + rho, dba, dbb (12) = 68 against 2 x 32.
 //
-// A translation unit of its own (born.hip): the field kernels are untouched, and a process that never calls sepfwi_born issues
+// A translation unit of its own (born.hip) that shares the device helpers and the launch tiling of the field kernels
+// (kernels_device.hpp, tiled()): the field kernels are untouched, and a process that never calls sepfwi_born issues
 // exactly the launches and allocates exactly the memory it did before.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,15 +47,5 @@ void launch_born_media(hipStream_t st, const Grid &g, const float *Mu_in, const 
 // one time step: stresses (frame_t non-null: the background's boundary frame of this step is saved first), then velocities
 void launch_born_stress(hipStream_t st, const Grid &g, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp);
 void launch_born_velocity(hipStream_t st, const Grid &g, const KernelOptions &o, const BornArgs &b);
-
-// The adjoint source of the Gauss-Newton product: res[it][b nrec + r] = -(w_b dsyn_b[it][r]), time sample 0 forced to 0 -- what the
-// residual kernels (k_residual, k_geo_residual) leave for observed data syn - J v.  Column blocks as geophone.hpp orders them.
-struct BornRes {
-    const float *dsyn[3];
-    float w[3];
-    float *res;
-    int nrec, nblk;
-};
-void launch_born_residual(hipStream_t st, const BornRes &q, int nSteps);
 
 }  // namespace sepfwi

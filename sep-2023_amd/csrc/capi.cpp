@@ -232,13 +232,10 @@ struct DeviceRestore {
 static int common_device(std::initializer_list<const void *> ptrs) {
     int dev = -1;
     for (const void *p : ptrs) {
-        hipPointerAttribute_t attr;
-        if (!p || hipPointerGetAttributes(&attr, p) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
-            throw std::invalid_argument("param maps: every array must be device memory (the host chain stays in torch)");
-        }
-        if (dev >= 0 && attr.device != dev) throw std::invalid_argument("param maps: arrays live on different devices");
-        dev = attr.device;
+        const int d = ptr_device(p);
+        if (d < 0) throw std::invalid_argument("param maps: every array must be device memory (the host chain stays in torch)");
+        if (dev >= 0 && d != dev) throw std::invalid_argument("param maps: arrays live on different devices");
+        dev = d;
     }
     return dev;
 }

@@ -1,5 +1,6 @@
 // exact_adjoint.hip -- the kernels of the exact discrete adjoint (exact_adjoint.hpp).  A translation unit of its own: the field kernels
-// (kernels.hip) are untouched.
+// (kernels.hip) are untouched.  Bundle unpacking, region, strip and Omega tests (kernels_device.hpp) and the launch tiling (tiled(),
+// kernels.hpp) are the field kernels' own.
 //
 // k_exact_a / k_exact_b keep the pairing, the launch shape and the cell mapping of k_bwd_a / k_bwd_b (one wave per 64-column row
 // segment, my_cell) and call the reverse-time bodies (velocity_body<false>, stress_body<false, false>, kernels_bodies.hpp: the same
@@ -17,20 +18,6 @@ namespace sepfwi {
 #include "kernels_bodies.hpp"
 
 namespace {
-
-__device__ __forceinline__ Fields x_fields(float *b, size_t n) { return Fields{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
-__device__ __forceinline__ PmlMem x_mem(float *b, size_t n) { return PmlMem{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n}; }
-__device__ __forceinline__ Media x_media(const float *b, size_t n) { return Media{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n}; }
-__device__ __forceinline__ ImgAcc x_acc(float *b, size_t n) { return ImgAcc{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
-__device__ __forceinline__ PmlCoef x_coef(const float *cz, int nzc, int nx) {
-    const float *cx = cz + 6 * nzc;
-    return PmlCoef{cz, cz + nzc, cz + 2 * nzc, cz + 3 * nzc, cz + 4 * nzc, cz + 5 * nzc, cx, cx + nx, cx + 2 * nx, cx + 3 * nx, cx + 4 * nx, cx + 5 * nx};
-}
-
-// the x strips of the forward kernels: el_stress.cu:61,77 and el_velocity.cu:56,71 (one column narrower on the right)
-__device__ __forceinline__ bool strip_xs(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml - 1; }
-__device__ __forceinline__ bool strip_xv(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml; }
-__device__ __forceinline__ bool on_region(const Grid &g, int z, int x) { return !(z < 2 || z > g.nzc - 3 || x < 2 || x > g.nx - 3); }
 
 // What a forward cell (profile index k, flat index j) hands back to the field it differenced: e / K + a P inside its strip, e outside
 __device__ __forceinline__ float pml_tap(bool in, float e, const float *__restrict__ rK, const float *__restrict__ a, const float *P, int k, size_t j) {
@@ -179,11 +166,11 @@ __device__ __forceinline__ void exact_st_apply(const StIn &q, const Grid &g, con
 }  // namespace
 
 __global__ __launch_bounds__(MAXT) void k_exact_a(Grid g, ExactArgs b, const float *__restrict__ frame_t) {
-    const Fields f = x_fields(b.fields, b.n), adj = x_fields(b.adj, b.n);
-    const PmlMem m = x_mem(b.mem, b.n);
-    const Media md = x_media(b.media, b.n);
-    const ImgAcc acc = x_acc(b.acc, b.n);
-    const PmlCoef pc = x_coef(b.cz, g.nzc, g.nx);
+    const Fields f = fields_of(b.fields, b.n), adj = fields_of(b.adj, b.n);
+    const PmlMem m = mem_of(b.mem, b.n);
+    const Media md = media_of(b.media, b.n);
+    const ImgAcc acc = acc_of(b.acc, b.n);
+    const PmlCoef pc = coef_of(b.cz, b.cz + 6 * g.nzc, g.nzc, g.nx);
     const Cell c = my_cell(g);
     const VtIn q = exact_vt_load(g, c, adj, m, md, pc);  // (in flight together with the reverse-velocity loads)
     velocity_body<false>(g, c, f, m, md, pc, frame_t, -1, -1, 0.0f, nullptr, adj, AccG{acc});
@@ -192,11 +179,11 @@ __global__ __launch_bounds__(MAXT) void k_exact_a(Grid g, ExactArgs b, const flo
 
 __global__ __launch_bounds__(MAXT) void k_exact_b(Grid g, ExactArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp,
                                                   int adjoint_only) {
-    const Fields f = x_fields(b.fields, b.n), adj = x_fields(b.adj, b.n);
-    const PmlMem m = x_mem(b.mem, b.n);
-    const Media md = x_media(b.media, b.n);
-    const ImgAcc acc = x_acc(b.acc, b.n);
-    const PmlCoef pc = x_coef(b.cz, g.nzc, g.nx);
+    const Fields f = fields_of(b.fields, b.n), adj = fields_of(b.adj, b.n);
+    const PmlMem m = mem_of(b.mem, b.n);
+    const Media md = media_of(b.media, b.n);
+    const ImgAcc acc = acc_of(b.acc, b.n);
+    const PmlCoef pc = coef_of(b.cz, b.cz + 6 * g.nzc, g.nzc, g.nx);
     const Cell c = my_cell(g);
     const StIn q = exact_st_load(g, c, adj, m, md, pc);
     if (!adjoint_only)  // launch-uniform
@@ -211,7 +198,7 @@ __global__ void k_exact_finalize(Grid g, Media md, ImgAcc acc, float *__restrict
     if (x >= g.nx || z >= g.nz) return;
     const size_t o = (size_t)z * g.nx + x;
     float gl = 0.0f, gm = 0.0f, gd = 0.0f;
-    if (z >= g.nPml + 1 && z <= g.zmax && x >= g.nPml + 1 && x <= g.xmax) {
+    if (in_omega(g, z, x)) {
         const size_t i = (size_t)z * g.pitch + x, P = (size_t)g.pitch;
         gl = (float)((double)acc.lam[i] * 1e6);
         const double mu = md.mu[i];
@@ -234,48 +221,18 @@ __global__ void k_exact_mask(Grid g, float *__restrict__ v, int k, size_t dense)
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int z = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= g.nx || z >= g.nz) return;
-    if (z >= g.nPml + 1 && z <= g.zmax && x >= g.nPml + 1 && x <= g.xmax) return;
+    if (in_omega(g, z, x)) return;
     for (int a = 0; a < k; a++) v[(size_t)a * dense + (size_t)z * g.nx + x] = 0.0f;
 }
 
-__global__ void k_exact_residual(ExactRes q, int nSteps) {
-    const int b = blockIdx.y;  // gridDim.y = q.nblk
-    const float *__restrict__ w = q.w[b];
-    float *__restrict__ res = q.res + (size_t)b * (size_t)q.nrec;
-    const int nrec = q.nrec;
-    const size_t row = (size_t)q.nblk * (size_t)nrec;
-    const long long n = (long long)nrec * (long long)nSteps;
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
-        const long long it = k / nrec;
-        const int r = (int)(k - it * nrec);
-        res[(size_t)it * row + r] = (it == 0 || !w) ? 0.0f : -w[(size_t)r * (size_t)nSteps + (size_t)it];
-    }
-}
-
-// the tiling of the backward field kernels (kernels.hip tiled(), fly bit 1): the reverse-time bodies take the paths of a gradient call
-static Grid exact_tiled(const Grid &g0, const KernelOptions &o) {
-    Grid g = g0;
-    g.bz = o.bz;
-    g.qr = 1;
-    g.gx = (g.nx + BX - 1) / BX;
-    g.gy = (g.nzc + g.bz - 1) / g.bz;
-    g.xcd_remap = o.xcd_remap;
-    g.rho_fly = (o.rho_fly >> 1) & 1;
-    g.amu_fly = (o.amu_fly >> 1) & 1;
-    g.rk_lazy = o.rk_lazy;
-    const int nb = g.gx * g.gy;
-    g.nblk = g.xcd_remap ? ((nb + 7) / 8) * 8 : nb;
-    return g;
-}
-
 void launch_exact_a(hipStream_t st, const Grid &g0, const KernelOptions &o, const ExactArgs &b, const float *frame_t) {
-    const Grid g = exact_tiled(g0, o);
+    const Grid g = tiled(g0, o, 1);  // the backward kernels' tiling: the reverse-time bodies take the paths of a gradient call
     hipLaunchKernelGGL(k_exact_a, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t);
 }
 
 void launch_exact_b(hipStream_t st, const Grid &g0, const KernelOptions &o, const ExactArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
                     bool adjoint_only) {
-    const Grid g = exact_tiled(g0, o);
+    const Grid g = tiled(g0, o, 1);  // the backward kernels' tiling: the reverse-time bodies take the paths of a gradient call
     const int zx = adjoint_only ? 0 : (z_src << 16) | x_src;
     hipLaunchKernelGGL(k_exact_b, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, zx, src_amp, adjoint_only ? 1 : 0);
 }
@@ -286,14 +243,6 @@ void launch_exact_finalize(hipStream_t st, const Grid &g, Media md, ImgAcc acc, 
 
 void launch_exact_mask(hipStream_t st, const Grid &g, float *v, int k, size_t dense) {
     hipLaunchKernelGGL(k_exact_mask, dim3((g.nx + 63) / 64, (g.nz + 3) / 4), dim3(64, 4), 0, st, g, v, k, dense);
-}
-
-void launch_exact_residual(hipStream_t st, const ExactRes &q, int nSteps) {
-    if (q.nrec <= 0 || q.nblk <= 0) return;
-    const long long n = (long long)q.nrec * nSteps;
-    const long long want = (n + 255) / 256;
-    const int bx = want > 1024 ? 1024 : want < 1 ? 1 : (int)want;
-    hipLaunchKernelGGL(k_exact_residual, dim3(bx, q.nblk), dim3(256), 0, st, q, nSteps);
 }
 
 }  // namespace sepfwi

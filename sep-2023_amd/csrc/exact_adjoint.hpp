@@ -68,13 +68,4 @@ void launch_exact_finalize(hipStream_t st, const Grid &g, Media md, ImgAcc acc, 
 // P_Omega in place on k dense (nz, nx) arrays at stride `dense`
 void launch_exact_mask(hipStream_t st, const Grid &g, float *v, int k, size_t dense);
 
-// The adjoint source of J^T w: res[it][b nrec + r] = -w_b[r][it] (w as sepfwi_born's gathers, [nrec][nSteps]; a null w_b: zeros), time
-// sample 0 forced to 0.  The sign is the residual kernels' (obs - syn): the pass returns -J^T res.
-struct ExactRes {
-    const float *w[3];
-    float *res;
-    int nrec, nblk;
-};
-void launch_exact_residual(hipStream_t st, const ExactRes &q, int nSteps);
-
 }  // namespace sepfwi

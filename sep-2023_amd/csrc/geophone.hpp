@@ -39,4 +39,17 @@ struct GeoResShot {
     int nrec, nblk;
 };
 
+// The same array from something that is not observed data (k_adjoint_source): res[it][b nrec + r] = -(scale_b src_b[r sr + it st]), time
+// sample 0 forced to 0, a null src_b: zeros.  The sign is the residual kernels' (obs - syn).  Two callers:
+//   the Gauss-Newton product   src_b = J v's gather of the block, time-major (sr 1, st nrec), scale_b = w_b: what the residual kernels leave
+//                              for observed data syn - J v
+//   J^T w                      src_b = the caller's w_b as sepfwi_born's gathers, [nrec][nSteps] (sr nSteps, st 1), scale_b = 1
+struct AdjSource {
+    const float *src[3];
+    float scale[3];
+    size_t sr, st;
+    float *res;
+    int nrec, nblk;
+};
+
 }  // namespace sepfwi

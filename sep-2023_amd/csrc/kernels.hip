@@ -130,7 +130,7 @@ int set_kernel_option(const char *name, int value) {
     return -1;
 }
 
-static inline Grid tiled(const Grid &g0, const KernelOptions &o, int fly_bit = -1, bool quiet = false) {
+Grid tiled(const Grid &g0, const KernelOptions &o, int fly_bit, bool quiet) {
     Grid g = g0;
     g.bz = o.bz;
     g.qr = quiet ? o.quiet_rows : 1;

@@ -57,6 +57,11 @@ KernelOptions kernel_options();                       // snapshot of the default
 int get_kernel_option(const char *name);              // -1: unknown
 int set_kernel_option(const char *name, int value);   // 0 or -1
 
+// The launch tiling of every field kernel, the extensions' included (born.hip, exact_adjoint.hip): the grid with this call's tile shape
+// and block order.  fly_bit: which bit of rho_fly / amu_fly applies (0 forward kernels, 1 backward kernels, -1 neither); quiet: the
+// quiet-skipping forward kernels' rows per wave.  A block is BX x g.bz threads, the grid g.nblk blocks.
+Grid tiled(const Grid &g, const KernelOptions &o, int fly_bit = -1, bool quiet = false);
+
 void launch_stress_fwd(hipStream_t st, const Grid &g, const KernelOptions &o, Fields f, PmlMem m, Media md, PmlCoef pc,
                        float *frame_t, int z_src, int x_src, float src_amp, LineRec lr);
 void launch_velocity_fwd(hipStream_t st, const Grid &g, const KernelOptions &o, Fields f, PmlMem m, Media md, PmlCoef pc);
@@ -109,6 +114,7 @@ void launch_inject_gauge_batch(hipStream_t st, const ShotDev *shots, const Gauge
 // and sum r_c^2 per component (sums[comp - 1], double)
 void launch_geo_residual(hipStream_t st, const GeoResShot &q, int nSteps, double *sums);
 void launch_geo_residual_batch(hipStream_t st, const GeoResShot *shots, int nb, int max_nrec, int max_nblk, int nSteps, double *sums);
+void launch_adjoint_source(hipStream_t st, const AdjSource &q, int nSteps);  // the array alone, from J v or the caller's w (geophone.hpp)
 void launch_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, long long n,
                      double *sumsq);
 void launch_transpose(hipStream_t st, const float *in, float *out, int rows, int cols);

@@ -1,6 +1,7 @@
 // kernels_device.hpp -- cell / tile helpers, accumulator and memory-scope policies of the field kernels
-// Part of the ONE translation unit kernels.hip (included there, inside namespace sepfwi): the kernels share their bodies as
-// inline functions, and every kernel structure must compile them identically (bit-identical results).
+// Included inside namespace sepfwi by kernels.hip (ONE translation unit for the field kernels: they share their bodies as inline
+// functions, and every kernel structure must compile them identically -- bit-identical results) and by the extensions
+// that call those bodies from kernels of their own (born.hip, exact_adjoint.hip).
 
 using namespace dev;
 
@@ -69,6 +70,26 @@ __device__ __forceinline__ float ave_mu_at(const Grid &g, const Media &md, size_
     return md.ave_mu[i];
 }
 
+// Bundle unpacking: kernels that take their arrays as a base pointer + stride n (BwdArgs, BornArgs, ExactArgs: <= 80 SGPRs) rebuild the
+// structs the bodies work on.  The C-PML profiles are ONE block: six z profiles of nzc floats at cz, then six x profiles of nx at cx.
+__device__ __forceinline__ Fields fields_of(float *b, size_t n) { return Fields{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
+__device__ __forceinline__ PmlMem mem_of(float *b, size_t n) {
+    return PmlMem{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n};
+}
+__device__ __forceinline__ Media media_of(const float *b, size_t n) { return Media{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n}; }
+__device__ __forceinline__ ImgAcc acc_of(float *b, size_t n) { return ImgAcc{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n}; }
+__device__ __forceinline__ PmlCoef coef_of(const float *cz, const float *cx, int nzc, int nx) {
+    return PmlCoef{cz, cz + nzc, cz + 2 * nzc, cz + 3 * nzc, cz + 4 * nzc, cz + 5 * nzc,
+                   cx, cx + nx,  cx + 2 * nx,  cx + 3 * nx,  cx + 4 * nx,  cx + 5 * nx};
+}
+
+// The update region of the forward bodies (el_stress.cu:52, el_velocity.cu:47) and their x strips: el_stress.cu:61,77 and
+// el_velocity.cu:56,71 (one column narrower on the right).  Omega: the physical interior without its first row and first column
+// (exact_adjoint.hpp).
+__device__ __forceinline__ bool on_region(const Grid &g, int z, int x) { return !(z < 2 || z > g.nzc - 3 || x < 2 || x > g.nx - 3); }
+__device__ __forceinline__ bool strip_xs(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml - 1; }
+__device__ __forceinline__ bool strip_xv(const Grid &g, int x) { return x < g.nPml || x > g.nx - g.nPml; }
+__device__ __forceinline__ bool in_omega(const Grid &g, int z, int x) { return z >= g.nPml + 1 && z <= g.zmax && x >= g.nPml + 1 && x <= g.xmax; }
 
 // Imaging accumulators behind an accessor, so that the same bodies serve the per-step launches (accumulators in HBM, AccG)
 // and the persistent time loop (accumulators of the workgroup's own tile in LDS, AccT below).

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -20,6 +21,11 @@
 #include "pseudo_hessian.hpp"
 
 namespace sepfwi {
+
+// Device that owns `p`, or -1 for host memory.  A pointer on ANOTHER device than the session's (the single-process
+// ngpu > 1 path handing GPU-0 tensors to the session of GPU i) is staged like host memory: the kernels only ever touch
+// memory of their own device, peer access is never assumed.
+int ptr_device(const void *p);
 
 class Session {
   public:
@@ -82,7 +88,33 @@ class Session {
         float src_scale = 0.0f;
         int n_probe = 0;              // HIP-event pairs handed out in the running backward pass
         int ph_every = 0;             // > 0: the call accumulates the pseudo-Hessian on every ph_every-th forward step (armed, calc_id 0 / 1)
+        std::chrono::steady_clock::time_point t_begin;  // begin_call, for total_ms
     };
+    // How run, born and adjoint_exact open and close a call (session_run.cpp).  The entry point holds the lock and has made the refusals
+    // that must leave everything untouched; what differs between them (if_res, with_adj, to_store, ph_every, options it overrides,
+    // last_exact_ / last_batched_, whether the observed store is touched: obs_begin) it sets on the Call it gets back.
+    Call begin_call(hipStream_t ext_stream, int group_size, const int *shot_ids);
+    void check_shot_ids(int group_size, const int *shot_ids) const;
+    void obs_begin(const Call &c);
+    void end_call(const Call &c, bool sync);
+    // closes a timing bracket whose events ev_[a], ev_[a + 1] are recorded on st: waits for the stream, -> the time between them
+    double bracket_ms(int a, hipStream_t st);
+    // the components with a weight (by default the axial strain alone): f(comp, column block of the adjoint-source array), and as a mask
+    // of seismogram components (bit comp)
+    template <class F> void for_active(F f) const {
+        for (int comp = 1; comp <= 3; comp++)
+            if (geo_block_[comp] >= 0) f(comp, geo_block_[comp]);
+    }
+    int active_comps() const { return (geo_block_[1] >= 0 ? 2 : 0) | (geo_block_[2] >= 0 ? 4 : 0) | (geo_block_[3] >= 0 ? 8 : 0); }
+    // The three dense gradients of a finalisation kernel: written in place where the caller's array lives on this device (dev = out),
+    // else into grad_stage_ and copied out on the stream after the launch (host memory, another GPU)
+    struct GradOut {
+        float *out[3], *dev[3];
+    };
+    GradOut grad_out(float *gLambda, float *gMu, float *gDen) const;
+    void copy_staged(const GradOut &o, hipStream_t st);
+    // the call's misfit from the sums on the device, the joint weights applied; parts: also what sepfwi_get_misfit_parts reports
+    void read_misfit(const Call &c, float *misfit, bool parts);
     struct GaugeDev;
     struct InjDev;
     struct ShotCtx {  // one shot of the call in the lane it runs in

@@ -181,10 +181,7 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
         for (int k = 0; k < nb; k++) cond_on_ ? residual_conditioned(c, cx[k]) : residual(cx[k]);
     HIP_OK(hipEventRecord(ev_[1], st));
     fwd_steps_ += (long long)nb * (nSteps - 1);
-    HIP_OK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-    fwd_ms_ += ms;
+    fwd_ms_ += bracket_ms(0, st);
 }
 
 // backward time loop of the sub-batch tab[first .. first + nbb) in backward lanes 0 .. nbb-1, libCUFD.cu:500-675
@@ -242,11 +239,8 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
     batch_join(st, nsb);
     HIP_OK(hipEventRecord(ev_[3], st));
     bwd_steps_ += (long long)nbb * (nSteps - 1);
-    HIP_OK(hipStreamSynchronize(st));
+    bwd_ms_ += bracket_ms(2, st);
     collect_probes(c);
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, ev_[2], ev_[3]));
-    bwd_ms_ += ms;
     if (looped) persist_check_pass(pk_ms_);
 }
 

@@ -6,15 +6,14 @@
 //   forward time loop   k_born_stress / k_born_velocity advance background and scattered field; the existing samplers (k_record,
 //                       k_record_gauge: one-cell, vertical, directional and gauge channels, vx, vz) read the SCATTERED fields
 //   gathers             transposed to [nrec][nSteps] and copied out
-//   product only        the residual buffer is filled with -(w_c dsyn_c) (k_born_residual) where a gradient call's residual kernel
-//                       would put w_c (obs_c - syn_c), and Session::backward runs as in a gradient call: persistent loop or two-launch
-//                       step, injection plans, the background's saved boundary frames
+//   product only        the residual buffer is filled with -(w_c dsyn_c) (k_adjoint_source, geophone.hip) where a gradient call's
+//                       residual kernel would put w_c (obs_c - syn_c), and Session::backward runs as in a gradient call: persistent loop
+//                       or two-launch step, injection plans, the background's saved boundary frames
 // and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
 // state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
 // exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
 // finalisation the exact one on Omega (exact_adjoint.hpp) -- the product P J^T W J P v, symmetric and non-negative.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 
 #include "born.hpp"
@@ -28,48 +27,20 @@
 
 namespace sepfwi {
 
-static bool on_device(const void *p, int dev) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();  // plain host memory is reported as an error on some ROCm versions
-        return false;
-    }
-    return (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) && attr.device == dev;
-}
-
 void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
                    hipStream_t ext_stream, bool exact) {
     std::lock_guard<std::mutex> lock(mu_);
-    const auto t_begin = std::chrono::steady_clock::now();
     const bool want_hv = hv_Lambda != nullptr;
     // refusals first: nothing is touched
     if (want_hv && cond_on_)
         throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit (if_win / filter / if_cross_misfit / if_src_update); "
                                     "the scattered gathers alone are served (hv_* = NULL)");
-    for (int i = 0; i < group_size; i++) {
-        const int id = shot_ids[i];
-        if (id < 0 || id >= (int)survey_.shots.size() || !survey_.shots[id].present)
-            throw std::invalid_argument("shot id " + std::to_string(id) + " is not in the survey file");
-    }
-    HIP_OK(hipSetDevice(gpu_id_));
-    Call c;
-    c.opt = kernel_options();
+    check_shot_ids(group_size, shot_ids);  // (begin_call checks them where run does: after it has touched the statistics)
+    Call c = begin_call(ext_stream, group_size, shot_ids);
     c.opt.quiet_skip = 0;
-    c.st = ext_stream ? ext_stream : own_stream_;
-    if (!ext_stream) order_after_null_stream(c.st);
-    c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files)
-    c.group_size = group_size;
-    c.shot_ids = shot_ids;
+    c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files; the observed store is not touched)
     hipStream_t st = c.st;
-    launches_ = 0;
-    fwd_ms_ = bwd_ms_ = 0.0;
-    probe_us_ = 0.0;
-    probe_calls_ = 0;
-    fwd_steps_ = bwd_steps_ = persist_steps_ = 0;
-    quiet_active_ = quiet_total_ = 0;
-    quiet_last_ = nullptr;
     last_batched_ = false;
     last_exact_ = exact && want_hv;
 
@@ -85,7 +56,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     }
     const float *dv[3] = {dLambda, dMu, dDen};
     for (int k = 0; k < 3; k++) {
-        if (!exact && on_device(dv[k], gpu_id_)) continue;  // (the exact product reads v on Omega only: it masks a copy)
+        if (!exact && ptr_device(dv[k]) == gpu_id_) continue;  // (the exact product reads v on Omega only: it masks a copy)
         if (!born_stage_) {
             HIP_OK(dev_malloc((void **)&born_stage_, 3 * dense * sizeof(float)));
             device_bytes_ += (long long)(3 * dense * sizeof(float));
@@ -97,14 +68,14 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         launch_exact_mask(st, g_, born_stage_, 3, dense);
         launches_++;
     }
-    const float *mu_dense = on_device(Mu, gpu_id_) ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
+    const float *mu_dense = ptr_device(Mu) == gpu_id_ ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
     float *dstate = born_, *dmedia = born_ + 13 * n;
     launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
     launches_++;
 
     // which scattered gathers the call needs: the requested ones, and for the product the components with a weight
     int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
-    if (want_hv) comps |= joint_ ? ((geo_block_[1] >= 0 ? 2 : 0) | (geo_block_[2] >= 0 ? 4 : 0) | (geo_block_[3] >= 0 ? 8 : 0)) : 8;
+    if (want_hv) comps |= active_comps();
     float *out[4] = {nullptr, d_vx, d_vz, d_ett};
     size_t out_off = 0;
     const BornArgs args{state_, dstate, media_, dmedia, pc_.a_z, n};
@@ -138,29 +109,15 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         }
         out_off += cnt;
         if (want_hv && x.nrec > 0) {
-            BornRes q{};
-            q.res = x.res;
-            q.nrec = x.nrec;
-            if (joint_) {
-                q.nblk = geo_ncomp_;
-                for (int comp = 1; comp <= 3; comp++) {
-                    const int b = geo_block_[comp];
-                    if (b < 0) continue;
-                    q.dsyn[b] = syn_of(x, comp);
-                    q.w[b] = par_.weight(comp);
-                }
-            } else {
-                q.nblk = 1;
-                q.dsyn[0] = syn_of(x, 3);
-                q.w[0] = 1.0f;
-            }
-            launch_born_residual(st, q, nSteps);
+            AdjSource q{{}, {}, 1, (size_t)x.nrec, x.res, x.nrec, geo_ncomp_};  // the time-major gathers of J v, by the weights
+            for_active([&](int comp, int b) {
+                q.src[b] = syn_of(x, comp);
+                q.scale[b] = par_.weight(comp);
+            });
+            launch_adjoint_source(st, q, nSteps);
             launches_++;
         }
-        HIP_OK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-        fwd_ms_ += ms;
+        fwd_ms_ += bracket_ms(0, st);  // (the time loop alone: ev_[1] was recorded before the gathers left)
         if (want_hv && exact)
             backward_exact(c, x);
         else if (want_hv)
@@ -170,9 +127,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         write_outputs_exact(c, hv_Lambda, hv_Mu, hv_Den);
     else if (want_hv)
         write_outputs(c, nullptr, hv_Lambda, hv_Mu, hv_Den, nullptr);
-    HIP_OK(hipStreamSynchronize(st));
-    total_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    last_shots_ = group_size;
+    end_call(c, true);
 }
 
 }  // namespace sepfwi

@@ -27,10 +27,7 @@ static std::string shot_file(const Params &p, int comp, int id) {
     return p.data_dir_name + "/Shot_" + kComp[comp] + std::to_string(id) + ".bin";
 }
 
-// Device that owns `p`, or -1 for host memory.  A pointer on ANOTHER device than the session's (the single-process
-// ngpu > 1 path handing GPU-0 tensors to the session of GPU i) is staged like host memory: the kernels only ever touch
-// memory of their own device, peer access is never assumed.
-static int ptr_device(const void *p) {
+int ptr_device(const void *p) {  // (session.hpp)
     if (!p) return -1;
     hipPointerAttribute_t attr;
     hipError_t e = hipPointerGetAttributes(&attr, p);
@@ -127,14 +124,12 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     x.rec = rec_idx_ + rec_off_[x.id];
     x.sens = (sens_ && !x.sh->sens.empty()) ? sens_ + 3 * (size_t)rec_off_[x.id] : nullptr;
     x.stf_s = c.stf_rows.data() + (size_t)is * par_.nSteps;
-    // the observed gathers of the components with a weight (by default the axial strain alone); one with weight 0 is never read
-    for (int comp = 1; comp <= 3; comp++)
-        x.obs_c[comp] = (c.if_res && with_obs && geo_block_[comp] >= 0) ? obs_->acquire(x.id, x.nrec, c.st, comp) : nullptr;
+    // the observed gathers of the components with a weight; one with weight 0 is never read
+    if (c.if_res && with_obs) for_active([&](int comp, int) { x.obs_c[comp] = obs_->acquire(x.id, x.nrec, c.st, comp); });
     x.d_obs = x.obs_c[3];
     x.nres = joint_ ? geo_ncomp_ * x.nrec : x.nrec;
     x.scratch = c.with_adj && !par_.scratch_dir_name.empty();  // libCUFD.cu:732-752
-    const int active = (geo_block_[1] >= 0 ? 2 : 0) | (geo_block_[2] >= 0 ? 4 : 0) | (geo_block_[3] >= 0 ? 8 : 0);  // 8 unless the misfit is a joint one
-    x.comps = (c.if_res || c.to_store) ? (active | (x.scratch ? 1 : 0)) : 15;
+    x.comps = (c.if_res || c.to_store) ? (active_comps() | (x.scratch ? 1 : 0)) : 15;  // (active_comps: 8 unless the misfit is a joint one)
     // horizontal line of consecutive channels inside the computed region?  (channels with a gauge length never are: they are not
     // sampled at their own cells, so the field kernels cannot take them, and quiet_skip stays off for them)
     const Shot &sh = *x.sh;
@@ -241,14 +236,12 @@ GeoResShot Session::geo_res_shot(const ShotCtx &x) const {
     q.res = x.res;
     q.nrec = x.nrec;
     q.nblk = geo_ncomp_;
-    for (int comp = 1; comp <= 3; comp++) {
-        const int b = geo_block_[comp];
-        if (b < 0) continue;
+    for_active([&](int comp, int b) {
         q.obs[b] = x.obs_c[comp];
         q.syn[b] = syn_of(x, comp);
         q.w[b] = par_.weight(comp);
         q.slot[b] = comp - 1;
-    }
+    });
     return q;
 }
 
@@ -355,8 +348,8 @@ void Session::scratch_dumps(const Call &c, const ShotCtx &x) {
 
 void Session::after_forward(Call &c, const ShotCtx &x) {
     if (c.to_store) {  // calc_id 3: the modelled gathers of the components with a weight (by default the axial strain alone) become the
-        for (int comp = 1; comp <= 3; comp++)  // shot's observed data, exactly as sepfwi_set_observed would install the files of calc_id 2
-            if (geo_block_[comp] >= 0) obs_->put_device_gather(x.id, syn_of(x, comp), x.nrec, c.st, comp);
+        // shot's observed data, exactly as sepfwi_set_observed would install the files of calc_id 2
+        for_active([&](int comp, int) { obs_->put_device_gather(x.id, syn_of(x, comp), x.nrec, c.st, comp); });
     } else if (!c.if_res)
         export_gathers(c, x);
     else if (x.scratch)
@@ -445,11 +438,8 @@ void Session::backward(Call &c, const ShotCtx &x) {
         for (int it = par_.nSteps - 2; it >= 0; it--) backward_step(c, x, L, it);
     HIP_OK(hipEventRecord(ev_[3], st));
     bwd_steps_ += (long long)(par_.nSteps - 1);
-    HIP_OK(hipStreamSynchronize(st));
+    bwd_ms_ += bracket_ms(2, st);
     collect_probes(c);
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, ev_[2], ev_[3]));
-    bwd_ms_ += ms;
     if (looped) persist_check_pass(pk_);
 }
 
@@ -490,10 +480,7 @@ void Session::run_streams(Call &c) {
             for (int k = 0; k < np; k++) residual_conditioned(c, ctx[k]);
         HIP_OK(hipEventRecord(ev_[1], st));
         fwd_steps_ += (long long)np * (nSteps - 1);
-        HIP_OK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-        fwd_ms_ += ms;
+        fwd_ms_ += bracket_ms(0, st);
         obs_->release_all();  // the residuals are formed: the group's observed gathers may leave HBM again
 
         for (int k = 0; k < np; k++) after_forward(c, ctx[k]);
@@ -557,13 +544,10 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
         HIP_OK(hipMemcpy(grad_stf, h_gstf.data(), h_gstf.size() * sizeof(float), hipMemcpyDefault));
     }
     if (c.with_adj) {
-        const bool devL = ptr_device(grad_Lambda) == gpu_id_, devM = ptr_device(grad_Mu) == gpu_id_, devD = ptr_device(grad_Den) == gpu_id_;
-        float *oL = devL ? grad_Lambda : grad_stage_, *oM = devM ? grad_Mu : grad_stage_ + dense, *oD = devD ? grad_Den : grad_stage_ + 2 * dense;
-        launch_finalize_gradients(st, g_, md_, acc_, oL, oM, oD);
+        const GradOut o = grad_out(grad_Lambda, grad_Mu, grad_Den);
+        launch_finalize_gradients(st, g_, md_, acc_, o.dev[0], o.dev[1], o.dev[2]);
         launches_++;
-        if (!devL) HIP_OK(hipMemcpyAsync(grad_Lambda, oL, dense * sizeof(float), hipMemcpyDefault, st));
-        if (!devM) HIP_OK(hipMemcpyAsync(grad_Mu, oM, dense * sizeof(float), hipMemcpyDefault, st));
-        if (!devD) HIP_OK(hipMemcpyAsync(grad_Den, oD, dense * sizeof(float), hipMemcpyDefault, st));
+        copy_staged(o, st);
     }
     if (c.ph_every > 0) {  // the sets summed in lane order, the constants of pseudo_hessian.hpp
         PhSets sets{};
@@ -575,43 +559,58 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
         launches_++;
         ph_valid_ = true;
     }
-    if (c.if_res && misfit) {
-        double sumsq = 0.0;
-        HIP_OK(hipMemcpyAsync(&sumsq, scal_, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c.if_res && misfit) read_misfit(c, misfit, true);
+}
+
+Session::GradOut Session::grad_out(float *gLambda, float *gMu, float *gDen) const {
+    const size_t dense = (size_t)par_.nz * (size_t)par_.nx;
+    GradOut o{{gLambda, gMu, gDen}, {}};
+    for (int k = 0; k < 3; k++) o.dev[k] = ptr_device(o.out[k]) == gpu_id_ ? o.out[k] : grad_stage_ + (size_t)k * dense;
+    return o;
+}
+
+void Session::copy_staged(const GradOut &o, hipStream_t st) {
+    const size_t dense = (size_t)par_.nz * (size_t)par_.nx;
+    for (int k = 0; k < 3; k++)
+        if (o.dev[k] != o.out[k]) HIP_OK(hipMemcpyAsync(o.out[k], o.dev[k], dense * sizeof(float), hipMemcpyDefault, st));
+}
+
+void Session::read_misfit(const Call &c, float *misfit, bool parts) {
+    hipStream_t st = c.st;
+    double sumsq = 0.0, s[3] = {0.0, 0.0, 0.0};  // sum r_c^2 per component (vx, vz, ett)
+    HIP_OK(hipMemcpyAsync(&sumsq, scal_, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    s[2] = sumsq;
+    if (joint_) {  // -> the weighted misfit and the unweighted parts
+        HIP_OK(hipMemcpyAsync(s, geo_sums_, sizeof(s), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        parts_[0] = parts_[1] = 0.0;
-        parts_[2] = 0.5 * sumsq;
-        if (joint_) {  // sum r_c^2 per component (vx, vz, ett) -> the weighted misfit and the unweighted parts
-            double s[3] = {0.0, 0.0, 0.0};
-            HIP_OK(hipMemcpyAsync(s, geo_sums_, sizeof(s), hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            sumsq = 0.0;
-            for (int comp = 1; comp <= 3; comp++) {
-                parts_[comp - 1] = 0.5 * s[comp - 1];
-                sumsq += (double)par_.weight(comp) * s[comp - 1];
-            }
-        }
-        const float mf = (float)(0.5 * sumsq);  // libCUFD.cu:776
-        HIP_OK(hipMemcpy(misfit, &mf, sizeof(float), hipMemcpyDefault));
+        sumsq = 0.0;
+        for (int comp = 1; comp <= 3; comp++) sumsq += (double)par_.weight(comp) * s[comp - 1];
+    }
+    if (parts)
+        for (int k = 0; k < 3; k++) parts_[k] = 0.5 * s[k];
+    const float mf = (float)(0.5 * sumsq);  // libCUFD.cu:776
+    HIP_OK(hipMemcpy(misfit, &mf, sizeof(float), hipMemcpyDefault));
+}
+
+// ---- how every call opens and closes (run below, born: session_born.cpp, adjoint_exact: session_exact.cpp) ----------------------
+void Session::check_shot_ids(int group_size, const int *shot_ids) const {
+    for (int i = 0; i < group_size; i++) {
+        const int id = shot_ids[i];
+        if (id < 0 || id >= (int)survey_.shots.size() || !survey_.shots[id].present)
+            throw std::invalid_argument("shot id " + std::to_string(id) + " is not in the survey file");
     }
 }
 
-// ---- the cufd call -------------------------------------------------------------------------------------------------------
-void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_Den, float *grad_stf, const float *Lambda, const float *Mu,
-                  const float *Den, const float *stf, int calc_id, int group_size, const int *shot_ids, hipStream_t ext_stream, bool async) {
-    std::lock_guard<std::mutex> lock(mu_);
-    const auto t_begin = std::chrono::steady_clock::now();
-    HIP_OK(hipSetDevice(gpu_id_));
+Session::Call Session::begin_call(hipStream_t ext_stream, int group_size, const int *shot_ids) {
     Call c;
+    c.t_begin = std::chrono::steady_clock::now();
+    HIP_OK(hipSetDevice(gpu_id_));
     c.opt = kernel_options();  // ONE snapshot for the whole call
     c.st = ext_stream ? ext_stream : own_stream_;
     if (!ext_stream) order_after_null_stream(c.st);
-    c.if_res = (calc_id == 0 || calc_id == 1);  // Parameter.cpp:125-137
-    c.with_adj = (calc_id == 1);
-    c.to_store = (calc_id == SEPFWI_CALC_OBSERVE_TO_STORE);  // observe, but into the HBM store instead of the four files
     c.group_size = group_size;
     c.shot_ids = shot_ids;
-    c.ph_every = c.if_res ? ph_every_ : 0;  // calc_id 2 and 3 never accumulate
     last_exact_ = false;
     launches_ = 0;
     fwd_ms_ = bwd_ms_ = 0.0;
@@ -620,15 +619,40 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
     fwd_steps_ = bwd_steps_ = persist_steps_ = 0;
     quiet_active_ = quiet_total_ = 0;
     quiet_last_ = nullptr;
-    for (int i = 0; i < group_size; i++) {
-        const int id = shot_ids[i];
-        if (id < 0 || id >= (int)survey_.shots.size() || !survey_.shots[id].present)
-            throw std::invalid_argument("shot id " + std::to_string(id) + " is not in the survey file");
-    }
-    // HBM budget of the observed-data store: parameter key "obs_cache_mb", else the option of the same name (0: unlimited)
+    check_shot_ids(group_size, shot_ids);
+    return c;
+}
+
+// HBM budget of the observed-data store: parameter key "obs_cache_mb", else the option of the same name (0: unlimited)
+void Session::obs_begin(const Call &c) {
     const long long mb = par_.obs_cache_mb > 0 ? par_.obs_cache_mb : c.opt.obs_cache_mb;
     obs_->set_budget_bytes(mb * 1000000LL);
     obs_->release_all();
+}
+
+void Session::end_call(const Call &c, bool sync) {
+    if (sync) HIP_OK(hipStreamSynchronize(c.st));
+    total_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c.t_begin).count();
+    last_shots_ = c.group_size;
+}
+
+double Session::bracket_ms(int a, hipStream_t st) {
+    HIP_OK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, ev_[a], ev_[a + 1]));
+    return ms;
+}
+
+// ---- the cufd call -------------------------------------------------------------------------------------------------------
+void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_Den, float *grad_stf, const float *Lambda, const float *Mu,
+                  const float *Den, const float *stf, int calc_id, int group_size, const int *shot_ids, hipStream_t ext_stream, bool async) {
+    std::lock_guard<std::mutex> lock(mu_);
+    Call c = begin_call(ext_stream, group_size, shot_ids);
+    c.if_res = (calc_id == 0 || calc_id == 1);  // Parameter.cpp:125-137
+    c.with_adj = (calc_id == 1);
+    c.to_store = (calc_id == SEPFWI_CALC_OBSERVE_TO_STORE);  // observe, but into the HBM store instead of the four files
+    c.ph_every = c.if_res ? ph_every_ : 0;  // calc_id 2 and 3 never accumulate
+    obs_begin(c);
 
     prepare_media(c, Lambda, Mu, Den);
     prepare_buffers(c, stf);
@@ -636,8 +660,7 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
     const size_t gather_bytes = (size_t)std::max(1, survey_.max_nrec) * par_.nSteps * sizeof(float) * (size_t)geo_ncomp_;
     if (c.if_res && obs_->budget_bytes() == 0)  // observed data of every shot of the call resident before the time loops start
         for (int is = 0; is < group_size; is++)
-            for (int comp = 1; comp <= 3; comp++)
-                if (geo_block_[comp] >= 0) (void)obs_->acquire(shot_ids[is], survey_.shots[shot_ids[is]].nrec, c.st, comp);
+            for_active([&](int comp, int) { (void)obs_->acquire(shot_ids[is], survey_.shots[shot_ids[is]].nrec, c.st, comp); });
     obs_->release_all();
 
     // Batch sizes from the Infinity-Cache budget: a forward batch keeps 5 fields per shot + 5 media arrays resident, a backward
@@ -676,8 +699,7 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
         for (unsigned int w : bits) quiet_active_ += __builtin_popcount(w);
         quiet_total_ = (long long)(g_.nzc - 4) * ((g_.nx + 63) / 64);
     }
-    total_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    last_shots_ = group_size;
+    end_call(c, false);  // (synchronised above, or left running: async)
     last_calc_ = calc_id;
 }
 

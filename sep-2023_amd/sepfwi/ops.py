@@ -73,6 +73,75 @@ def _para_dims(para_fname):
     return _DIMS_CACHE[key]
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _checked(Lambda, Mu, Den, Stf, shot_ids, para_fname, what, v=(), need_dims=True):
+    """What _cufd, _born and _adjoint_exact do to their arguments before anything is allocated: float32 contiguous tensors, one
+    shape and one device for the model (and the perturbation v), Stf and Shot_ids against the parameter file.
+    -> (Lambda, Mu, Den, Stf, v, ids, nSteps); nSteps is None where the parameter file cannot be read and need_dims is false (the
+    library then reports the file)."""
+    Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
+    v = [_f32c(t, n) for t, n in zip(v, ("dLambda", "dMu", "dDen"))]
+    names = "Lambda, Mu, Den, dLambda, dMu, dDen" if v else "Lambda, Mu, Den"
+    if Lambda.dim() != 2 or any(t.shape != Lambda.shape for t in [Mu, Den] + v):
+        raise ValueError(names + " must be 2-D tensors of one shape (nz_pad, nx_pad)")
+    if any(t.device != Lambda.device for t in [Mu, Den] + v):
+        raise ValueError(names + " must live on one device")
+    ids = np.ascontiguousarray(np.asarray(shot_ids.cpu() if torch.is_tensor(shot_ids) else shot_ids, dtype=np.int32)).reshape(-1)
+    dims = _para_dims(para_fname)
+    if dims is None:
+        if need_dims:
+            raise ValueError("cannot read nz, nx, nSteps from the parameter file %r" % (para_fname,))
+        return Lambda, Mu, Den, Stf, v, ids, None
+    nz, nx, nSteps = dims
+    if tuple(Lambda.shape) != (nz, nx):
+        raise ValueError("%s %s but the parameter file says (nz, nx) = (%d, %d)" % (what, tuple(Lambda.shape), nz, nx))
+    if Stf.dim() != 2 or Stf.shape[1] != nSteps:
+        raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
+        raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
+    return Lambda, Mu, Den, Stf, v, ids, nSteps
+
+
+def _gdev(Lambda, gpu_id):
+    """Where a call's outputs are allocated, so that the session writes them in place: on ITS GPU when the model lives on a GPU (also
+    another one: single-process ngpu > 1), on the host for the reference's CPU tensors."""
+    return torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+
+
+def _stream_or_sync(Lambda, Stf, gpu_id, sync_current=False):
+    """The stream argument of a call, after everything it reads has been queued: torch's current stream when the model lives on the
+    session's GPU, else NULL (the legacy default stream: the library orders itself behind it) after the model's device has finished."""
+    stream = None
+    if Lambda.is_cuda and Lambda.device.index == gpu_id:
+        cs = torch.cuda.current_stream(Lambda.device).cuda_stream
+        stream = C.c_void_p(cs) if cs else None
+        if sync_current:
+            torch.cuda.current_stream(Lambda.device).synchronize()
+    elif Lambda.is_cuda:
+        torch.cuda.synchronize(Lambda.device)   # the model was produced on another GPU: finished before it is staged
+    if Stf.is_cuda:
+        torch.cuda.synchronize(Stf.device)      # read with a blocking copy inside the library
+    return stream
+
+
+def _nrec_per_shot(para_fname, ids):
+    """Channels of every shot of ids, from the survey file the parameter file names."""
+    import json
+    with open(para_fname) as fp:
+        survey_fname = json.loads(fp.readline())["survey_fname"]
+    with open(survey_fname) as fp:
+        survey = json.loads(fp.readline())
+    nrec = []
+    for i in ids:
+        if "shot%d" % int(i) not in survey:
+            raise ValueError("shot id %d is not in the survey file" % int(i))
+        nrec.append(len(survey["shot%d" % int(i)]["z_rec"]))
+    return nrec
+
+
 class _FwiOps:
     """Module object: fwi_ops.forward / backward / obscalc."""
 
@@ -89,26 +158,10 @@ class _FwiOps:
             raise ValueError("pseudo_hessian must be >= 0 (0: off, k: accumulate on every k-th forward step)")
         if k > 0 and calc_id not in (0, 1):
             raise ValueError("pseudo_hessian needs a misfit or gradient call")
-        Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
-        if Lambda.dim() != 2 or Lambda.shape != Mu.shape or Lambda.shape != Den.shape:
-            raise ValueError("Lambda, Mu, Den must be 2-D tensors of one shape (nz_pad, nx_pad)")
-        if Mu.device != Lambda.device or Den.device != Lambda.device:
-            raise ValueError("Lambda, Mu, Den must live on one device")
-        ids = np.ascontiguousarray(np.asarray(shot_ids.cpu() if torch.is_tensor(shot_ids) else shot_ids, dtype=np.int32))
-        dims = _para_dims(para_fname)
-        if dims is not None:
-            nz, nx, nSteps = dims
-            if tuple(Lambda.shape) != (nz, nx):
-                raise ValueError("Lambda/Mu/Den are %s but the parameter file says (nz, nx) = (%d, %d)" % (tuple(Lambda.shape), nz, nx))
-            if Stf.dim() != 2 or Stf.shape[1] != nSteps:
-                raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
-            if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
-                raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
+        Lambda, Mu, Den, Stf, _, ids, _ = _checked(Lambda, Mu, Den, Stf, shot_ids, para_fname, "Lambda/Mu/Den are", need_dims=False)
         gpu_id = int(gpu_id)
         dev = out_device if out_device is not None else Lambda.device
-        # gradients are allocated where the session writes them in place: on ITS GPU when the model lives on a GPU
-        # (also another one: single-process ngpu > 1), on the host for the reference's CPU tensors
-        gdev = torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+        gdev = _gdev(Lambda, gpu_id)
         # the loss lives where the model lives (the reference: CPU tensors throughout, torch::zeros(1)); calc_id 1 below makes it the
         # last element of the gradient buffer
         misfit = torch.zeros(1, dtype=torch.float32, device=gdev if calc_id == 0 else "cpu")
@@ -121,27 +174,19 @@ class _FwiOps:
             gL, gM, gD = (fused[k * n:(k + 1) * n].view(Lambda.shape) for k in range(3))
             misfit = fused[3 * n:3 * n + 1]
             gS = torch.zeros((int(ids.size), Stf.shape[1]), dtype=torch.float32)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = None        # NULL = the legacy default stream: the library orders itself behind it
-        if Lambda.is_cuda and Lambda.device.index == gpu_id:
-            cs = torch.cuda.current_stream(Lambda.device).cuda_stream
-            stream = C.c_void_p(cs) if cs else None
-        elif Lambda.is_cuda:
-            torch.cuda.synchronize(Lambda.device)   # the model was produced on another GPU: finished before it is staged
-        if Stf.is_cuda:
-            torch.cuda.synchronize(Stf.device)      # read with a blocking copy inside the library
+        stream = _stream_or_sync(Lambda, Stf, gpu_id)
         fn = str(para_fname).encode()
         H = None
         with (_ph_lock(para_fname, gpu_id) if k > 0 else contextlib.nullcontext()):
             if k > 0:
                 _native.check(L.sepfwi_pseudo_hessian_arm(fn, gpu_id, k))
             try:
-                rc = L.sepfwi_cufd_stream(ptr(misfit), ptr(gL), ptr(gM), ptr(gD), ptr(gS), ptr(Lambda), ptr(Mu), ptr(Den),
-                                          ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
+                rc = L.sepfwi_cufd_stream(_ptr(misfit), _ptr(gL), _ptr(gM), _ptr(gD), _ptr(gS), _ptr(Lambda), _ptr(Mu), _ptr(Den),
+                                          _ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
                 _native.check(rc)
                 if k > 0:   # ONE buffer [hLambda | hMu | hDen], the unit of the all-reduce under torch.distributed
                     H = torch.empty((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
-                    _native.check(L.sepfwi_get_pseudo_hessian(fn, gpu_id, ptr(H[0]), ptr(H[1]), ptr(H[2])))
+                    _native.check(L.sepfwi_get_pseudo_hessian(fn, gpu_id, _ptr(H[0]), _ptr(H[1]), _ptr(H[2])))
             finally:
                 if k > 0:
                     L.sepfwi_pseudo_hessian_arm(fn, gpu_id, 0)   # disarm, also on error
@@ -269,51 +314,19 @@ class _FwiOps:
             if c not in comp_id:
                 raise ValueError("components must be among 'ett', 'vx', 'vz', got %r" % (c,))
         L = _native.lib()
-        Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
-        dLambda, dMu, dDen = _f32c(dLambda, "dLambda"), _f32c(dMu, "dMu"), _f32c(dDen, "dDen")
-        if Lambda.dim() != 2 or any(t.shape != Lambda.shape for t in (Mu, Den, dLambda, dMu, dDen)):
-            raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must be 2-D tensors of one shape (nz_pad, nx_pad)")
-        if any(t.device != Lambda.device for t in (Mu, Den, dLambda, dMu, dDen)):
-            raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must live on one device")
-        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
-        dims = _para_dims(para_fname)
-        if dims is None:
-            raise ValueError("cannot read nz, nx, nSteps from the parameter file %r" % (para_fname,))
-        nz, nx, nSteps = dims
-        if tuple(Lambda.shape) != (nz, nx):
-            raise ValueError("the model and its perturbation are %s but the parameter file says (nz, nx) = (%d, %d)" % (tuple(Lambda.shape), nz, nx))
-        if Stf.dim() != 2 or Stf.shape[1] != nSteps:
-            raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
-        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
-            raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
-        import json
-        with open(para_fname) as fp:
-            survey_fname = json.loads(fp.readline())["survey_fname"]
-        with open(survey_fname) as fp:
-            survey = json.loads(fp.readline())
-        nrec = []
-        for i in ids:
-            if "shot%d" % int(i) not in survey:
-                raise ValueError("shot id %d is not in the survey file" % int(i))
-            nrec.append(len(survey["shot%d" % int(i)]["z_rec"]))
+        Lambda, Mu, Den, Stf, (dLambda, dMu, dDen), ids, nSteps = _checked(Lambda, Mu, Den, Stf, Shot_ids, para_fname, "the model and its perturbation are",
+                                                                         v=(dLambda, dMu, dDen))
+        nrec = _nrec_per_shot(para_fname, ids)
         gpu_id = self._device_for(Lambda, 0)
-        gdev = torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+        gdev = _gdev(Lambda, gpu_id)
         total = int(sum(nrec)) * nSteps
         bufs = [None, None, None]
         for c in components:
             bufs[comp_id[c]] = torch.zeros(max(total, 1), dtype=torch.float32, device=gdev)
         hv = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev) if with_hv else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = None
-        if Lambda.is_cuda and Lambda.device.index == gpu_id:
-            cs = torch.cuda.current_stream(Lambda.device).cuda_stream
-            stream = C.c_void_p(cs) if cs else None
-        elif Lambda.is_cuda:
-            torch.cuda.synchronize(Lambda.device)
-        if Stf.is_cuda:
-            torch.cuda.synchronize(Stf.device)
-        rc = L.sepfwi_born(ptr(bufs[2]), ptr(bufs[0]), ptr(bufs[1]), ptr(hv[0]) if with_hv else None, ptr(hv[1]) if with_hv else None,
-                           ptr(hv[2]) if with_hv else None, ptr(Lambda), ptr(Mu), ptr(Den), ptr(dLambda), ptr(dMu), ptr(dDen), ptr(Stf), gpu_id,
+        stream = _stream_or_sync(Lambda, Stf, gpu_id)
+        rc = L.sepfwi_born(_ptr(bufs[2]), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(hv[0]) if with_hv else None, _ptr(hv[1]) if with_hv else None,
+                           _ptr(hv[2]) if with_hv else None, _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(dLambda), _ptr(dMu), _ptr(dDen), _ptr(Stf), gpu_id,
                            int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
         _native.check(rc)
         out, off = [], 0
@@ -351,49 +364,21 @@ class _FwiOps:
         if _dist.active():
             raise ValueError("the exact adjoint does not run under torch.distributed: the multi-rank path is not implemented for it")
         L = _native.lib()
-        Lambda, Mu, Den, Stf = _f32c(Lambda, "Lambda"), _f32c(Mu, "Mu"), _f32c(Den, "Den"), _f32c(Stf, "Stf")
-        if Lambda.dim() != 2 or Mu.shape != Lambda.shape or Den.shape != Lambda.shape:
-            raise ValueError("Lambda, Mu, Den must be 2-D tensors of one shape (nz_pad, nx_pad)")
-        if Mu.device != Lambda.device or Den.device != Lambda.device:
-            raise ValueError("Lambda, Mu, Den must live on one device")
-        if v is not None:
-            v = [_f32c(t, n) for t, n in zip(v, ("dLambda", "dMu", "dDen"))]
-            if any(t.shape != Lambda.shape for t in v):
-                raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must be 2-D tensors of one shape (nz_pad, nx_pad)")
-            if any(t.device != Lambda.device for t in v):
-                raise ValueError("Lambda, Mu, Den, dLambda, dMu, dDen must live on one device")
-        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
-        dims = _para_dims(para_fname)
-        if dims is None:
-            raise ValueError("cannot read nz, nx, nSteps from the parameter file %r" % (para_fname,))
-        nz, nx, nSteps = dims
-        if tuple(Lambda.shape) != (nz, nx):
-            raise ValueError("the model is %s but the parameter file says (nz, nx) = (%d, %d)" % (tuple(Lambda.shape), nz, nx))
-        if Stf.dim() != 2 or Stf.shape[1] != nSteps:
-            raise ValueError("Stf must be (nSrc, nSteps = %d), got %s" % (nSteps, tuple(Stf.shape)))
-        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= Stf.shape[0]):
-            raise ValueError("Shot_ids must index rows of Stf (0..%d), got %d..%d" % (Stf.shape[0] - 1, int(ids.min()), int(ids.max())))
+        Lambda, Mu, Den, Stf, v, ids, nSteps = _checked(Lambda, Mu, Den, Stf, Shot_ids, para_fname, "the model is", v=v or ())
         gpu_id = self._device_for(Lambda, 0)
-        gdev = torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
+        gdev = _gdev(Lambda, gpu_id)
         wbuf = {"ett": None, "vx": None, "vz": None}
         if w is not None:
-            import json
-            with open(para_fname) as fp:
-                survey_fname = json.loads(fp.readline())["survey_fname"]
-            with open(survey_fname) as fp:
-                survey = json.loads(fp.readline())
             w = list(w)
             if len(w) != ids.size:
                 raise ValueError("w must hold one dict of gathers per shot of Shot_ids")
             comps = sorted({c for d in w for c in d})
             if not comps or any(c not in wbuf for c in comps):
                 raise ValueError("w: components must be among 'ett', 'vx', 'vz', and at least one must be given")
+            nrec_of = _nrec_per_shot(para_fname, ids)
             for c in comps:
                 rows = []
-                for i, d in zip(ids, w):
-                    if "shot%d" % int(i) not in survey:
-                        raise ValueError("shot id %d is not in the survey file" % int(i))
-                    nrec = len(survey["shot%d" % int(i)]["z_rec"])
+                for i, d, nrec in zip(ids, w, nrec_of):
                     t = d.get(c)
                     t = torch.zeros((nrec, nSteps), dtype=torch.float32) if t is None else _f32c(torch.as_tensor(t), "w[%r]" % c)
                     if tuple(t.shape) != (nrec, nSteps):
@@ -402,19 +387,10 @@ class _FwiOps:
                 wbuf[c] = torch.cat(rows) if rows else torch.zeros(1, dtype=torch.float32, device=gdev)
         g = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
         misfit = torch.zeros(1, dtype=torch.float32)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = None
-        if Lambda.is_cuda and Lambda.device.index == gpu_id:
-            cs = torch.cuda.current_stream(Lambda.device).cuda_stream
-            stream = C.c_void_p(cs) if cs else None
-            torch.cuda.current_stream(Lambda.device).synchronize()   # (w was assembled on this stream; the library may run on its own)
-        elif Lambda.is_cuda:
-            torch.cuda.synchronize(Lambda.device)
-        if Stf.is_cuda:
-            torch.cuda.synchronize(Stf.device)
-        vp = [ptr(t) for t in v] if v is not None else [None, None, None]
-        rc = L.sepfwi_adjoint_exact(ptr(misfit), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(wbuf["ett"]), ptr(wbuf["vx"]), ptr(wbuf["vz"]), *vp,
-                                    ptr(Lambda), ptr(Mu), ptr(Den), ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data),
+        stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=True)   # (w was assembled on this stream; the library may run on its own)
+        vp = [_ptr(t) for t in v] if v else [None, None, None]
+        rc = L.sepfwi_adjoint_exact(_ptr(misfit), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(wbuf["ett"]), _ptr(wbuf["vx"]), _ptr(wbuf["vz"]), *vp,
+                                    _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data),
                                     str(para_fname).encode(), stream)
         _native.check(rc)
         g = g.to(Lambda.device)
