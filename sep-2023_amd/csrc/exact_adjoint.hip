@@ -42,28 +42,32 @@ __device__ __forceinline__ VtIn exact_vt_load(const Grid &g, const Cell &c, cons
     q.sxz = a.sxz[i];
     auto fz = [&](size_t j) { return md.byc_a[j] * a.vz[j] * g.dt; };
     auto fx = [&](size_t j) { return md.byc_b[j] * a.vx[j] * g.dt; };
+    // Only the cells of R are rows of V: a tap outside R hands nothing back.  The adjoint velocities are NOT zero there -- the injection of
+    // a channel on the first row or column of R (or, directional, on the last) writes one cell outside it, where nothing ever clears it.
+    auto row_on = [&](int zt) { return zt >= 2 && zt <= g.nzc - 3; };
+    auto col_on = [&](int xt) { return xt >= 2 && xt <= g.nx - 3; };
     float e1[4], e3[4], e2[4], e4[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         {   // z taps z-2 .. z+1 (D-z) of fz: the forward cell differenced szz with D+z, memory dszz_dz, half profiles
             const int zt = z + k - 2;
             const size_t j = i + (size_t)((long long)(k - 2) * P);
-            e1[k] = pml_tap(in_pml_z(g, zt), fz(j), pc.rK_zh, pc.a_zh, m.dszz_dz, zt, j);
+            e1[k] = row_on(zt) ? pml_tap(in_pml_z(g, zt), fz(j), pc.rK_zh, pc.a_zh, m.dszz_dz, zt, j) : 0.0f;
         }
         {   // z taps z-1 .. z+2 (D+z) of fx: sxz differenced with D-z, memory dsxz_dz
             const int zt = z + k - 1;
             const size_t j = i + (size_t)((long long)(k - 1) * P);
-            e3[k] = pml_tap(in_pml_z(g, zt), fx(j), pc.rK_z, pc.a_z, m.dsxz_dz, zt, j);
+            e3[k] = row_on(zt) ? pml_tap(in_pml_z(g, zt), fx(j), pc.rK_z, pc.a_z, m.dsxz_dz, zt, j) : 0.0f;
         }
         {   // x taps x-1 .. x+2 (D+x) of fz: sxz differenced with D-x, memory dsxz_dx
             const int xt = x + k - 1;
             const size_t j = i + k - 1;
-            e2[k] = pml_tap(strip_xv(g, xt), fz(j), pc.rK_x, pc.a_x, m.dsxz_dx, xt, j);
+            e2[k] = col_on(xt) ? pml_tap(strip_xv(g, xt), fz(j), pc.rK_x, pc.a_x, m.dsxz_dx, xt, j) : 0.0f;
         }
         {   // x taps x-2 .. x+1 (D-x) of fx: sxx differenced with D+x, memory dsxx_dx, half profiles
             const int xt = x + k - 2;
             const size_t j = i + k - 2;
-            e4[k] = pml_tap(strip_xv(g, xt), fx(j), pc.rK_xh, pc.a_xh, m.dsxx_dx, xt, j);
+            e4[k] = col_on(xt) ? pml_tap(strip_xv(g, xt), fx(j), pc.rK_xh, pc.a_xh, m.dsxx_dx, xt, j) : 0.0f;
         }
     }
     q.uz = -dminus(e1[0], e1[1], e1[2], e1[3], g.rdz);

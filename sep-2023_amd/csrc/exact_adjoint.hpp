@@ -9,7 +9,9 @@
 //   S:  szz += dt ((lam + 2 mu) D~-z vz + lam D~-x vx)   sxx += dt (lam D~-z vz + (lam + 2 mu) D~-x vx)   sxz += dt amu (D~+z vx + D~+x vz)
 //   V:  vz  += dt ba (D~+z szz + D~-x sxz)               vx  += dt bb (D~-z sxz + D~+x sxx)
 // and column it + 1 of the gathers samples the velocities after V of step it.  Transposed time loop, it = nSteps-2 ... 0, with
-// (D-)^T = -D+ and (D+)^T = -D- wherever the differenced quantity is 0 outside R (the adjoint fields are only ever written on R):
+// (D-)^T = -D+ and (D+)^T = -D- wherever the differenced quantity is 0 outside R.  The kernels write the adjoint fields on R only, so the
+// adjoint stresses are; the adjoint velocities are not: the injection of a channel on the first row or column of R (a directional one:
+// on the last, too) adds to one cell outside R, which the forward pass samples as an exact zero.  V^T therefore takes its taps on R only:
 //   before the loop    v_ += R^T w[nSteps-1]                                  (the column the reference never injects)
 //   k_exact_a (it)     rho image (reverse-time velocity body, unchanged), then V^T:
 //                        fz = dt ba v_z, fx = dt bb v_x  at the TAP;  E(tap) = in strip ? f / K(tap) + a(tap) Q(tap) : f

@@ -6,7 +6,9 @@ Tolerance, none new: the suite's gradient tolerance 1e-3, relative, plus 3 x the
 oracle builds (plain and nvfma), the yardstick of tests/test_gpu_born_fuzz.py for float32 rounding:
     |got - ref| <= 1e-3 |ref| + 3 |alt - ref|
 Every dot product is accumulated in float64 on the host.  Each comparison prints its deviation before it asserts
-(profiles/r11_exact_adjoint.txt holds the figures measured on the MI355X).
+(profiles/r11_exact_adjoint.txt holds the figures measured on the MI355X).  The problems here are hand-picked;
+tests/test_gpu_exact_adjoint_fuzz.py holds the same identities on seeded random geometries (channels inside the absorbing layers, ragged
+channel counts with the caller's w, w in host memory, joint and gauge misfits).
 
 Every test fails on the parent (the entry point is missing); 1, 3, 4 and 6 would also fail on the parent's adjoint if it were merely
 re-exported: v^T H v / |W^1/2 J v|^2 reads 0.9923 and 0.9844 there on the fixed problems, residual column nSteps-1 is dropped."""
