@@ -233,7 +233,7 @@ typedef struct sepfwi_stats {
     long long fwd_steps;      /* forward time steps executed                                  */
     long long bwd_steps;      /* backward time steps executed                                 */
     long long launches;       /* kernel launches issued                                       */
-    long long device_bytes;   /* device memory held by the session                            */
+    long long device_bytes;   /* device memory held by the session: every block, at its allocated size, while it is held */
     int n_c;                  /* computed cells per step (nz-nPad)*(nx)  [PML included]       */
     double probe_kernel_us;   /* option "probe">0: mean duration of the sampled k_bwd_b launches (HIP events) */
     long long probe_calls;    /* number of sampled launches                                     */
@@ -298,6 +298,13 @@ int sepfwi_param_backward(int kind, int nz, int nx, int nPml, int nPad, const fl
  * property checked at the full 2000 x 1000 x 4000 size, where the CPU oracle cannot go.
  */
 int sepfwi_debug_field(const char *para_fname, int gpu_id, int lane, int which, float *out);
+
+/*
+ * Test hook: the bytes of device memory and of pinned host memory that the library holds in this process right now, over all its
+ * sessions and devices (every allocation of the library goes through one seam that counts them).  After sepfwi_release_all both are
+ * back where they were before the first session.
+ */
+int sepfwi_debug_live_bytes(long long *device, long long *pinned);
 
 #ifdef __cplusplus
 }

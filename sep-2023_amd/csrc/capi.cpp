@@ -220,6 +220,14 @@ int sepfwi_debug_field(const char *para_fname, int gpu_id, int lane, int which, 
     });
 }
 
+int sepfwi_debug_live_bytes(long long *device, long long *pinned) {
+    return guarded([&] {
+        if (!device || !pinned) throw std::invalid_argument("bad arguments");
+        *device = live_bytes().device.load();
+        *pinned = live_bytes().pinned.load();
+    });
+}
+
 // The calling thread's current HIP device, restored on scope exit: the parameterisation maps run on the autograd thread, whose
 // current device torch's own guards read back with hipGetDevice.
 struct DeviceRestore {

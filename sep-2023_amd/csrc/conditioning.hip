@@ -217,9 +217,9 @@ void fft_ok(hipfftResult r, const char *what) {
 
 Conditioner::Conditioner(int nt, int max_nrec) : nt_(nt), cap_(max_nrec) {
     const size_t npad = 2 * (size_t)nt, nf = (size_t)nt + 1;
-    if (dev_malloc((void **)&pad_, npad * cap_ * sizeof(float)) != hipSuccess || dev_malloc((void **)&spec_, nf * cap_ * sizeof(hipfftComplex)) != hipSuccess ||
-        dev_malloc((void **)&norm_, 3 * (size_t)cap_ * sizeof(float)) != hipSuccess)
-        throw std::runtime_error("conditioning: out of device memory");
+    pad_ = DevBuf<float>(&bytes_, npad * cap_);
+    spec_ = DevBuf<float2>(&bytes_, nf * cap_);
+    norm_ = DevBuf<float>(&bytes_, 3 * (size_t)cap_);
 }
 
 Conditioner::~Conditioner() {
@@ -227,18 +227,6 @@ Conditioner::~Conditioner() {
         (void)fft().Destroy((hipfftHandle)kv.second.fwd);
         (void)fft().Destroy((hipfftHandle)kv.second.inv);
     }
-    (void)hipFree(pad_);
-    (void)hipFree(spec_);
-    (void)hipFree(norm_);
-    if (pad2_) (void)hipFree(pad2_);
-    if (spec2_) (void)hipFree(spec2_);
-    if (coef_) (void)hipFree(coef_);
-}
-
-long long Conditioner::device_bytes() const {
-    const size_t pad = 2 * (size_t)nt_ * cap_ * sizeof(float), spec = ((size_t)nt_ + 1) * cap_ * sizeof(hipfftComplex);
-    const size_t src = pad2_ ? pad + spec + ((size_t)nt_ + 1) * sizeof(hipfftComplex) : 0;  // source-update buffers, allocated on first use
-    return (long long)(pad + spec + 3 * (size_t)cap_ * sizeof(float) + src);
 }
 
 void Conditioner::window(hipStream_t st, float *data, int nrec, float dt, const float *win_start, const float *win_end,
@@ -255,13 +243,13 @@ void Conditioner::bandpass(hipStream_t st, float *data, int nrec, float dt, cons
     const int npad = 2 * nt_, nf = nt_ + 1;
     Plans &pl = plans_for(nrec, st);
     hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
-    hipLaunchKernelGGL(k_embed, dim3((npad + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_);
-    fft_ok(fft().ExecR2C(f, pad_, (hipfftComplex *)spec_), "hipfftExecR2C");
+    hipLaunchKernelGGL(k_embed, dim3((npad + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_.get());
+    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
     const float df = (float)(1.0 / (double)dt / (double)npad);
     hipLaunchKernelGGL(k_bp_filter, dim3((nf + 255) / 256, nrec), dim3(256), 0, st, nf, nrec, df, filt[0], filt[1], filt[2], filt[3],
-                       (hipfftComplex *)spec_);
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_, pad_), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_, 1.0f / (float)npad);
+                       (hipfftComplex *)spec_.get());
+    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
+    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_.get(), 1.0f / (float)npad);
 }
 
 Conditioner::Plans &Conditioner::plans_for(int nrec, hipStream_t st) {
@@ -285,17 +273,16 @@ Conditioner::Plans &Conditioner::plans_for(int nrec, hipStream_t st) {
 }
 
 void Conditioner::ensure_source_buffers(hipStream_t st) {
-    if (pad2_) return;
+    if (pad2_.get()) return;
     const size_t npad = 2 * (size_t)nt_, nf = (size_t)nt_ + 1;
-    if (dev_malloc((void **)&pad2_, npad * cap_ * sizeof(float)) != hipSuccess ||
-        dev_malloc((void **)&spec2_, nf * cap_ * sizeof(hipfftComplex)) != hipSuccess ||
-        dev_malloc((void **)&coef_, nf * sizeof(hipfftComplex)) != hipSuccess)
-        throw std::runtime_error("conditioning: out of device memory (source update)");
+    pad2_ = DevBuf<float>(&bytes_, npad * cap_);
+    spec2_ = DevBuf<float2>(&bytes_, nf * cap_);
+    coef_ = DevBuf<float2>(&bytes_, nf);
     // ON THE CALLER'S STREAM: a plain hipMemset runs on the null stream without blocking the host, the session's streams are
     // non-blocking ones that do not wait for it, and it could land after k_matching_coef has written the coefficients -- zeroing
     // the first shot's source update or (later still) only its adjoint step: misfit right, gradient short of one shot.  That is
     // what a six-process fuzz sweep of round 3 caught once in about 15 000 draws (seed 11558: gradient 45 % off, 1.5e-6 when repeated).
-    if (hipMemsetAsync(coef_, 0, nf * sizeof(hipfftComplex), st) != hipSuccess) throw std::runtime_error("conditioning: hipMemsetAsync failed");
+    if (hipMemsetAsync(coef_.get(), 0, nf * sizeof(hipfftComplex), st) != hipSuccess) throw std::runtime_error("conditioning: hipMemsetAsync failed");
 }
 
 // source_update, utilities.cu:1170-1281
@@ -307,17 +294,17 @@ void Conditioner::source_update(hipStream_t st, const float *obs, float *syn, in
     Plans &pl = plans_for(nrec, st);
     hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
     const dim3 gpad((npad + 255) / 256, nrec), blk(256);
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, obs, pad_);
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)syn, pad2_);
+    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, obs, pad_.get());
+    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)syn, pad2_.get());
     // cuda_window over the PADDED length, ratio 0.01 (utilities.cu:1199-1202)
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_);
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad2_);
-    fft_ok(fft().ExecR2C(f, pad_, (hipfftComplex *)spec_), "hipfftExecR2C");
-    fft_ok(fft().ExecR2C(f, pad2_, (hipfftComplex *)spec2_), "hipfftExecR2C");
-    hipLaunchKernelGGL(k_matching_coef, dim3(nf), blk, 0, st, nf, nrec, (const hipfftComplex *)spec_, (const hipfftComplex *)spec2_, (hipfftComplex *)coef_);
-    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec2_, (const hipfftComplex *)coef_, 0);
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec2_, pad2_), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, syn, pad2_, 1.0f / (float)npad);
+    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_.get());
+    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad2_.get());
+    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
+    fft_ok(fft().ExecR2C(f, pad2_.get(), (hipfftComplex *)spec2_.get()), "hipfftExecR2C");
+    hipLaunchKernelGGL(k_matching_coef, dim3(nf), blk, 0, st, nf, nrec, (const hipfftComplex *)spec_.get(), (const hipfftComplex *)spec2_.get(), (hipfftComplex *)coef_.get());
+    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec2_.get(), (const hipfftComplex *)coef_.get(), 0);
+    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec2_.get(), pad2_.get()), "hipfftExecC2R");
+    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, syn, pad2_.get(), 1.0f / (float)npad);
 }
 
 void Conditioner::source_update_adj(hipStream_t st, float *res, int nrec, float dt) {
@@ -328,12 +315,12 @@ void Conditioner::source_update_adj(hipStream_t st, float *res, int nrec, float 
     Plans &pl = plans_for(nrec, st);
     hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
     const dim3 gpad((npad + 255) / 256, nrec), blk(256);
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)res, pad_);
-    fft_ok(fft().ExecR2C(f, pad_, (hipfftComplex *)spec_), "hipfftExecR2C");
-    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec_, (const hipfftComplex *)coef_, 1);
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_, pad_), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_);
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, res, pad_, 1.0f / (float)npad);
+    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)res, pad_.get());
+    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
+    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec_.get(), (const hipfftComplex *)coef_.get(), 1);
+    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
+    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_.get());
+    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, res, pad_.get(), 1.0f / (float)npad);
 }
 
 void Conditioner::l2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc) {
@@ -345,7 +332,7 @@ void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *
                                  float src_weight, double *acc) {
     if (nrec <= 0) return;
     if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
-    float *n_oo = norm_, *n_ss = norm_ + cap_, *n_os = norm_ + 2 * (size_t)cap_;
+    float *n_oo = norm_.get(), *n_ss = n_oo + cap_, *n_os = n_oo + 2 * (size_t)cap_;
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, obs, n_oo);
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, syn, syn, n_ss);
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, syn, n_os);

@@ -5,6 +5,8 @@
 
 #include <map>
 
+#include "device_alloc.hpp"
+
 namespace sepfwi {
 
 class Conditioner {
@@ -35,10 +37,10 @@ class Conditioner {
     // end taper of the padded length, crop.  (Conscious fix of source_update_adj, utilities.cu:1283-1325: oracle/oracle.py.)
     void source_update_adj(hipStream_t st, float *res, int nrec, float dt);
     // the second padded gather / spectrum and the coefficients of the source update, allocated (and the coefficients zeroed on `st`)
-    // once; the session calls it up-front when the parameter file sets if_src_update, so that device_bytes() is complete and no
-    // shot pays an allocation inside its time loop
+    // once; the session calls it up-front when the parameter file sets if_src_update, so that no shot pays an allocation inside
+    // its time loop
     void ensure_source_buffers(hipStream_t st);
-    long long device_bytes() const;
+    long long device_bytes() const { return bytes_; }  // what the buffers below hold
 
   private:
     struct Plans {
@@ -46,9 +48,10 @@ class Conditioner {
     };
     Plans &plans_for(int nrec, hipStream_t st);
     int nt_, cap_;
-    float *pad_ = nullptr, *norm_ = nullptr, *pad2_ = nullptr;
-    void *spec_ = nullptr;  // hipfftComplex [cap][nt + 1]
-    void *spec2_ = nullptr, *coef_ = nullptr;  // second padded gather / spectrum and the nt + 1 matching-filter coefficients (source update)
+    long long bytes_ = 0;
+    DevBuf<float> pad_, norm_, pad2_;
+    DevBuf<float2> spec_;          // hipfftComplex [cap][nt + 1]
+    DevBuf<float2> spec2_, coef_;  // second padded gather / spectrum and the nt + 1 matching-filter coefficients (source update)
     std::map<int, Plans> plans_;  // by number of traces
 };
 

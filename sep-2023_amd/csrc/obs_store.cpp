@@ -21,32 +21,13 @@ int ObservedStore::max_group(size_t bytes, int want) const {
     return (int)std::max(1LL, std::min<long long>(fit, want));
 }
 
-void ObservedStore::free_entry(Entry &e) {
-    if (e.d) {
-        (void)hipFree(e.d);
-        dev_bytes_ -= (long long)e.bytes;
-        e.d = nullptr;
-    }
-    if (e.h) {
-        (void)hipHostFree(e.h);
-        host_bytes_ -= (long long)e.bytes;
-        e.h = nullptr;
-    }
-}
-
 void ObservedStore::clear() {
     (void)hipSetDevice(h_.gpu_id);
-    for (auto &kv : obs_) free_entry(kv.second);
     obs_.clear();
 }
 
 void ObservedStore::forget(int shot_id) {
-    for (int comp = 1; comp <= 3; comp++) {
-        auto it = obs_.find(key(shot_id, comp));
-        if (it == obs_.end()) continue;
-        free_entry(it->second);
-        obs_.erase(it);
-    }
+    for (int comp = 1; comp <= 3; comp++) obs_.erase(key(shot_id, comp));
 }
 
 void ObservedStore::release_all() {
@@ -57,14 +38,11 @@ void ObservedStore::release_all() {
 void ObservedStore::to_host_tier(Entry &e, hipStream_t st) {
     if (!e.d) return;
     if (!e.h) {
-        HIP_OK(hipHostMalloc((void **)&e.h, e.bytes, hipHostMallocDefault));
-        host_bytes_ += (long long)e.bytes;
-        HIP_OK(hipMemcpyAsync(e.h, e.d, e.bytes, hipMemcpyDeviceToHost, st));
+        e.h = PinBuf<float>(&host_bytes_, e.bytes / sizeof(float));
+        HIP_OK(hipMemcpyAsync(e.h.get(), e.d.get(), e.bytes, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
     }
-    (void)hipFree(e.d);
-    e.d = nullptr;
-    dev_bytes_ -= (long long)e.bytes;
+    e.d.reset();
     evictions_++;
 }
 
@@ -85,26 +63,23 @@ void ObservedStore::make_room(size_t bytes, hipStream_t st) {
     }
 }
 
+// the entry's HBM block, if it has none: room under the budget first
+void ObservedStore::make_resident(Entry &e, hipStream_t st) {
+    if (e.d) return;
+    make_room(e.bytes, st);
+    e.d = DevBuf<float>(&dev_bytes_, e.bytes / sizeof(float));
+}
+
 void ObservedStore::materialise(Entry &e, hipStream_t st) {
     if (e.d || e.bytes == 0) return;
-    make_room(e.bytes, st);
-    HIP_OK(dev_malloc((void **)&e.d, e.bytes));
-    dev_bytes_ += (long long)e.bytes;
-    HIP_OK(hipMemcpyAsync(e.d, e.h, e.bytes, hipMemcpyHostToDevice, st));  // pinned source: asynchronous, ordered on the call's stream
+    make_resident(e, st);
+    HIP_OK(hipMemcpyAsync(e.d.get(), e.h.get(), e.bytes, hipMemcpyHostToDevice, st));  // pinned source: asynchronous, ordered on the call's stream
     uploads_++;
 }
 
 void ObservedStore::reset(Entry &e, size_t bytes) {
-    if (e.h) {  // bytes are about to change: the host copy is stale
-        (void)hipHostFree(e.h);
-        host_bytes_ -= (long long)e.bytes;
-        e.h = nullptr;
-    }
-    if (e.d && e.bytes != bytes) {
-        (void)hipFree(e.d);
-        dev_bytes_ -= (long long)e.bytes;
-        e.d = nullptr;
-    }
+    e.h.reset();  // bytes are about to change: the host copy is stale
+    if (e.bytes != bytes) e.d.reset();
     e.bytes = bytes;
 }
 
@@ -112,9 +87,9 @@ void ObservedStore::reset(Entry &e, size_t bytes) {
 void ObservedStore::fill_from_xpose(Entry &e, int shot_id, int nrec, hipStream_t st) {
     if (h_.cond_on) {  // kept conditioned and trace-major
         h_.condition(st, h_.xpose, shot_id, nrec);
-        HIP_OK(hipMemcpyAsync(e.d, h_.xpose, e.bytes, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(e.d.get(), h_.xpose, e.bytes, hipMemcpyDeviceToDevice, st));
     } else {
-        launch_transpose(st, h_.xpose, e.d, nrec, h_.par->nSteps);  // [rec][it] -> [it][rec]
+        launch_transpose(st, h_.xpose, e.d.get(), nrec, h_.par->nSteps);  // [rec][it] -> [it][rec]
     }
     HIP_OK(hipStreamSynchronize(st));
 }
@@ -128,11 +103,7 @@ void ObservedStore::put(int shot_id, const float *ett, int nrec, hipStream_t st,
     e.tick = ++clock_;
     if (nrec <= 0) return;
     e.held = true;  // not a candidate while room is made for it
-    if (!e.d) {
-        make_room(want, st);
-        HIP_OK(dev_malloc((void **)&e.d, want));
-        dev_bytes_ += (long long)want;
-    }
+    make_resident(e, st);
     HIP_OK(hipMemcpyAsync(h_.xpose, ett, want, hipMemcpyDefault, st));
     fill_from_xpose(e, shot_id, nrec, st);
     e.held = was_held;
@@ -147,17 +118,13 @@ void ObservedStore::put_device_gather(int shot_id, const float *syn_time_major, 
     e.tick = ++clock_;
     if (nrec <= 0) return;
     e.held = true;
-    if (!e.d) {
-        make_room(want, st);
-        HIP_OK(dev_malloc((void **)&e.d, want));
-        dev_bytes_ += (long long)want;
-    }
+    make_resident(e, st);
     if (h_.cond_on) {  // the device gather is time-major; the conditioned store is trace-major
         launch_transpose(st, syn_time_major, h_.xpose, h_.par->nSteps, nrec);  // [it][rec] -> [rec][it]
         h_.condition(st, h_.xpose, shot_id, nrec);
-        HIP_OK(hipMemcpyAsync(e.d, h_.xpose, want, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(e.d.get(), h_.xpose, want, hipMemcpyDeviceToDevice, st));
     } else {
-        HIP_OK(hipMemcpyAsync(e.d, syn_time_major, want, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(e.d.get(), syn_time_major, want, hipMemcpyDeviceToDevice, st));
     }
     HIP_OK(hipStreamSynchronize(st));
     e.held = was_held;
@@ -192,7 +159,7 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st, int c
             e.held = true;
             e.tick = ++clock_;
             materialise(e, st);
-            return e.d;
+            return e.d.get();
         }
     }
     // where the gather lives: the survey's packed file when the parameter file names one and it holds this shot, else the
@@ -221,7 +188,7 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st, int c
         e.held = true;
         e.tick = ++clock_;
         materialise(e, st);
-        return e.d;
+        return e.d.get();
     }
     FILE *fp = fopen(fn.c_str(), "rb");
     if (!fp) throw IoError("cannot read observed data '" + fn + "'");
@@ -237,14 +204,10 @@ const float *ObservedStore::acquire(int shot_id, int nrec, hipStream_t st, int c
     e.from_memory = false;
     e.size = (long long)sb.st_size;
     e.mtime_ns = stamp;
-    if (!e.d) {
-        make_room(want, st);
-        HIP_OK(dev_malloc((void **)&e.d, want));
-        dev_bytes_ += (long long)want;
-    }
+    make_resident(e, st);
     HIP_OK(hipMemcpyAsync(h_.xpose, h_.h_io, want, hipMemcpyHostToDevice, st));
     fill_from_xpose(e, shot_id, nrec, st);
-    return e.d;
+    return e.d.get();
 }
 
 }  // namespace sepfwi

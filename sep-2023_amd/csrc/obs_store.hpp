@@ -6,7 +6,7 @@
 // (time-major [it][rec]; with data conditioning: conditioned, [rec][it]) and kept.  Two tiers:
 //   HBM          every gather, as long as the budget allows (default: no budget, everything stays in HBM);
 //   pinned host  with a budget ("obs_cache_mb"), the least recently used gathers that are not in use move to page-locked host
-//                memory (hipHostMalloc) and come back by one asynchronous copy on the call's stream when a shot needs them.
+//                memory and come back by one asynchronous copy on the call's stream when a shot needs them.
 // The bytes that travel are the device-layout bytes, so a gather that went to the host tier and back is bit-identical.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include <string>
 
 #include "config.hpp"
+#include "device_alloc.hpp"
 #include "host_checks.hpp"
 
 namespace sepfwi {
@@ -58,8 +59,8 @@ class ObservedStore {
 
   private:
     struct Entry {
-        float *d = nullptr;  // HBM copy (device layout) or null
-        float *h = nullptr;  // pinned host copy of the same bytes or null
+        DevBuf<float> d;  // HBM copy (device layout) or empty; booked in dev_bytes_
+        PinBuf<float> h;  // pinned host copy of the same bytes or empty; booked in host_bytes_
         size_t bytes = 0;
         long long size = 0, mtime_ns = 0;  // stamp of the file behind it
         bool from_memory = false;          // no file behind it
@@ -69,9 +70,9 @@ class ObservedStore {
     size_t want_bytes(int nrec) const { return (size_t)nrec * (size_t)h_.par->nSteps * sizeof(float); }
     void make_room(size_t bytes, hipStream_t st);
     void to_host_tier(Entry &e, hipStream_t st);
+    void make_resident(Entry &e, hipStream_t st);
     void materialise(Entry &e, hipStream_t st);
     void reset(Entry &e, size_t bytes);  // fresh device buffer of `bytes`, host copy dropped
-    void free_entry(Entry &e);
     void fill_from_xpose(Entry &e, int shot_id, int nrec, hipStream_t st);  // xpose ([rec][it]) -> device layout
     long long pack_offset(int shot_id, int nrec);
 

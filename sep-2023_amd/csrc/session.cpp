@@ -30,11 +30,8 @@ namespace sepfwi {
 
 template <class T>
 T *Session::dalloc(size_t n) {
-    void *p = nullptr;
-    HIP_OK(dev_malloc(&p, n * sizeof(T)));
-    allocs_.push_back(p);
-    device_bytes_ += (long long)(n * sizeof(T));
-    return (T *)p;
+    allocs_.push_back(dev<char>(n * sizeof(T)));
+    return (T *)allocs_.back().get();
 }
 
 // grid geometry of the session from the parameter file (Parameter.cpp:41-178, Boundary.cu:17-27)
@@ -174,10 +171,10 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     joint_ = par.joint();
     geo_ncomp_ = geo_blocks(par, geo_block_);
     HIP_OK(hipSetDevice(gpu_id_));
-    HIP_OK(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&ev_order_, hipEventDisableTiming));
-    for (auto &e : ev_) HIP_OK(hipEventCreate(&e));
-    for (auto &e : probe_ev_) HIP_OK(hipEventCreate(&e));
+    own_stream_ = make_stream();
+    ev_order_ = make_event(false);
+    for (auto &e : ev_) e = make_event(true);
+    for (auto &e : probe_ev_) e = make_event(true);
 
     init_grid();
     alloc_arrays();
@@ -193,17 +190,16 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     if (cond_on_) {
         xpose2_ = dalloc<float>(dlen);
         cond_.reset(new Conditioner(par.nSteps, std::max(1, survey_.max_nrec)));
-        if (par.if_src_update) cond_->ensure_source_buffers(own_stream_);  // now, so that sepfwi_stats.device_bytes counts them
-        device_bytes_ += cond_->device_bytes();
+        if (par.if_src_update) cond_->ensure_source_buffers(own_stream_);  // now: no shot pays an allocation inside its time loop
     }
-    HIP_OK(hipHostMalloc((void **)&h_io_, dlen * sizeof(float), hipHostMallocDefault));
+    h_io_.ensure(dlen);
     {
         ObservedStore::Host h;
         h.gpu_id = gpu_id_;
         h.par = &par_;
         h.survey = &survey_;
         h.xpose = xpose_;
-        h.h_io = h_io_;
+        h.h_io = h_io_.get();
         h.cond_on = cond_on_;
         h.condition = [this](hipStream_t st, float *gather, int shot_id, int nrec) { condition_gather(st, gather, shot_id, nrec); };
         obs_.reset(new ObservedStore(h));
@@ -213,61 +209,16 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     HIP_OK(hipDeviceSynchronize());
 }
 
+// The members free what they own (session.hpp: buffers before events and streams); what is left to do is to let the device finish.
 Session::~Session() {
     (void)hipSetDevice(gpu_id_);
     (void)hipDeviceSynchronize();
-    for (float *p : {ba_.state, ba_.syn, ba_.res, ba_.frame, ba_.bwd})
-        if (p) (void)hipFree(p);
-    if (d_shots_) (void)hipFree(d_shots_);
-    if (d_shots_bwd_) (void)hipFree(d_shots_bwd_);
-    if (d_geo_res_) (void)hipFree(d_geo_res_);
-    if (d_stf_) (void)hipFree(d_stf_);
-    for (XLane &L : xl_) {
-        if (L.state) (void)hipFree(L.state);
-        if (L.frame) (void)hipFree(L.frame);
-        if (L.syn) (void)hipFree(L.syn);
-        if (L.res) (void)hipFree(L.res);
-        if (L.stream) (void)hipStreamDestroy(L.stream);
-        if (L.join) (void)hipEventDestroy(L.join);
-    }
-    obs_.reset();
-    for (Persist *k : {&pk_, &pk_ms_}) {
-        if (k->d_seg) (void)hipFree(k->d_seg);
-        if (k->d_hdr) (void)hipFree(k->d_hdr);
-        if (k->d_sync) (void)hipFree(k->d_sync);
-        if (k->d_qnbr) (void)hipFree(k->d_qnbr);
-        if (k->d_stf) (void)hipFree(k->d_stf);
-        if (k->h_err) (void)hipHostFree(k->h_err);
-    }
-    for (auto &kv : inj_) {
-        InjDev &d = kv.second;
-        (void)hipFree(d.lookup);
-        (void)hipFree(d.segs);
-        (void)hipFree(d.tgt_start);
-        (void)hipFree(d.ent_rec);
-        (void)hipFree(d.ent_w);
-        if (d.tgt_cell) (void)hipFree(d.tgt_cell);
-        if (d.tgt_field) (void)hipFree(d.tgt_field);
-        if (d.tile_has) (void)hipFree(d.tile_has);
-        if (d.d_args) (void)hipFree(d.d_args);
-    }
-    for (auto &kv : gauge_)
-        for (void *p : {(void *)kv.second.start, (void *)kv.second.cell, (void *)kv.second.field, (void *)kv.second.w}) (void)hipFree(p);
-    if (d_gauge_) (void)hipFree(d_gauge_);
-    if (inj_val_) (void)hipFree(inj_val_);
-    for (float *p : ph_set_)
-        if (p) (void)hipFree(p);
-    if (ph_out_) (void)hipFree(ph_out_);
-    if (born_) (void)hipFree(born_);
-    if (born_stage_) (void)hipFree(born_stage_);
-    for (void *p : allocs_) (void)hipFree(p);
-    if (frame_) (void)hipFree(frame_);
-    if (stf_grad_) (void)hipFree(stf_grad_);
-    if (h_io_) (void)hipHostFree(h_io_);
-    for (auto &e : ev_) (void)hipEventDestroy(e);
-    for (auto &e : probe_ev_) (void)hipEventDestroy(e);
-    if (ev_order_) (void)hipEventDestroy(ev_order_);
-    if (own_stream_) (void)hipStreamDestroy(own_stream_);
+}
+
+void Session::ensure_lane_stream(XLane &L) {
+    if (L.stream) return;
+    L.stream = make_stream();
+    L.join = make_event(false);
 }
 
 // Extra lanes of forward state (fields, memory variables, boundary frames, seismograms, residual) and their streams.
@@ -275,21 +226,13 @@ void Session::ensure_lanes(int n_lanes, bool with_frames) {
     const size_t n = cells_;
     for (int k = 1; k < n_lanes && k < kMaxLanes; k++) {
         XLane &L = xl_[k];
-        if (!L.stream) {
-            HIP_OK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&L.join, hipEventDisableTiming));
-        }
+        ensure_lane_stream(L);
         if (!L.state) {
-            HIP_OK(dev_malloc((void **)&L.state, 13 * n * sizeof(float)));
-            HIP_OK(dev_malloc((void **)&L.syn, 4 * data_len_ * sizeof(float)));
-            HIP_OK(dev_malloc((void **)&L.res, res_len_ * sizeof(float)));
-            device_bytes_ += (long long)((13 * n + 4 * data_len_ + res_len_) * sizeof(float));
+            L.state = dev<float>(13 * n);
+            L.syn = dev<float>(4 * data_len_);
+            L.res = dev<float>(res_len_);
         }
-        if (with_frames && !L.frame) {
-            const size_t fb = (size_t)par_.nSteps * 5 * (size_t)g_.frame_len * sizeof(float);
-            HIP_OK(dev_malloc((void **)&L.frame, fb));
-            device_bytes_ += (long long)fb;
-        }
+        if (with_frames && !L.frame) L.frame = dev<float>((size_t)par_.nSteps * 5 * (size_t)g_.frame_len);
     }
 }
 
@@ -300,46 +243,24 @@ void Session::ensure_lanes(int n_lanes, bool with_frames) {
 // nothing from one call to the next.
 void Session::ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots) {
     const size_t n = cells_;
-    auto regrow = [&](float *&arena, int &cap, int want, size_t per_lane) {
-        if (want <= cap) return;
-        if (arena) {
-            (void)hipFree(arena);
-            device_bytes_ -= (long long)((size_t)cap * per_lane * sizeof(float));
-        }
-        arena = nullptr;
-        cap = 0;
-        HIP_OK(dev_malloc((void **)&arena, (size_t)want * per_lane * sizeof(float)));
-        cap = want;
-        device_bytes_ += (long long)((size_t)want * per_lane * sizeof(float));
-    };
     const size_t frame_lane = (size_t)par_.nSteps * 5 * (size_t)g_.frame_len;
-    regrow(ba_.state, ba_.n_state, n_fwd, 13 * n);
-    regrow(ba_.syn, ba_.n_syn, n_fwd, 4 * data_len_);
-    regrow(ba_.res, ba_.n_res, n_fwd, res_len_);
-    if (with_frames) regrow(ba_.frame, ba_.n_frame, n_fwd, frame_lane);
-    regrow(ba_.bwd, ba_.n_bwd, n_bwd, 18 * n);
-    bl_.assign((size_t)std::max(ba_.n_state, 1), BLane{});
-    for (int k = 0; k < ba_.n_state; k++) {
+    ba_.state.ensure((size_t)n_fwd * 13 * n);
+    ba_.syn.ensure((size_t)n_fwd * 4 * data_len_);
+    ba_.res.ensure((size_t)n_fwd * res_len_);
+    if (with_frames) ba_.frame.ensure((size_t)n_fwd * frame_lane);
+    ba_.bwd.ensure((size_t)n_bwd * 18 * n);
+    const size_t n_state = ba_.state.size() / (13 * n), n_frame = ba_.frame.size() / frame_lane, n_bwd_have = ba_.bwd.size() / (18 * n);
+    bl_.assign(std::max<size_t>(n_state, 1), BLane{});
+    for (size_t k = 0; k < n_state; k++) {
         BLane &L = bl_[k];
-        L.state = ba_.state + (size_t)k * 13 * n;
-        L.syn = ba_.syn + (size_t)k * 4 * data_len_;
-        L.res = ba_.res + (size_t)k * res_len_;
-        L.frame = k < ba_.n_frame ? ba_.frame + (size_t)k * frame_lane : nullptr;
-        L.bwd = k < ba_.n_bwd ? ba_.bwd + (size_t)k * 18 * n : nullptr;
+        L.state = ba_.state.get() + k * 13 * n;
+        L.syn = ba_.syn.get() + k * 4 * data_len_;
+        L.res = ba_.res.get() + k * res_len_;
+        L.frame = k < n_frame ? ba_.frame.get() + k * frame_lane : nullptr;
+        L.bwd = k < n_bwd_have ? ba_.bwd.get() + k * 18 * n : nullptr;
     }
-    if (n_shots > shots_cap_) {
-        if (d_shots_) (void)hipFree(d_shots_);
-        d_shots_ = nullptr;
-        HIP_OK(dev_malloc((void **)&d_shots_, (size_t)n_shots * sizeof(ShotDev)));
-        shots_cap_ = n_shots;
-    }
-    const size_t need = (size_t)n_shots * par_.nSteps;
-    if (need > d_stf_len_) {
-        if (d_stf_) (void)hipFree(d_stf_);
-        d_stf_ = nullptr;
-        HIP_OK(dev_malloc((void **)&d_stf_, need * sizeof(float)));
-        d_stf_len_ = need;
-    }
+    d_shots_.ensure((size_t)n_shots);
+    d_stf_.ensure((size_t)n_shots * par_.nSteps);
 }
 
 void Session::drop_observed() {
@@ -387,7 +308,7 @@ void Session::copy_field(int lane, int which, float *out) {
     const float *base = nullptr;
     if (which >= 10) {  // the scattered fields of the last Born call
         if (!born_) throw std::invalid_argument("debug_field: no Born call yet");
-        base = born_ + (size_t)(which - 10) * cells_;
+        base = born_.get() + (size_t)(which - 10) * cells_;
     } else if (which >= 5) {  // adjoint fields: one set per session (stream mode) or per backward lane (batched mode)
         if (last_batched_) {
             if (lane < 0 || lane >= (int)bl_.size() || !bl_[lane].bwd) throw std::invalid_argument("debug_field: no such backward lane");
@@ -400,7 +321,7 @@ void Session::copy_field(int lane, int which, float *out) {
         base = bl_[lane].state + (size_t)which * cells_;
     } else {
         if (lane < 0 || lane >= kMaxLanes || (lane > 0 && !xl_[lane].state)) throw std::invalid_argument("debug_field: no such lane");
-        base = (lane ? xl_[lane].state : state_) + (size_t)which * cells_;
+        base = (lane ? xl_[lane].state.get() : state_) + (size_t)which * cells_;
     }
     HIP_OK(hipMemcpy2D(out, (size_t)g_.nx * sizeof(float), base, (size_t)g_.pitch * sizeof(float), (size_t)g_.nx * sizeof(float),
                        (size_t)g_.nzc, hipMemcpyDefault));
@@ -414,7 +335,7 @@ void Session::stats(sepfwi_stats *out) const {
     out->fwd_steps = fwd_steps_;
     out->bwd_steps = bwd_steps_;
     out->launches = launches_;
-    out->device_bytes = device_bytes_ + obs_->device_bytes();
+    out->device_bytes = device_bytes_ + (cond_ ? cond_->device_bytes() : 0) + obs_->device_bytes();
     out->obs_device_bytes = obs_->device_bytes();
     out->obs_host_bytes = obs_->host_bytes();
     out->obs_evictions = obs_->evictions();

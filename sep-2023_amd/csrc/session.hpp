@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <map>
 #include <memory>
@@ -13,6 +14,7 @@
 #include "../../include/sepfwi.h"
 #include "conditioning.hpp"
 #include "config.hpp"
+#include "device_alloc.hpp"
 #include "errors.hpp"
 #include "fwi_types.hpp"
 #include "kernels.hpp"
@@ -186,7 +188,7 @@ class Session {
     InjDev &inj_dev(const ShotCtx &x);
     void persist_demote(Persist &k, const std::string &why, int retry_in);
     void persist_check_pass(Persist &k);
-    hipEvent_t *probe_pair(Call &c, int it);
+    const Event *probe_pair(Call &c, int it);
     void collect_probes(Call &c);
     // the two schedules of a call's shots
     void run_streams(Call &c);
@@ -209,15 +211,29 @@ class Session {
     Survey survey_;
     Grid g_{};
     std::mutex mu_;
-    hipStream_t own_stream_ = nullptr;
-    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_order_ = nullptr;
+    // Ownership (device_alloc.hpp): every device block of the session is a buffer booked in device_bytes_ at its real size while it is
+    // held (sepfwi_stats.device_bytes).  Members are destroyed in reverse order of declaration: the buffers first, the events and streams
+    // after them, the conditioner's FFT plans last -- ~Session only waits for the device.
+    long long device_bytes_ = 0;
+    template <class T> DevBuf<T> dev(size_t n) { return DevBuf<T>(&device_bytes_, n); }
+    // a host vector as a device block of its own (at least one element: the kernels take the pointer of an empty table too)
+    template <class T> DevBuf<T> upload(const std::vector<T> &v) {
+        DevBuf<T> b = dev<T>(std::max<size_t>(1, v.size()));
+        if (!v.empty()) HIP_OK(hipMemcpy(b.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return b;
+    }
+    // data conditioning (parameter keys if_win / filter / if_cross_misfit): the hipFFT work space
+    std::unique_ptr<Conditioner> cond_;
+    Stream own_stream_;
+    Event ev_order_;
     static constexpr int kProbePairs = 64;
-    hipEvent_t probe_ev_[2 * kProbePairs] = {};
+    Event probe_ev_[2 * kProbePairs];
+    Event ev_[4];
     double probe_us_ = 0.0;
     long long probe_calls_ = 0;
-    std::vector<void *> allocs_;
-    long long device_bytes_ = 0;
+    PinBuf<float> h_io_;
+    DevBuf<float> stf_grad_{&device_bytes_}, frame_;
+    std::vector<DevBuf<char>> allocs_;  // the constructor's blocks (dalloc): what state_, media_ ... below are views of
 
     size_t cells_ = 0, data_len_ = 0;
     // joint DAS + geophone misfit (parameter keys misfit_w_*; geophone.hpp): on?, number of active components, the column block of
@@ -228,109 +244,101 @@ class Session {
     int geo_ncomp_ = 1, geo_block_[4] = {-1, -1, -1, 0};
     size_t res_len_ = 0;
     double *geo_sums_ = nullptr;
-    GeoResShot *d_geo_res_ = nullptr;
-    int geo_res_cap_ = 0;
     std::vector<GeoResShot> geo_res_tab_;
-    ShotDev *d_shots_bwd_ = nullptr;
-    int shots_bwd_cap_ = 0;
     double parts_[3] = {0.0, 0.0, 0.0};
     // diagonal pseudo-Hessian (pseudo_hessian.hpp): armed with this stride (0: not armed); one accumulator set [E_lam | E_mu | E_rho]
     // per concurrently running forward lane or sub-batch stream, allocated on first use; how many the running call uses; the result
     // of the most recent armed call, three dense (nz, nx) arrays, and whether there is one
     int ph_every_ = 0;
-    float *ph_set_[kPhMaxSets] = {nullptr, nullptr, nullptr, nullptr};
     int ph_nsets_ = 0;
-    float *ph_out_ = nullptr;
     bool ph_valid_ = false;
     // Born modelling (born.hpp), allocated on the first Born call: [5 scattered fields | their 8 C-PML memories | 5 perturbed-media
     // arrays] and the staging of a perturbation that does not live on this device
-    float *born_ = nullptr, *born_stage_ = nullptr;
-    // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): fields + memories, frames, seismograms,
-    // residual, stream, join event
-    static constexpr int kMaxLanes = 4;
-    struct XLane {
-        float *state = nullptr, *frame = nullptr, *syn = nullptr, *res = nullptr;
-        hipStream_t stream = nullptr;
-        hipEvent_t join = nullptr;
+    DevBuf<float> born_stage_, born_;
+    DevBuf<float> ph_out_, ph_set_[kPhMaxSets];
+    DevBuf<float> inj_val_{&device_bytes_};
+    // gauge channels (parameter key das_gauge_length): per shot its taps (device copies, built on first use); the batched schedule's
+    // side table of the call's shots (GaugeShotDev, indexed like d_shots_) and its host copy
+    struct GaugeDev {
+        DevBuf<int> start, cell, field;
+        DevBuf<float> w;
     };
-    XLane xl_[kMaxLanes];
-    size_t stf_grad_len_ = 0;
-    // batched mode: lanes of per-shot state (forward: fields + memories, frames, seismograms, residual; backward: memories,
-    // adjoint fields, accumulators) and the device table of the call's shots
-    struct BLane {
-        float *state = nullptr, *bwd = nullptr, *frame = nullptr, *syn = nullptr, *res = nullptr;
+    DevBuf<GaugeShotDev> d_gauge_{&device_bytes_};
+    std::vector<GaugeShotDev> gauge_tab_;
+    std::map<int, GaugeDev> gauge_;
+    // adjoint-source injection inside the loop for shots whose receivers are not a fused line: the plan of each such shot (device
+    // copies, built on first use) and the pass's residual folded per target cell [nSteps][ntgt] (inj_val_)
+    struct InjDev {
+        DevBuf<int> lookup, tgt_start, ent_rec;
+        DevBuf<int> tgt_cell, tgt_field;  // gauge shots: per target its flat cell and field (k_inject_gauge)
+        DevBuf<InjSeg> segs;
+        DevBuf<float> ent_w;
+        std::vector<int> target_segs;       // row segments (z * nseg + xs) that hold target cells
+        DevBuf<unsigned char> tile_has;     // per tile of the tiling numbered tile_gen: owns target cells?
+        InjArgs h_args{};                   // what the kernel reads through PersistArgs::injp ...
+        DevBuf<InjArgs> d_args;             // ... and its device copy
+        int ntgt = 0, tile_gen = -1;
     };
-    std::vector<BLane> bl_;
-    struct BatchArenas {  // the lanes of one kind at a constant stride (ensure_batch)
-        float *state = nullptr, *syn = nullptr, *res = nullptr, *frame = nullptr, *bwd = nullptr;
-        int n_state = 0, n_syn = 0, n_res = 0, n_frame = 0, n_bwd = 0;
-    } ba_;
-    ShotDev *d_shots_ = nullptr;
-    int shots_cap_ = 0;
-    float *d_stf_ = nullptr;
-    size_t d_stf_len_ = 0;
-    bool last_batched_ = false;
-    bool last_exact_ = false;  // the last call's backward passes were exact ones (loop_status)
-    float *state_ = nullptr, *media_ = nullptr, *acc_buf_ = nullptr, *in_stage_ = nullptr, *grad_stage_ = nullptr;
-    float *frame_ = nullptr, *syn_ = nullptr, *res_ = nullptr, *xpose_ = nullptr, *stf_grad_ = nullptr, *h_io_ = nullptr;
-    double *scal_ = nullptr;
-    unsigned int *cp2_bits_ = nullptr;
-    int *rec_idx_ = nullptr;
-    float *sens_ = nullptr;  // directional DAS sensitivities (3 per channel) or null
-    // data conditioning (parameter keys if_win / filter / if_cross_misfit): per-channel windows and weights (3 per channel:
-    // start, end, weight; same offsets as rec_idx_), a second [rec][it] scratch gather, the hipFFT work space
-    bool cond_on_ = false;
-    float *win_ = nullptr, *xpose2_ = nullptr;
-    std::unique_ptr<Conditioner> cond_;
-    std::vector<int> rec_off_;
-    Fields fld_{}, adj_{};
-    PmlMem mem_{};
-    Media md_{};
-    PmlCoef pc_{};
-    ImgAcc acc_{};
-    std::unique_ptr<ObservedStore> obs_;
-    unsigned int *quiet_pool_ = nullptr;  // kQuietSlots x 4 maps of Grid::qn words (Fields::q)
+    std::map<int, InjDev> inj_;
     // persistent backward time loop: the tiling in use, its device copy, synchronisation words, what the census of the grid said
     struct Persist {
         PersistPlan plan;
-        uint32_t *d_seg = nullptr;
-        TileHdr *d_hdr = nullptr;
-        unsigned int *d_sync = nullptr;  // [nwg x 32 flag words | 8 band XCC ids | arrived | err]
-        unsigned long long *d_qnbr = nullptr;  // quiet variant: stencil neighbours of every row segment inside its tile (persist_plan.hpp)
-        float *d_stf = nullptr;
-        int *h_err = nullptr;            // pinned
+        DevBuf<uint32_t> d_seg;
+        DevBuf<TileHdr> d_hdr;
+        DevBuf<unsigned int> d_sync;  // [nwg x 32 flag words | 8 band XCC ids | arrived | err]
+        DevBuf<unsigned long long> d_qnbr;  // quiet variant: stencil neighbours of every row segment inside its tile (persist_plan.hpp)
+        DevBuf<float> d_stf;          // (d_stf and h_err are kept across tilings, the four above belong to one)
+        PinBuf<int> h_err;
         int nwg = 0, threads = 0, lmask = 0, lmask_req = -1, wpc = 0, strip_w = 0, order = -1, wx = -1, wxp = -1, wz = -1, snake = -1, nshots = 0;
         size_t lds_bytes = 0;
         int state = -1;                  // -1 not examined for this configuration, 0 the two-launch step is used, 1 ready
         std::string why;                 // when state == 0
         int plan_gen = 0;                // counts the tilings built (what depends on one is rebuilt when it changes)
         int retry_in = 0, aborts = 0;    // passes until the loop is tried again after a start rendezvous that failed; how often it did
-    } pk_, pk_ms_;  // one shot per launch (stream schedule) / the shots of a backward sub-batch in one launch (batched schedule)
-    // adjoint-source injection inside the loop for shots whose receivers are not a fused line: the plan of each such shot (device
-    // copies, built on first use) and the pass's residual folded per target cell [nSteps][ntgt]
-    struct InjDev {
-        int *lookup = nullptr, *tgt_start = nullptr, *ent_rec = nullptr;
-        int *tgt_cell = nullptr, *tgt_field = nullptr;  // gauge shots: per target its flat cell and field (k_inject_gauge)
-        InjSeg *segs = nullptr;
-        float *ent_w = nullptr;
-        std::vector<int> target_segs;       // row segments (z * nseg + xs) that hold target cells
-        unsigned char *tile_has = nullptr;  // per tile of the tiling numbered tile_gen: owns target cells?
-        InjArgs h_args{}, *d_args = nullptr;  // what the kernel reads through PersistArgs::injp
-        int ntgt = 0, tile_gen = -1;
+    } pk_ms_, pk_;  // the shots of a backward sub-batch in one launch (batched schedule) / one shot per launch (stream schedule)
+    std::unique_ptr<ObservedStore> obs_;
+    // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): stream, join event, fields + memories, frames,
+    // seismograms, residual
+    static constexpr int kMaxLanes = 4;
+    struct XLane {
+        Stream stream;
+        Event join;
+        DevBuf<float> state, frame, syn, res;
     };
-    std::map<int, InjDev> inj_;
-    // gauge channels (parameter key das_gauge_length): per shot its taps (device copies, built on first use); the batched schedule's
-    // side table of the call's shots (GaugeShotDev, indexed like d_shots_) and its host copy
-    struct GaugeDev {
-        int *start = nullptr, *cell = nullptr, *field = nullptr;
-        float *w = nullptr;
+    XLane xl_[kMaxLanes];
+    void ensure_lane_stream(XLane &L);
+    // batched mode: lanes of per-shot state (forward: fields + memories, frames, seismograms, residual; backward: memories,
+    // adjoint fields, accumulators) and the device tables of the call's shots and source rows
+    struct BLane {
+        float *state = nullptr, *bwd = nullptr, *frame = nullptr, *syn = nullptr, *res = nullptr;
     };
-    std::map<int, GaugeDev> gauge_;
-    GaugeShotDev *d_gauge_ = nullptr;
-    int gauge_cap_ = 0;
-    std::vector<GaugeShotDev> gauge_tab_;
-    float *inj_val_ = nullptr;
-    size_t inj_val_len_ = 0;
+    std::vector<BLane> bl_;
+    DevBuf<float> d_stf_{&device_bytes_};
+    DevBuf<GeoResShot> d_geo_res_{&device_bytes_};
+    DevBuf<ShotDev> d_shots_bwd_{&device_bytes_}, d_shots_{&device_bytes_};
+    struct BatchArenas {  // the lanes of one kind at a constant stride (ensure_batch)
+        explicit BatchArenas(long long *tally) : state(tally), syn(tally), res(tally), frame(tally), bwd(tally) {}
+        DevBuf<float> state, syn, res, frame, bwd;
+    } ba_{&device_bytes_};
+    bool last_batched_ = false;
+    bool last_exact_ = false;  // the last call's backward passes were exact ones (loop_status)
+    float *state_ = nullptr, *media_ = nullptr, *acc_buf_ = nullptr, *in_stage_ = nullptr, *grad_stage_ = nullptr;
+    float *syn_ = nullptr, *res_ = nullptr, *xpose_ = nullptr;
+    double *scal_ = nullptr;
+    unsigned int *cp2_bits_ = nullptr;
+    int *rec_idx_ = nullptr;
+    float *sens_ = nullptr;  // directional DAS sensitivities (3 per channel) or null
+    // data conditioning: per-channel windows and weights (3 per channel: start, end, weight; same offsets as rec_idx_), a second
+    // [rec][it] scratch gather
+    bool cond_on_ = false;
+    float *win_ = nullptr, *xpose2_ = nullptr;
+    std::vector<int> rec_off_;
+    Fields fld_{}, adj_{};
+    PmlMem mem_{};
+    Media md_{};
+    PmlCoef pc_{};
+    ImgAcc acc_{};
+    unsigned int *quiet_pool_ = nullptr;  // kQuietSlots x 4 maps of Grid::qn words (Fields::q)
     long long persist_steps_ = 0;
     long long quiet_active_ = 0, quiet_total_ = 0;
     unsigned int *quiet_last_ = nullptr;  // maps of the shot whose forward pass started last in this call

@@ -44,12 +44,12 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
         d.mem = x.state + 5 * n;
         d.frame = x.frame;
         d.syn = x.syn;
-        d.stf = d_stf_ + (size_t)is * nSteps;
+        d.stf = d_stf_.get() + (size_t)is * nSteps;
         d.bmem = c.with_adj ? LB.bwd : nullptr;
         d.adj = c.with_adj ? LB.bwd + 8 * n : nullptr;
         d.acc = c.with_adj ? LB.bwd + 13 * n : nullptr;
         d.res = x.res;
-        d.stf_grad = c.with_adj ? stf_grad_ + (size_t)is * nSteps : nullptr;
+        d.stf_grad = c.with_adj ? stf_grad_.get() + (size_t)is * nSteps : nullptr;
         d.z_src = x.sh->z_src;
         d.x_src = x.sh->x_src;
         d.lr_z = x.line.z;
@@ -66,44 +66,33 @@ std::vector<ShotDev> Session::batch_table(const Call &c, int Bf, int Bb) {
             q.nrec = x.nrec;
             q.comps = x.comps;
             q.rec = x.rec;
-            q.tap_start = x.gauge->start;
-            q.tap_cell = x.gauge->cell;
-            q.tap_field = x.gauge->field;
-            q.tap_w = x.gauge->w;
+            q.tap_start = x.gauge->start.get();
+            q.tap_cell = x.gauge->cell.get();
+            q.tap_field = x.gauge->field.get();
+            q.tap_w = x.gauge->w.get();
             gauged = true;
         }
         if (x.ginj) {
             gauged = true;
             q.nres = x.nres;
             q.ntgt = x.ginj->ntgt;
-            q.tgt_start = x.ginj->tgt_start;
-            q.tgt_cell = x.ginj->tgt_cell;
-            q.tgt_field = x.ginj->tgt_field;
-            q.ent_rec = x.ginj->ent_rec;
-            q.ent_w = x.ginj->ent_w;
+            q.tgt_start = x.ginj->tgt_start.get();
+            q.tgt_cell = x.ginj->tgt_cell.get();
+            q.tgt_field = x.ginj->tgt_field.get();
+            q.ent_rec = x.ginj->ent_rec.get();
+            q.ent_w = x.ginj->ent_w.get();
         }
     }
-    HIP_OK(hipMemcpyAsync(d_shots_, tab.data(), tab.size() * sizeof(ShotDev), hipMemcpyHostToDevice, c.st));
+    HIP_OK(hipMemcpyAsync(d_shots_.get(), tab.data(), tab.size() * sizeof(ShotDev), hipMemcpyHostToDevice, c.st));
     if (gauged) {  // the side table of the gauge twins
-        if (c.group_size > gauge_cap_) {
-            if (d_gauge_) (void)hipFree(d_gauge_);
-            d_gauge_ = nullptr;
-            HIP_OK(dev_malloc((void **)&d_gauge_, (size_t)c.group_size * sizeof(GaugeShotDev)));
-            device_bytes_ += (long long)((size_t)(c.group_size - gauge_cap_) * sizeof(GaugeShotDev));
-            gauge_cap_ = c.group_size;
-        }
-        HIP_OK(hipMemcpyAsync(d_gauge_, gauge_tab_.data(), gauge_tab_.size() * sizeof(GaugeShotDev), hipMemcpyHostToDevice, c.st));
+        d_gauge_.ensure((size_t)c.group_size);
+        HIP_OK(hipMemcpyAsync(d_gauge_.get(), gauge_tab_.data(), gauge_tab_.size() * sizeof(GaugeShotDev), hipMemcpyHostToDevice, c.st));
     }
     if (joint_ && c.with_adj) {  // the backward launches' table: no shot injects a fused line or through the generic receiver kernel
         std::vector<ShotDev> bt = tab;
         for (ShotDev &d : bt) d.lr_n = d.nrec = 0;
-        if (c.group_size > shots_bwd_cap_) {
-            if (d_shots_bwd_) (void)hipFree(d_shots_bwd_);
-            d_shots_bwd_ = nullptr;
-            HIP_OK(dev_malloc((void **)&d_shots_bwd_, (size_t)c.group_size * sizeof(ShotDev)));
-            shots_bwd_cap_ = c.group_size;
-        }
-        HIP_OK(hipMemcpy(d_shots_bwd_, bt.data(), bt.size() * sizeof(ShotDev), hipMemcpyHostToDevice));
+        d_shots_bwd_.ensure((size_t)c.group_size);
+        HIP_OK(hipMemcpy(d_shots_bwd_.get(), bt.data(), bt.size() * sizeof(ShotDev), hipMemcpyHostToDevice));
     }
     HIP_OK(hipStreamSynchronize(c.st));  // `tab` and `stf_rows` are pageable host memory
     return tab;
@@ -115,10 +104,7 @@ void Session::batch_streams(hipStream_t st, int ns, hipStream_t *sub) {
     if (ns <= 1) return;
     for (int q = 1; q < ns; q++) {
         XLane &L = xl_[q];
-        if (!L.stream) {
-            HIP_OK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&L.join, hipEventDisableTiming));
-        }
+        ensure_lane_stream(L);
         sub[q] = L.stream;
     }
     HIP_OK(hipEventRecord(ev_order_, st));
@@ -156,19 +142,19 @@ void Session::batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0,
     for (int it = 0; it <= nSteps - 2; it++)
         for (int q = 0; q < ns; q++) {
             const int a0 = (int)((long long)nb * q / ns), a1 = (int)((long long)nb * (q + 1) / ns);
-            launch_stress_fwd_batch(sub[q], g_, opt, d_shots_ + is0 + a0, a1 - a0, md_, pc_, cells_, data_len_, it, c.src_scale, c.with_adj);
+            launch_stress_fwd_batch(sub[q], g_, opt, d_shots_.get() + is0 + a0, a1 - a0, md_, pc_, cells_, data_len_, it, c.src_scale, c.with_adj);
             if (c.ph_every > 0 && it % c.ph_every == 0) {  // armed: the sub-batch's shots into the set of its stream (pseudo_hessian.hpp)
-                launch_pseudo_hessian_batch(sub[q], g_, d_shots_ + is0 + a0, a1 - a0, cells_, md_, ph_acc(ph_set_[q]), (float)c.ph_every);
+                launch_pseudo_hessian_batch(sub[q], g_, d_shots_.get() + is0 + a0, a1 - a0, cells_, md_, ph_acc(ph_set_[q].get()), (float)c.ph_every);
                 launches_++;
             }
-            launch_velocity_fwd_batch(sub[q], g_, opt, d_shots_ + is0 + a0, a1 - a0, md_, pc_, cells_);
+            launch_velocity_fwd_batch(sub[q], g_, opt, d_shots_.get() + is0 + a0, a1 - a0, md_, pc_, cells_);
             launches_ += 2;
             if (general(a0, a1)) {  // general receivers: ONE launch samples the new state of the sub-batch's shots into column it + 1
-                launch_record_batch(sub[q], g_, d_shots_ + is0 + a0, a1 - a0, survey_.max_nrec, cells_, data_len_, it + 1);
+                launch_record_batch(sub[q], g_, d_shots_.get() + is0 + a0, a1 - a0, survey_.max_nrec, cells_, data_len_, it + 1);
                 launches_++;
             }
             if (const int gn = gauge_nrec(a0, a1)) {  // gauge channels: their twin, from the side table
-                launch_record_gauge_batch(sub[q], d_shots_ + is0 + a0, d_gauge_ + is0 + a0, a1 - a0, gn, cells_, data_len_, it + 1);
+                launch_record_gauge_batch(sub[q], d_shots_.get() + is0 + a0, d_gauge_.get() + is0 + a0, a1 - a0, gn, cells_, data_len_, it + 1);
                 launches_++;
             }
         }
@@ -201,7 +187,7 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
             if (tab[first + k].lr_n == 0 && tab[first + k].nrec > 0) return !joint_;  // (a joint misfit: the plan serves every shot)
         return false;
     };
-    const ShotDev *shots = joint_ ? d_shots_bwd_ : d_shots_;
+    const ShotDev *shots = joint_ ? d_shots_bwd_.get() : d_shots_.get();
     // An experiment that lost, kept in the -DSEPFWI_PROBES build (option pk_ms; profiles/EXPERIMENTS.md #48): the whole sub-batch as ONE
     // persistent launch (the multi-shot loop, session_persist.cpp) where every shot's channels are a fused line (or absent).  On every
     // grid that takes the batched schedule the per-step launches below are faster, also against the loop without any synchronisation.
@@ -217,21 +203,21 @@ void Session::batched_backward(Call &c, const std::vector<ShotDev> &tab, int fir
     if (looped) nsb = 1;
     batch_streams(st, nsb, sub);
     for (int it = nSteps - 2; it >= 0 && !looped; it--) {
-        hipEvent_t *ev = probe_pair(c, it);
+        const Event *ev = probe_pair(c, it);
         Grid gs = g;
         if (opt.img_every > 1) gs.dt_img = (it % opt.img_every == 0) ? (float)opt.img_every * g.dt : 0.0f;
         for (int q = 0; q < nsb; q++) {
             const int a0 = (int)((long long)nbb * q / nsb), a1 = (int)((long long)nbb * (q + 1) / nsb);
             launch_bwd_a_batch(sub[q], gs, opt, shots + first + a0, a1 - a0, md_, pc_, n, it);
-            launch_bwd_b_batch(sub[q], gs, opt, shots + first + a0, a1 - a0, md_, pc_, n, it, c.src_scale, (ev && q == 0) ? ev[0] : nullptr,
-                               (ev && q == 0) ? ev[1] : nullptr);
+            launch_bwd_b_batch(sub[q], gs, opt, shots + first + a0, a1 - a0, md_, pc_, n, it, c.src_scale, (ev && q == 0) ? ev[0].get() : nullptr,
+                               (ev && q == 0) ? ev[1].get() : nullptr);
             launches_ += 2;
             if (general(a0, a1)) {  // res_injection_exx / _ezz for the sub-batch's shots whose channels are not a fused line: ONE launch
                 launch_inject_batch(sub[q], g, shots + first + a0, a1 - a0, survey_.max_nrec, n, it);
                 launches_++;
             }
             if (const int gt = gauge_ntgt(a0, a1)) {  // gauge channels: their twin, from the side table
-                launch_inject_gauge_batch(sub[q], shots + first + a0, d_gauge_ + first + a0, a1 - a0, gt, n, it);
+                launch_inject_gauge_batch(sub[q], shots + first + a0, d_gauge_.get() + first + a0, a1 - a0, gt, n, it);
                 launches_++;
             }
         }
@@ -249,7 +235,7 @@ void Session::run_batched(Call &c, int Bf, int Bb) {
     const int nSteps = par_.nSteps, group_size = c.group_size;
     const size_t n = cells_;
     ensure_batch(Bf, c.with_adj ? Bb : 0, c.with_adj, group_size);
-    HIP_OK(hipMemcpyAsync(d_stf_, c.stf_rows.data(), (size_t)group_size * nSteps * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_stf_.get(), c.stf_rows.data(), (size_t)group_size * nSteps * sizeof(float), hipMemcpyHostToDevice, st));
     const std::vector<ShotDev> tab = batch_table(c, Bf, Bb);
     if (c.ph_every > 0) ph_begin(c, std::min(std::min(c.opt.batch_split, (int)kMaxLanes - 1), Bf));  // one set per sub-batch stream
     if (c.with_adj)

@@ -49,27 +49,20 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
 
     const size_t n = cells_, dense = (size_t)par_.nz * (size_t)par_.nx;
     const int nSteps = par_.nSteps;
-    if (!born_) {
-        const size_t bytes = 18 * n * sizeof(float);
-        HIP_OK(dev_malloc((void **)&born_, bytes));
-        device_bytes_ += (long long)bytes;
-    }
+    if (!born_) born_ = dev<float>(18 * n);
     const float *dv[3] = {dLambda, dMu, dDen};
     for (int k = 0; k < 3; k++) {
         if (!exact && ptr_device(dv[k]) == gpu_id_) continue;  // (the exact product reads v on Omega only: it masks a copy)
-        if (!born_stage_) {
-            HIP_OK(dev_malloc((void **)&born_stage_, 3 * dense * sizeof(float)));
-            device_bytes_ += (long long)(3 * dense * sizeof(float));
-        }
-        HIP_OK(hipMemcpyAsync(born_stage_ + (size_t)k * dense, dv[k], dense * sizeof(float), hipMemcpyDefault, st));
-        dv[k] = born_stage_ + (size_t)k * dense;
+        if (!born_stage_) born_stage_ = dev<float>(3 * dense);
+        HIP_OK(hipMemcpyAsync(born_stage_.get() + (size_t)k * dense, dv[k], dense * sizeof(float), hipMemcpyDefault, st));
+        dv[k] = born_stage_.get() + (size_t)k * dense;
     }
     if (exact) {
-        launch_exact_mask(st, g_, born_stage_, 3, dense);
+        launch_exact_mask(st, g_, born_stage_.get(), 3, dense);
         launches_++;
     }
     const float *mu_dense = ptr_device(Mu) == gpu_id_ ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
-    float *dstate = born_, *dmedia = born_ + 13 * n;
+    float *dstate = born_.get(), *dmedia = born_.get() + 13 * n;
     launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
     launches_++;
 

@@ -112,29 +112,21 @@ bool Session::persist_prepare(Persist &k, const KernelOptions &opt, int nshots) 
         k.why = std::string("configuration cannot be resident at once: ") + kWhy[rc >= -4 && rc < 0 ? -rc : 0] + " (code " + std::to_string(rc) + ")";
         return false;
     }
-    auto refree = [](auto *&p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    };
-    refree(k.d_seg);
-    refree(k.d_hdr);
-    refree(k.d_sync);
-    refree(k.d_qnbr);
+    k.d_seg.reset();  // the tables of the last tiling go before the new ones come
+    k.d_hdr.reset();
+    k.d_sync.reset();
+    k.d_qnbr.reset();
     if (!multi) {  // quiet row segments inside the loop: where a segment's stencil neighbours sit in its tile
         const std::vector<unsigned long long> nb = make_quiet_neighbours(k.plan);
-        if (!nb.empty()) {
-            HIP_OK(dev_malloc((void **)&k.d_qnbr, nb.size() * sizeof(unsigned long long)));
-            HIP_OK(hipMemcpy(k.d_qnbr, nb.data(), nb.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        }
+        if (!nb.empty()) k.d_qnbr = upload(nb);
     }
-    const size_t sync_words = (size_t)k.nwg * 32 + 16;
-    HIP_OK(dev_malloc((void **)&k.d_seg, k.plan.seg.size() * sizeof(uint32_t)));
-    HIP_OK(dev_malloc((void **)&k.d_hdr, k.plan.hdr.size() * sizeof(TileHdr)));
-    HIP_OK(dev_malloc((void **)&k.d_sync, sync_words * sizeof(unsigned int)));
-    if (!k.d_stf) HIP_OK(dev_malloc((void **)&k.d_stf, (size_t)par_.nSteps * sizeof(float)));
-    if (!k.h_err) HIP_OK(hipHostMalloc((void **)&k.h_err, 4 * sizeof(int), hipHostMallocDefault));
-    HIP_OK(hipMemcpy(k.d_seg, k.plan.seg.data(), k.plan.seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(k.d_hdr, k.plan.hdr.data(), k.plan.hdr.size() * sizeof(TileHdr), hipMemcpyHostToDevice));
+    k.d_seg = dev<uint32_t>(k.plan.seg.size());
+    k.d_hdr = dev<TileHdr>(k.plan.hdr.size());
+    k.d_sync = dev<unsigned int>((size_t)k.nwg * 32 + 16);
+    if (!k.d_stf) k.d_stf = dev<float>((size_t)par_.nSteps);
+    k.h_err.ensure(4);
+    HIP_OK(hipMemcpy(k.d_seg.get(), k.plan.seg.data(), k.plan.seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(k.d_hdr.get(), k.plan.hdr.data(), k.plan.hdr.size() * sizeof(TileHdr), hipMemcpyHostToDevice));
     k.state = 1;
     k.plan_gen++;
     k.why.clear();
@@ -160,23 +152,18 @@ Session::InjDev &Session::inj_dev(const ShotCtx &x) {
                                  : make_inject_plan(sh.nrec, sh.z_rec.data(), sh.x_rec.data(), sens, par_.fiber != 0, g_.dx * g_.rdz, g_.nzc, g_.nx);
     InjDev d;
     d.ntgt = p.ntgt;
-    auto up = [&](auto **dst, const auto &v) {
-        HIP_OK(dev_malloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(v[0])));
-        if (!v.empty()) HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        device_bytes_ += (long long)(v.size() * sizeof(v[0]));
-    };
-    up(&d.lookup, p.lookup);
-    up(&d.segs, p.segs);
-    up(&d.tgt_start, p.tgt_start);
-    up(&d.ent_rec, p.ent_rec);
-    up(&d.ent_w, p.ent_w);
+    d.lookup = upload(p.lookup);
+    d.segs = upload(p.segs);
+    d.tgt_start = upload(p.tgt_start);
+    d.ent_rec = upload(p.ent_rec);
+    d.ent_w = upload(p.ent_w);
     if (by_taps) {
-        up(&d.tgt_cell, tgt_cell);
-        up(&d.tgt_field, tgt_field);
+        d.tgt_cell = upload(tgt_cell);
+        d.tgt_field = upload(tgt_field);
     }
     for (size_t sidx = 0; sidx < p.lookup.size(); sidx++)
         if (p.lookup[sidx] >= 0) d.target_segs.push_back((int)sidx);  // (which tiles own them depends on the tiling: persist_inject)
-    return inj_.emplace(x.id, d).first->second;
+    return inj_.emplace(x.id, std::move(d)).first->second;
 }
 
 // Adjoint source of a shot whose receivers are not a fused horizontal line (strided or scattered channels, a vertical fibre,
@@ -188,14 +175,8 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
     auto it = inj_.find(x.id);
     const InjDev &d = it->second;
     const size_t need = (size_t)par_.nSteps * (size_t)std::max(1, d.ntgt);
-    if (need > inj_val_len_) {
-        if (inj_val_) (void)hipFree(inj_val_);
-        inj_val_ = nullptr;
-        HIP_OK(dev_malloc((void **)&inj_val_, need * sizeof(float)));
-        device_bytes_ += (long long)((need - inj_val_len_) * sizeof(float));
-        inj_val_len_ = need;
-    }
-    launch_inject_values(st, x.res, x.nres, par_.nSteps, d.tgt_start, d.ent_rec, d.ent_w, d.ntgt, inj_val_);
+    inj_val_.ensure(need);
+    launch_inject_values(st, x.res, x.nres, par_.nSteps, d.tgt_start.get(), d.ent_rec.get(), d.ent_w.get(), d.ntgt, inj_val_.get());
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) throw HipError(std::string("k_inject_values launch failed: ") + hipGetErrorString(le));
     launches_++;
@@ -203,22 +184,20 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
         InjDev &dd = it->second;
         std::vector<unsigned char> has((size_t)pk_.nwg, 0);
         for (int sidx : dd.target_segs) has[(size_t)pk_.plan.owner[(size_t)sidx]] = 1;
-        if (dd.tile_has) (void)hipFree(dd.tile_has);
-        dd.tile_has = nullptr;
-        HIP_OK(dev_malloc((void **)&dd.tile_has, has.size()));
-        HIP_OK(hipMemcpy(dd.tile_has, has.data(), has.size(), hipMemcpyHostToDevice));
+        dd.tile_has.reset();
+        dd.tile_has = upload(has);
         dd.tile_gen = pk_.plan_gen;
     }
     InjDev &dd = it->second;  // the kernel reaches the tables through ONE pointer: this block, in device memory
-    dd.h_args.tile_has = d.tile_has;
-    dd.h_args.lookup = d.lookup;
-    dd.h_args.segs = d.segs;
-    dd.h_args.val = inj_val_;
+    dd.h_args.tile_has = d.tile_has.get();
+    dd.h_args.lookup = d.lookup.get();
+    dd.h_args.segs = d.segs.get();
+    dd.h_args.val = inj_val_.get();
     dd.h_args.ntgt = d.ntgt;
     dd.h_args.nseg = (g_.nx + 63) / 64;
-    if (!dd.d_args) HIP_OK(dev_malloc((void **)&dd.d_args, sizeof(InjArgs)));
-    HIP_OK(hipMemcpyAsync(dd.d_args, &dd.h_args, sizeof(InjArgs), hipMemcpyHostToDevice, st));  // (h_args lives in the session's map: valid until the copy has run)
-    return dd.d_args;
+    if (!dd.d_args) dd.d_args = dev<InjArgs>(1);
+    HIP_OK(hipMemcpyAsync(dd.d_args.get(), &dd.h_args, sizeof(InjArgs), hipMemcpyHostToDevice, st));  // (h_args lives in the session's map: valid until the copy has run)
+    return dd.d_args.get();
 }
 
 std::string Session::loop_status() {
@@ -244,17 +223,17 @@ bool Session::backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L) {
     Persist &k = pk_;
     const int nSteps = par_.nSteps;
     hipStream_t st = L.s;
-    HIP_OK(hipMemcpyAsync(k.d_stf, x.stf_s, (size_t)nSteps * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(k.d_stf.get(), x.stf_s, (size_t)nSteps * sizeof(float), hipMemcpyHostToDevice, st));
     PersistArgs a{};
     ShotDev &d = a.s;
     d.fields = x.state;
     d.frame = x.frame;
-    d.stf = k.d_stf;
+    d.stf = k.d_stf.get();
     d.bmem = L.bm.dvz_dz;
     d.adj = L.adj.vz;
     d.acc = L.acc.lam;
     d.res = x.res;
-    d.stf_grad = stf_grad_ + (size_t)x.is * nSteps;
+    d.stf_grad = stf_grad_.get() + (size_t)x.is * nSteps;
     d.z_src = x.sh->z_src;
     d.x_src = x.sh->x_src;
     d.lr_z = x.line.z;
@@ -265,7 +244,7 @@ bool Session::backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L) {
     d.lr_n = a.injp ? 0 : x.line.n;  // a line that is not fused (line_fuse=0) goes through the plan: the bodies must not inject it again
     if (x.quiet && k.d_qnbr && !a.injp) {  // option quiet_skip (fused line of channels, or none): the quiet variant of the loop
         a.q.maps = x.quiet;
-        a.q.nbr = k.d_qnbr;
+        a.q.nbr = k.d_qnbr.get();
     }
     if (!persist_launch(k, c, a, st)) return false;
     persist_steps_ += (long long)(nSteps - 1);
@@ -281,7 +260,7 @@ bool Session::batched_backward_persistent(Call &c, const std::vector<ShotDev> &t
     PersistArgs a{};
     a.s = tab[first];
     MultiShot &m = a.ms;
-    m.shots = d_shots_ + first;
+    m.shots = d_shots_.get() + first;
     m.nshot = nbb;
     if (nbb > 1) {
         m.state_stride = (size_t)(tab[first + 1].fields - tab[first].fields);
@@ -304,9 +283,9 @@ bool Session::batched_backward_persistent(Call &c, const std::vector<ShotDev> &t
 // The launch of a prepared configuration and its start verdict (shared by the single- and the multi-shot loop).
 bool Session::persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st) {
     const int nSteps = par_.nSteps;
-    unsigned int *band_xcc = k.d_sync + (size_t)k.nwg * 32;
+    unsigned int *band_xcc = k.d_sync.get() + (size_t)k.nwg * 32;
     int *err = (int *)(band_xcc + 10);
-    HIP_OK(hipMemsetAsync(k.d_sync, 0, ((size_t)k.nwg * 32 + 16) * sizeof(unsigned int), st));
+    HIP_OK(hipMemsetAsync(k.d_sync.get(), 0, ((size_t)k.nwg * 32 + 16) * sizeof(unsigned int), st));
     HIP_OK(hipMemsetAsync(band_xcc, 0xff, 8 * sizeof(unsigned int), st));
     a.media = md_.lam;
     a.cz = pc_.a_z;
@@ -318,9 +297,9 @@ bool Session::persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st
     a.nband = k.plan.nband;
     a.per_band = k.plan.per_band;
     a.cap = k.plan.cap;
-    a.seg = k.d_seg;
-    a.hdr = k.d_hdr;
-    a.flags = k.d_sync;
+    a.seg = k.d_seg.get();
+    a.hdr = k.d_hdr.get();
+    a.flags = k.d_sync.get();
     a.band_xcc = band_xcc;
     a.err = err;
     a.phase0 = 0;
@@ -334,11 +313,11 @@ bool Session::persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st
         return false;
     }
     launches_++;
-    HIP_OK(hipMemcpyAsync(k.h_err, err, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(k.h_err + 1, band_xcc + 9, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(k.h_err.get(), err, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(k.h_err.get() + 1, band_xcc + 9, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (k.h_err[1] != (int)kPersistGo) {  // the loop did not start: this pass, and the session from now on, as per-step launches
-        const bool busy = k.h_err[1] != (int)kPersistAbortPlacement;
+    if (k.h_err.get()[1] != (int)kPersistGo) {  // the loop did not start: this pass, and the session from now on, as per-step launches
+        const bool busy = k.h_err.get()[1] != (int)kPersistAbortPlacement;
         // transient contention: another try after 16 passes, three times at most
         persist_demote(k, busy ? "the grid was not resident at once (GPU busy, or the configuration does not fit)" : "workgroups of one band run on several XCDs",
                        busy && k.aborts < 3 ? 16 : 0);
@@ -351,9 +330,9 @@ bool Session::persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st
 // discarded, the session goes back to the two-launch step and the call fails with where the tiles stood (the reference: exit(1),
 // Src/utilities.h:28-36).
 void Session::persist_check_pass(Persist &k) {
-    if (k.h_err[0] == 0) return;
+    if (k.h_err.get()[0] == 0) return;
     std::vector<unsigned int> fl((size_t)k.nwg * 32);  // flags[tile] = phases whose edge part is complete
-    HIP_OK(hipMemcpy(fl.data(), k.d_sync, fl.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(fl.data(), k.d_sync.get(), fl.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
     unsigned int lo = ~0u, hi = 0;
     int t_lo = 0, never = 0;
     for (int t = 0; t < k.nwg; t++) {

@@ -76,11 +76,7 @@ void Session::prepare_buffers(Call &c, const float *stf) {
     hipStream_t st = c.st;
     const int nSteps = par_.nSteps;
     const size_t n = cells_;
-    if (c.with_adj && !frame_) {
-        const size_t fb = (size_t)nSteps * 5 * (size_t)g_.frame_len * sizeof(float);
-        HIP_OK(dev_malloc((void **)&frame_, fb));
-        device_bytes_ += (long long)fb;
-    }
+    if (c.with_adj && !frame_) frame_ = dev<float>((size_t)nSteps * 5 * (size_t)g_.frame_len);
     if (c.with_adj) HIP_OK(hipMemsetAsync(acc_buf_, 0, 5 * n * sizeof(float), st));
     if (c.if_res) HIP_OK(hipMemsetAsync(scal_, 0, 4 * sizeof(double), st));
     if (c.if_res && joint_) HIP_OK(hipMemsetAsync(geo_sums_, 0, 4 * sizeof(double), st));
@@ -92,14 +88,8 @@ void Session::prepare_buffers(Call &c, const float *stf) {
     c.src_scale = (float)std::pow(1500.0, 2);  // utilities.cu:531
     if (c.with_adj) {  // source-time-function gradients of all shots of the call, one row each
         const size_t need = (size_t)c.group_size * nSteps;
-        if (need > stf_grad_len_) {
-            if (stf_grad_) (void)hipFree(stf_grad_);
-            stf_grad_ = nullptr;
-            HIP_OK(dev_malloc((void **)&stf_grad_, need * sizeof(float)));
-            device_bytes_ += (long long)((need - stf_grad_len_) * sizeof(float));
-            stf_grad_len_ = need;
-        }
-        HIP_OK(hipMemsetAsync(stf_grad_, 0, need * sizeof(float), st));
+        stf_grad_.ensure(need);
+        HIP_OK(hipMemsetAsync(stf_grad_.get(), 0, need * sizeof(float), st));
     }
 }
 
@@ -144,11 +134,11 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     if (gauge) x.gauge = &gauge_taps(x);
     if ((gauge || (joint_ && x.nrec > 0)) && c.with_adj) x.ginj = &inj_dev(x);  // (a joint misfit: every shot's adjoint source goes through its plan)
     x.quiet = quiet_wanted(c, x) ? quiet_slot(lane) : nullptr;
-    x.ph = c.ph_every > 0 ? ph_set_[lane] : nullptr;
-    use_state(x, lane ? xl_[lane].state : state_);
-    x.frame = lane ? xl_[lane].frame : frame_;
-    x.syn = lane ? xl_[lane].syn : syn_;
-    x.res = lane ? xl_[lane].res : res_;
+    x.ph = c.ph_every > 0 ? ph_set_[lane].get() : nullptr;
+    use_state(x, lane ? xl_[lane].state.get() : state_);
+    x.frame = lane ? xl_[lane].frame.get() : frame_.get();
+    x.syn = lane ? xl_[lane].syn.get() : syn_;
+    x.res = lane ? xl_[lane].res.get() : res_;
     x.st = lane_st;
     return x;
 }
@@ -169,7 +159,7 @@ void Session::forward_init(const ShotCtx &x) {
 void Session::record_column(const ShotCtx &x, int column) {
     const size_t col = (size_t)column * x.nrec;
     if (x.gauge)
-        launch_record_gauge(x.st, x.fld, x.nrec, x.rec, x.gauge->start, x.gauge->cell, x.gauge->field, x.gauge->w, syn_of(x, 0) + col, syn_of(x, 1) + col,
+        launch_record_gauge(x.st, x.fld, x.nrec, x.rec, x.gauge->start.get(), x.gauge->cell.get(), x.gauge->field.get(), x.gauge->w.get(), syn_of(x, 0) + col, syn_of(x, 1) + col,
                             syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps);
     else
         launch_record(x.st, g_, x.fld, x.nrec, x.rec, syn_of(x, 0) + col, syn_of(x, 1) + col, syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps, x.sens);
@@ -186,16 +176,11 @@ const Session::GaugeDev &Session::gauge_taps(const ShotCtx &x) {
     std::vector<int> cell(t.w.size());
     for (size_t e = 0; e < cell.size(); e++) cell[e] = t.z[e] * g_.pitch + t.x[e];
     GaugeDev d;
-    auto up = [&](auto **dst, const auto &v) {
-        HIP_OK(dev_malloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(v[0])));
-        if (!v.empty()) HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        device_bytes_ += (long long)(v.size() * sizeof(v[0]));
-    };
-    up(&d.start, t.start);
-    up(&d.cell, cell);
-    up(&d.field, t.field);
-    up(&d.w, t.w);
-    return gauge_.emplace(x.id, d).first->second;
+    d.start = upload(t.start);
+    d.cell = upload(cell);
+    d.field = upload(t.field);
+    d.w = upload(t.w);
+    return gauge_.emplace(x.id, std::move(d)).first->second;
 }
 
 // one forward time step (libCUFD.cu:268-332); inl: the line of channels is sampled inside k_stress
@@ -253,15 +238,9 @@ void Session::residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int 
         geo_res_tab_[k] = geo_res_shot(cx[k]);
         max_nrec = std::max(max_nrec, cx[k].nrec);
     }
-    if (nb > geo_res_cap_) {
-        if (d_geo_res_) (void)hipFree(d_geo_res_);
-        d_geo_res_ = nullptr;
-        HIP_OK(dev_malloc((void **)&d_geo_res_, (size_t)nb * sizeof(GeoResShot)));
-        device_bytes_ += (long long)((size_t)(nb - geo_res_cap_) * sizeof(GeoResShot));
-        geo_res_cap_ = nb;
-    }
-    HIP_OK(hipMemcpyAsync(d_geo_res_, geo_res_tab_.data(), (size_t)nb * sizeof(GeoResShot), hipMemcpyHostToDevice, c.st));
-    launch_geo_residual_batch(c.st, d_geo_res_, nb, max_nrec, geo_ncomp_, par_.nSteps, geo_sums_);
+    d_geo_res_.ensure((size_t)nb);
+    HIP_OK(hipMemcpyAsync(d_geo_res_.get(), geo_res_tab_.data(), (size_t)nb * sizeof(GeoResShot), hipMemcpyHostToDevice, c.st));
+    launch_geo_residual_batch(c.st, d_geo_res_.get(), nb, max_nrec, geo_ncomp_, par_.nSteps, geo_sums_);
     launches_++;
 }
 
@@ -296,12 +275,12 @@ void Session::export_gathers(const Call &c, const ShotCtx &x) {
     const size_t cnt = (size_t)x.nrec * par_.nSteps;
     for (int k = 0; k < 4; k++) {
         launch_transpose(st, syn_of(x, k), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
-        HIP_OK(hipMemcpyAsync(h_io_, xpose_, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_io_.get(), xpose_, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         const std::string fn = shot_file(par_, k, x.id);
         FILE *fp = fopen(fn.c_str(), "wb");
         if (!fp) throw IoError("cannot write '" + fn + "'");  // utilities.cu:22-31
-        const size_t w = fwrite(h_io_, sizeof(float), cnt, fp);
+        const size_t w = fwrite(h_io_.get(), sizeof(float), cnt, fp);
         fclose(fp);
         if (w != cnt) throw IoError("short write on '" + fn + "'");
     }
@@ -316,7 +295,7 @@ void Session::scratch_dumps(const Call &c, const ShotCtx &x) {
     const int nSteps = par_.nSteps;
     const size_t cnt = (size_t)x.nrec * nSteps;
     launch_transpose(st, syn_of(x, 0), xpose_, nSteps, x.nrec);
-    HIP_OK(hipMemcpyAsync(h_io_, xpose_, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_io_.get(), xpose_, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     std::vector<float> obs_pr(cnt);
     {
@@ -335,11 +314,11 @@ void Session::scratch_dumps(const Call &c, const ShotCtx &x) {
         fclose(fp);
         if (w != cnt) throw IoError("short write on '" + fn + "'");
     };
-    dump("Syn_Shot", h_io_);
+    dump("Syn_Shot", h_io_.get());
     dump("CondObs_Shot", obs_pr.data());
     for (int r = 0; r < x.nrec; r++) {
         float *o = obs_pr.data() + (size_t)r * nSteps;
-        const float *sy = h_io_ + (size_t)r * nSteps;
+        const float *sy = h_io_.get() + (size_t)r * nSteps;
         o[0] = 0.0f;
         for (int t = 1; t < nSteps; t++) o[t] = o[t] - sy[t];
     }
@@ -365,7 +344,7 @@ void Session::backward_init(const BwdLane &L) {
 }
 
 // HIP-event pair for this step's k_bwd_b launch (option probe: every probe-th step), or null
-hipEvent_t *Session::probe_pair(Call &c, int it) {
+const Event *Session::probe_pair(Call &c, int it) {
     if (c.opt.probe <= 0 || c.n_probe >= kProbePairs || (it % c.opt.probe) != 0) return nullptr;
     return &probe_ev_[2 * c.n_probe++];
 }
@@ -387,7 +366,7 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
     const bool inj_inl = inject_inline(c, x);
     const Shot &sh = *x.sh;
     float *frame_t = x.frame + (size_t)it * 5 * (size_t)g.frame_len;
-    float *sg = stf_grad_ + (size_t)x.is * par_.nSteps + it;
+    float *sg = stf_grad_.get() + (size_t)x.is * par_.nSteps + it;
     const float amp = c.src_scale * x.stf_s[it] * par_.dt;
     const float *res_t = x.res + (size_t)it * x.nres;
     LineRec lr{};
@@ -398,12 +377,12 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
     Grid gs = g;  // this step's imaging weight (option img_every)
     if (opt.img_every > 1) gs.dt_img = (it % opt.img_every == 0) ? (float)opt.img_every * g.dt : 0.0f;
     if (opt.bwd_fuse != 0) {
-        hipEvent_t *ev = probe_pair(c, it);
+        const Event *ev = probe_pair(c, it);
         Fields adj = L.adj;  // (the adjoint maps follow the shot's lane; the residual enters inside k_bwd_b, which marks the channels' segments)
         adj.q = x.quiet ? x.quiet + 2 * (size_t)g.qn : nullptr;
         launch_bwd_a(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, adj, L.acc);
-        launch_bwd_b(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, (float)sh.src_rxz, sg, adj, L.acc, lr, ev ? ev[0] : nullptr,
-                     ev ? ev[1] : nullptr);
+        launch_bwd_b(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, (float)sh.src_rxz, sg, adj, L.acc, lr, ev ? ev[0].get() : nullptr,
+                     ev ? ev[1].get() : nullptr);
         if (!inj_inl) inject_column(x, L, res_t);
         launches_ += inj_inl ? 2 : 3;
     } else {  // the reference's launch structure
@@ -419,7 +398,8 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
 // this step's adjoint source: res_injection_exx / _ezz per channel (k_inject), or a gauge shot's plan, one add per target (k_inject_gauge)
 void Session::inject_column(const ShotCtx &x, const BwdLane &L, const float *res_t) {
     if (x.ginj)
-        launch_inject_gauge(L.s, L.adj, x.ginj->ntgt, res_t, x.ginj->tgt_start, x.ginj->tgt_cell, x.ginj->tgt_field, x.ginj->ent_rec, x.ginj->ent_w);
+        launch_inject_gauge(L.s, L.adj, x.ginj->ntgt, res_t, x.ginj->tgt_start.get(), x.ginj->tgt_cell.get(), x.ginj->tgt_field.get(), x.ginj->ent_rec.get(),
+                            x.ginj->ent_w.get());
     else
         launch_inject(L.s, g_, L.adj, x.nrec, x.rec, res_t, x.sens);
 }
@@ -495,13 +475,9 @@ void Session::run_streams(Call &c) {
 // first use, zeroed on the call's stream at the start of every armed call -- the result is that call's own.
 void Session::ph_begin(Call &c, int nsets) {
     nsets = std::max(1, std::min(nsets, (int)kPhMaxSets));
-    const size_t bytes = 3 * cells_ * sizeof(float);
     for (int k = 0; k < nsets; k++) {
-        if (!ph_set_[k]) {
-            HIP_OK(dev_malloc((void **)&ph_set_[k], bytes));
-            device_bytes_ += (long long)bytes;
-        }
-        HIP_OK(hipMemsetAsync(ph_set_[k], 0, bytes, c.st));
+        if (!ph_set_[k]) ph_set_[k] = dev<float>(3 * cells_);
+        HIP_OK(hipMemsetAsync(ph_set_[k].get(), 0, 3 * cells_ * sizeof(float), c.st));
     }
     ph_nsets_ = nsets;
 }
@@ -512,13 +488,8 @@ void Session::pseudo_hessian_arm(int every) {
     if (every > 0 && par_.nPml < 2) throw std::invalid_argument("pseudo-Hessian: needs nPml >= 2 (the stencils of the interior reach two cells out)");
     if (every > 0 && !ph_out_) {  // first arming: the result arrays and the first accumulator set
         HIP_OK(hipSetDevice(gpu_id_));
-        const size_t out_bytes = 3 * (size_t)par_.nz * (size_t)par_.nx * sizeof(float), set_bytes = 3 * cells_ * sizeof(float);
-        HIP_OK(dev_malloc((void **)&ph_out_, out_bytes));
-        device_bytes_ += (long long)out_bytes;
-        if (!ph_set_[0]) {
-            HIP_OK(dev_malloc((void **)&ph_set_[0], set_bytes));
-            device_bytes_ += (long long)set_bytes;
-        }
+        ph_out_ = dev<float>(3 * (size_t)par_.nz * (size_t)par_.nx);
+        if (!ph_set_[0]) ph_set_[0] = dev<float>(3 * cells_);
     }
     ph_every_ = every;
 }
@@ -531,7 +502,7 @@ void Session::pseudo_hessian_get(float *hLambda, float *hMu, float *hDen) {
     const size_t dense = (size_t)par_.nz * (size_t)par_.nx;
     float *out[3] = {hLambda, hMu, hDen};
     for (int k = 0; k < 3; k++)
-        if (out[k]) HIP_OK(hipMemcpy(out[k], ph_out_ + (size_t)k * dense, dense * sizeof(float), hipMemcpyDefault));
+        if (out[k]) HIP_OK(hipMemcpy(out[k], ph_out_.get() + (size_t)k * dense, dense * sizeof(float), hipMemcpyDefault));
 }
 
 // ---- outputs: written in place when they live on this device, staged otherwise (host memory, another GPU) ------------------
@@ -540,7 +511,7 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
     const size_t dense = (size_t)par_.nz * (size_t)par_.nx;
     if (c.with_adj && grad_stf) {  // rows indexed by local shot position (libCUFD.cu:671-673)
         std::vector<float> h_gstf((size_t)c.group_size * par_.nSteps);
-        HIP_OK(hipMemcpy(h_gstf.data(), stf_grad_, h_gstf.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(h_gstf.data(), stf_grad_.get(), h_gstf.size() * sizeof(float), hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(grad_stf, h_gstf.data(), h_gstf.size() * sizeof(float), hipMemcpyDefault));
     }
     if (c.with_adj) {
@@ -552,10 +523,10 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
     if (c.ph_every > 0) {  // the sets summed in lane order, the constants of pseudo_hessian.hpp
         PhSets sets{};
         sets.nsets = ph_nsets_;
-        for (int k = 0; k < ph_nsets_; k++) sets.set[k] = ph_set_[k];
+        for (int k = 0; k < ph_nsets_; k++) sets.set[k] = ph_set_[k].get();
         const double mdt = 1e6 * (double)g_.dt;
-        launch_pseudo_hessian_finalize(st, g_, sets, cells_, 2.0 * mdt * mdt, mdt * mdt, (double)g_.dt * (double)g_.dt, ph_out_, ph_out_ + dense,
-                                       ph_out_ + 2 * dense);
+        launch_pseudo_hessian_finalize(st, g_, sets, cells_, 2.0 * mdt * mdt, mdt * mdt, (double)g_.dt * (double)g_.dt, ph_out_.get(), ph_out_.get() + dense,
+                                       ph_out_.get() + 2 * dense);
         launches_++;
         ph_valid_ = true;
     }
@@ -607,7 +578,7 @@ Session::Call Session::begin_call(hipStream_t ext_stream, int group_size, const 
     c.t_begin = std::chrono::steady_clock::now();
     HIP_OK(hipSetDevice(gpu_id_));
     c.opt = kernel_options();  // ONE snapshot for the whole call
-    c.st = ext_stream ? ext_stream : own_stream_;
+    c.st = ext_stream ? ext_stream : own_stream_.get();
     if (!ext_stream) order_after_null_stream(c.st);
     c.group_size = group_size;
     c.shot_ids = shot_ids;

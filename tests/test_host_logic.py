@@ -63,6 +63,9 @@ def test_status_queries_without_a_session_are_errors_not_crashes(tmp_path):
     assert L.sepfwi_get_stats(fn, 0, C.byref(st)) == -1 and b"no session" in L.sepfwi_last_error()
     out = (C.c_float * 4)()
     assert L.sepfwi_debug_field(fn, 0, 0, 0, out) == -1
+    dev, pin = C.c_longlong(-1), C.c_longlong(-1)
+    assert L.sepfwi_debug_live_bytes(None, C.byref(pin)) == -1 and L.sepfwi_debug_live_bytes(C.byref(dev), None) == -1
+    assert L.sepfwi_debug_live_bytes(C.byref(dev), C.byref(pin)) == 0 and dev.value >= 0 and pin.value >= 0
 
 
 def test_library_does_not_link_hipfft():

@@ -69,3 +69,18 @@ def test_injection_plan_under_asan_ubsan(tmp_path):
     for seed in (1, 2):
         out = subprocess.run([exe, str(seed), "400"], env=env, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_owning_buffers_under_asan_ubsan(tmp_path):
+    """The owners of every device and pinned allocation, stream and event of the library (csrc/device_alloc.hpp), on a malloc-backed
+    stub of the two raw functions: moves, the tally and the process-wide counters against the bytes really held, ensure (free before
+    allocate; a failed allocation leaves an empty buffer of capacity 0), constructors that throw after every j-th allocation, maps
+    of move-only structs of buffers -- and a clean leak report."""
+    exe = str(tmp_path / "device_buffer_check")
+    src = [os.path.join(ROOT, "tests", "native", "device_buffer_check.cpp")]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-o", exe] + src)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
