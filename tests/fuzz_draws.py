@@ -1,0 +1,357 @@
+"""The generators of the fuzz tests: everything a seed draws, and nothing that compares.  Every generator draws every quantity for every
+seed, used or not, and later ingredients come from generators of their own, so that the geometry of a seed stays what the other fuzz
+files see; tests/test_gauge_reference.py, tests/test_born_fuzz_reference.py and tests/test_exact_adjoint_fuzz_reference.py hold digests of
+the first 16 seeds' draws
+(draw_problem; draw_gauge, draw_born and draw_exact change its draw for tests/test_gpu_gauge_fuzz.py, test_gpu_born_fuzz.py and
+test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw)."""
+import json
+import os
+
+import numpy as np
+
+import born_ref as B
+import exact_adjoint_ref as X
+from gauge_ref import COND_KEYS
+
+OPTION_SETS = [dict(), dict(batch=0), dict(batch=1, batch_f=2, batch_b=1), dict(batch=1, batch_f=3, batch_b=3), dict(batch_order=0),
+               dict(batch=0, fwd_lanes=2), dict(line_fuse=0), dict(bwd_fuse=0), dict(early=3, rho_fly=3), dict(amu_fly=3)]
+
+
+def draw_problem(tmp_path, seed, scale):
+    """Everything a seed draws, the problem written under tmp_path: -> dict(pb, sv, opts, extra, kind, want_cross, water, nSteps, f0).
+    The problem of the seed at `scale` times its record length (the re-draw of fuzz_common.settle)."""
+    import problems as P
+    rng = np.random.default_rng(1000 + seed)
+    nPml = int(rng.integers(4, 13))
+    nz, nx = int(rng.integers(24, 60)), int(rng.integers(30, 100))
+    nPad = int(rng.integers(0, 9))
+    nSteps = int(rng.integers(90, 200)) * scale
+    nshots = int(rng.integers(1, 5))
+    # spacings, time step and peak frequency from a generator of their own (the geometry of a seed is what it was before they
+    # varied): 5 ... 25 m cells, dz within 30 % of dx, a Courant number of 0.25 ... 0.8 for the fastest cell, 8 ... 40 Hz
+    rq = np.random.default_rng(77000 + seed)
+    dx = float(np.round(rq.uniform(5.0, 25.0), 2))
+    dz = float(np.round(dx * rq.uniform(0.7, 1.3), 2))
+    dt = float(rq.uniform(0.25, 0.8) * min(dz, dx) / (3800.0 * 1.05 * np.sqrt(2.0) * (9.0 / 8.0 + 1.0 / 24.0)))
+    f0 = float(np.round(max(rq.uniform(8.0, 40.0), 3.0 / (nSteps * dt)), 1))   # the wavelet's peak (1.2 / f0) inside the first 40 % of the record
+    tweak = os.environ.get("SEPFWI_FUZZ_TWEAK", "").split(",")      # diagnosis: the same draw with one ingredient changed
+    if "square" in tweak:
+        dz = dx
+    if "lowf" in tweak:
+        f0 = float(np.round(max(8.0, 3.0 / (nSteps * dt)), 1))
+    if os.environ.get("SEPFWI_FUZZ_DIAG"):
+        print("seed %d: nz %d nx %d nPml %d nPad %d nSteps %d nshots %d dx %.2f dz %.2f dt %.3e f0 %.1f (Courant %.2f, %.1f points per shortest S wavelength)"
+              % (seed, nz, nx, nPml, nPad, nSteps, nshots, dx, dz, dt, f0, 3990.0 * dt * 1.65 / min(dx, dz), 1400.0 / (2.5 * f0) / max(dx, dz)))
+    pb = P.make_problem(str(tmp_path), nz=nz, nx=nx, nPml=nPml, nSteps=nSteps, nshots=nshots, nPad=nPad, hetero=True, seed=seed,
+                        src_z=int(rng.integers(1, 5)), rec_z=int(rng.integers(2, nz - 3)), dh=dx, dz=dz, dt=dt, f0=f0)
+    sv = json.load(open(pb["survey_fname"]))
+    kind = int(rng.integers(0, 3))
+    if kind == 1:      # every 2nd .. 4th cell
+        step = int(rng.integers(2, 5))
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            sh["x_rec"], sh["z_rec"] = sh["x_rec"][::step], sh["z_rec"][::step]
+            sh["nrec"] = len(sh["x_rec"])
+    elif kind == 2:    # scattered channels, the same for all shots (the oracle front end wants one nrec)
+        m = int(rng.integers(3, 15))
+        xs = rng.integers(1, nx - 1, size=m).tolist()
+        zs = rng.integers(1, nz - 1, size=m).tolist()
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            sh["x_rec"], sh["z_rec"], sh["nrec"] = [int(v) for v in xs], [int(v) for v in zs], m
+    json.dump(sv, open(pb["survey_fname"], "w"))
+    opts = OPTION_SETS[int(rng.integers(0, len(OPTION_SETS)))]
+    if os.environ.get("SEPFWI_FUZZ_OPTS"):      # diagnosis: the same draw with other kernel options ("amu_fly=0,rho_fly=0")
+        opts = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in os.environ["SEPFWI_FUZZ_OPTS"].split(",")}
+    # extensions, drawn last so that the geometry of a seed does not depend on them: per-channel directional sensitivities
+    # (survey key das_sensitivity) and the data-conditioning chain (band-pass, cross-correlation misfit, source-signature update)
+    extra = int(rng.integers(0, 6))
+    if os.environ.get("SEPFWI_FUZZ_NOEXTRA"):   # diagnosis: the same geometry without the extension it drew
+        extra = 0
+    if extra == 1:
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            sens = np.zeros((sh["nrec"], 6))
+            sens[:, [0, 3, 1]] = rng.uniform(-1.0, 1.0, (sh["nrec"], 3))
+            sh["das_sensitivity"] = sens.tolist()
+        json.dump(sv, open(pb["survey_fname"], "w"))
+    want_cross = False
+    if extra in (2, 4, 5):
+        para = dict(pb["para"])
+        if extra != 5:
+            para["filter"] = [0.12 * f0, 0.32 * f0, 1.8 * f0, 2.8 * f0]
+        if extra == 2:
+            want_cross = bool(rng.integers(0, 2))
+        elif kind != 2:
+            # source-signature update, with (4) and without (5) the band-pass.  Not for scattered channels: their amplitudes span
+            # tens of decades, ONE channel dominates the least-squares filter, which then fits it exactly -- the misfit collapses
+            # to rounding level and its gradient is noise on both sides (seed 232 of a round-3 sweep: misfit 1.7e-4 of 1.4e4)
+            para["if_src_update"] = True
+        json.dump(para, open(pb["para_fname"], "w"))
+        pb["para"] = para
+    # a water layer (mu = 0) over the top rows in one draw of four -- the LAST draw, so that everything above is what it was for a
+    # seed before the layer was added (round 3: 1 / mu^2 of a fluid cell met a zero spray weight in the gradient finalisation)
+    w = 0
+    if int(rng.integers(0, 4)) == 0 and "nowater" not in tweak:
+        w = nPml + int(rng.integers(2, max(3, nz // 3)))
+        P.add_water(pb, w)
+    return dict(pb=pb, sv=sv, opts=opts, extra=extra, kind=kind, want_cross=want_cross, water=w, nSteps=nSteps, f0=f0)
+
+
+def observed_model(pb):
+    """The "observed" model = the true model made 8 % stiffer / 3 % denser everywhere: residuals of the size of the data, so the gradient is
+    well conditioned against float32 round-off (with a residual 1e-3 of the data, 1e-7 of forward noise -- e.g. two equally valid FMA
+    contractions -- is already 1e-3 of the gradient).  -> three contiguous tensors"""
+    lam_t, mu_t, den_t = pb["lame_true"]
+    return (lam_t * 1.08).contiguous(), (mu_t * 0.95).contiguous(), (den_t * 1.03).contiguous()
+
+
+def ragged_counts(rg, n, nshots, ragged):
+    """Per-shot channel counts out of n and the shot that keeps a single channel, drawn whether used or not.  -> the counts: ragged ones
+    with a single-channel shot and at least two different counts, else n for every shot."""
+    counts = [int(c) for c in rg.integers(1, n + 1, size=nshots)]
+    single = int(rg.integers(0, nshots))
+    if not ragged:
+        return [n] * nshots
+    counts[single] = 1
+    if len(set(counts)) == 1:
+        counts[(single + 1) % nshots] = n
+    return counts
+
+
+# ---- gauge channels ------------------------------------------------------------------------------------------------------------
+GAUGE_SEED0 = 52000      # offset of the gauge generator's seeds (test_gauge_fuzz_draws_have_parity_targets holds for the default 16)
+MODES = ("horizontal", "vertical", "directional-horizontal", "directional-vertical")
+SETS = ("overlapping line", "line", "scattered")
+SIDES = ("top", "bottom", "left", "right")
+
+
+def member_bounds(nz, nx, nPml, vertical, directional):
+    """Padded cells where check_gauge_members (csrc/das_gauge.cpp) accepts a member: (zlo, zhi, xlo, xhi), inclusive.  nz, nx unpadded."""
+    nzc, nxp = nz + 2 * nPml, nx + 2 * nPml
+    return (1 if (vertical or directional) else 0, nzc - 1 - (1 if directional else 0),
+            0 if (vertical and not directional) else 1, nxp - 1 - (1 if directional else 0))
+
+
+def draw_gauge(d, seed):
+    """Replaces the channels of the draw d (draw_problem) by gauge channels and rewrites its two files.  -> dict(G, mode,
+    vertical, directional, set, stride, ragged, touch (side name or None), bad_survey (channel 0 one cell beyond the bound, or None))."""
+    pb = d["pb"]
+    nPml, nPad = pb["nPml"], pb["nPad"]
+    nz, nx = pb["nz_pad"] - 2 * nPml - nPad, pb["nx_pad"] - 2 * nPml
+    nshots = int(pb["Shot_ids"].numel())
+    rg = np.random.default_rng(GAUGE_SEED0 + seed)
+    G = int(rg.integers(2, 10))
+    mode = int(rg.integers(0, 4))
+    vertical, directional = mode in (1, 3), mode in (2, 3)
+    h = G // 2                                        # reach of the outermost member, odd and even G
+    na, nc = (nz, nx) if vertical else (nx, nz)       # extent along / across the gauge axis
+    cs = int(rg.integers(0, 3))
+    stride = 0
+    if cs < 2:
+        stride = int(rg.integers(1, G)) if cs == 0 else G + int(rg.integers(0, 3))
+        cross = int(rg.integers(2, nc - 2))
+        along = np.arange(h + 1 + int(rg.integers(0, 3)), na - h - 1, stride)
+        cr = np.full(along.size, cross)
+    else:
+        m = int(rg.integers(4, 15))
+        along = rg.integers(h + 1, na - h - 1, size=m)
+        cr = rg.integers(2, nc - 2, size=m)
+        along[2], cr[2] = along[1], cr[1]                                                        # a repeat
+        along[3], cr[3] = (along[1] + 1 if along[1] + 1 < na - h - 1 else along[1] - 1), cr[1]   # a neighbour one cell along the axis
+    n = int(along.size)
+    assert n >= 2, (seed, n)
+    z, x = (along, cr) if vertical else (cr, along)
+    z, x = [int(v) for v in z], [int(v) for v in x]
+    sens = np.zeros((n, 6))
+    sens[:, [0, 3, 1]] = rg.uniform(-1.0, 1.0, (n, 3))
+    ragged = bool(rg.integers(0, 2)) and nshots > 1
+    counts = ragged_counts(rg, n, nshots, ragged)
+    touch, side = int(rg.integers(0, 4)) == 0, int(rg.integers(0, 4))
+    bad = None
+    if touch:       # channel 0 (in every shot's list): its outermost member on the last accepted cell of one side
+        zlo, zhi, xlo, xhi = member_bounds(nz, nx, nPml, vertical, directional)
+        hz, hx = (h, 0) if vertical else (0, h)
+        bz, bx = z[0], x[0]
+        if side == 0:
+            z[0] = zlo + hz - nPml; bz = z[0] - 1
+        elif side == 1:
+            z[0] = zhi - hz - nPml; bz = z[0] + 1
+        elif side == 2:
+            x[0] = xlo + hx - nPml; bx = x[0] - 1
+        else:
+            x[0] = xhi - hx - nPml; bx = x[0] + 1
+    sv = d["sv"]
+
+    def put(sv_, z_, x_):
+        for k in range(nshots):
+            sh = sv_["shot%d" % k]
+            sh["z_rec"], sh["x_rec"], sh["nrec"] = z_[:counts[k]], x_[:counts[k]], counts[k]
+            sh.pop("das_sensitivity", None)
+            if directional:
+                sh["das_sensitivity"] = sens[:counts[k]].tolist()
+
+    put(sv, z, x)
+    if touch:
+        bad = json.loads(json.dumps(sv))
+        put(bad, [bz] + z[1:], [bx] + x[1:])
+    para = dict(pb["para"])
+    para.pop("das_fiber", None)
+    if vertical:
+        para["das_fiber"] = "vertical"
+    para["das_gauge_length"] = G * float(para["dz"] if vertical else para["dx"])
+    if cs == 2:
+        # no source update for scattered channels, as in draw_problem (one channel dominates the least-squares filter, the misfit
+        # collapses to rounding level and its gradient is noise on both sides)
+        para.pop("if_src_update", None)
+    json.dump(sv, open(pb["survey_fname"], "w"))
+    json.dump(para, open(pb["para_fname"], "w"))
+    pb["para"] = para
+    return dict(G=G, mode=MODES[mode], vertical=vertical, directional=directional, set=SETS[cs], stride=stride, ragged=ragged, counts=counts,
+                touch=SIDES[side] if touch else None, bad_survey=bad)
+
+
+# ---- Born modelling --------------------------------------------------------------------------------------------------------------
+BORN_SEED0 = 91000
+BORN_OPTION_SETS = [dict(), dict(bz=1), dict(bz=4), dict(xcd_remap=0), dict(rho_fly=0), dict(amu_fly=0), dict(rk_lazy=0), dict(bwd_fuse=0),
+                    dict(quiet_skip=1), dict(batch=0)]
+
+
+def born_raw(seed):
+    """What draw_born draws for a seed before it looks at the problem, and its generator, from which the channel counts follow.
+    mode 0: joint weights, 1: gauge length, 2 and 3: the draw's own channels and misfit"""
+    rg = np.random.default_rng(BORN_SEED0 + seed)
+    raw = dict(want_cond=int(rg.integers(0, 4)) == 0, opts=BORN_OPTION_SETS[int(rg.integers(0, len(BORN_OPTION_SETS)))],
+               want_ragged=bool(rg.integers(0, 2)), mode=int(rg.integers(0, 4)))
+    raw["w_vx"], raw["w_vz"] = [float(np.round(w, 3)) for w in rg.uniform(0.1, 1.0, 2)]
+    raw["G"] = int(rg.integers(2, 6))
+    raw["vertical"] = bool(rg.integers(0, 2))
+    raw["stride"], raw["start"], raw["cross_u"] = int(rg.integers(1, raw["G"] + 2)), int(rg.integers(0, 3)), float(rg.uniform())
+    return raw, rg
+
+
+def draw_born(d, seed):
+    """Changes the draw d (draw_problem) as the docstring of tests/test_gpu_born_fuzz.py says and rewrites its two files.  Every quantity is drawn
+    for every seed, used or not, so that one ingredient never shifts another.
+    -> dict(opts, cond_fname (or None), ragged, counts, weights ((1, w_vx, w_vz) or None), G (0: none), vertical)."""
+    pb, sv = d["pb"], d["sv"]
+    nPml, nPad = pb["nPml"], pb["nPad"]
+    nz, nx = pb["nz_pad"] - 2 * nPml - nPad, pb["nx_pad"] - 2 * nPml
+    nshots = int(pb["Shot_ids"].numel())
+    raw, rg = born_raw(seed)
+    want_cond, opts, mode, w_vx, w_vz, G, vertical = [raw[k] for k in ("want_cond", "opts", "mode", "w_vx", "w_vz", "G", "vertical")]
+    stride, start, cross_u = raw["stride"], raw["start"], raw["cross_u"]
+    para = {k: v for k, v in pb["para"].items() if k not in COND_KEYS}
+    if mode == 1:       # a line of gauge channels along the gauge's axis, every member inside the physical grid
+        h = G // 2
+        na, nc = (nz, nx) if vertical else (nx, nz)
+        along = np.arange(h + 1 + start, na - h - 1, stride)
+        cross = np.full(along.size, 2 + int(cross_u * (nc - 4)))
+        z, x = (along, cross) if vertical else (cross, along)
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            sh["z_rec"], sh["x_rec"], sh["nrec"] = [int(a) for a in z], [int(a) for a in x], int(along.size)
+            sh.pop("das_sensitivity", None)
+        para.pop("das_fiber", None)
+        if vertical:
+            para["das_fiber"] = "vertical"
+        para["das_gauge_length"] = G * float(para["dz"] if vertical else para["dx"])
+    else:
+        G, vertical = 0, para.get("das_fiber", "horizontal") == "vertical"
+    weights = None
+    if mode == 0:
+        weights = (1.0, w_vx, w_vz)
+        para.update(misfit_w_ett=1.0, misfit_w_vx=w_vx, misfit_w_vz=w_vz)
+    n = int(sv["shot0"]["nrec"])
+    ragged = raw["want_ragged"] and nshots > 1 and n > 1
+    counts = ragged_counts(rg, n, nshots, ragged)
+    if ragged:
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            sh["z_rec"], sh["x_rec"], sh["nrec"] = sh["z_rec"][:counts[k]], sh["x_rec"][:counts[k]], counts[k]
+            if "das_sensitivity" in sh:
+                sh["das_sensitivity"] = sh["das_sensitivity"][:counts[k]]
+    json.dump(sv, open(pb["survey_fname"], "w"))
+    json.dump(para, open(pb["para_fname"], "w"))
+    pb["para"] = para
+    cond_fname = None
+    if want_cond:       # the same problem with a live conditioning key, a session of its own (plain misfit: a joint one refuses the key)
+        cond_fname = os.path.join(os.path.dirname(pb["para_fname"]), "para_cond.json")
+        cdir = os.path.join(os.path.dirname(pb["para_fname"]), "Cond_Data")
+        os.makedirs(cdir, exist_ok=True)
+        json.dump(dict({k: val for k, val in para.items() if not k.startswith("misfit_w_")}, if_cross_misfit=True, data_dir_name=cdir), open(cond_fname, "w"))
+    return dict(opts=opts, cond_fname=cond_fname, ragged=ragged, counts=counts, weights=weights, G=G, vertical=vertical)
+
+
+# ---- the exact adjoint -------------------------------------------------------------------------------------------------------------
+EXACT_SEED0 = 95400
+MAX_LAYER_CHANNELS = 12
+
+
+def strips(pb):
+    """{name: (rows lo..hi, columns lo..hi)} of the three strips of layer mode, padded cells, inclusive"""
+    nPml, nzc, nx = pb["nPml"], pb["nz_pad"] - pb["nPad"], pb["nx_pad"]
+    half = max(nPml, nzc // 2)
+    return dict(top=((2, nPml - 1), (2, nx - 3)), left=((2, half), (2, nPml - 1)), right=((2, half), (nx - nPml, nx - 3)))
+
+
+def draw_exact(d, b, seed):
+    """Changes the draw (d: draw_problem, b: draw_born) as the docstring of tests/test_gpu_exact_adjoint_fuzz.py says, rewrites its two files and updates b (counts,
+    ragged, weights).  -> dict(layer, cells (padded (z, x) of the layer channels, else None), v_seeds)."""
+    pb, sv = d["pb"], d["sv"]
+    nPml = pb["nPml"]
+    nshots = int(pb["Shot_ids"].numel())
+    rg = np.random.default_rng(EXACT_SEED0 + seed)
+    layer = int(rg.integers(0, 3)) == 0 and not b["G"]
+    m = int(rg.integers(6, MAX_LAYER_CHANNELS + 1))
+    place = [0, 1, 2] + [int(p) for p in rg.integers(0, 3, size=MAX_LAYER_CHANNELS - 3)]
+    u = rg.uniform(size=(MAX_LAYER_CHANNELS, 2))
+    sens = rg.uniform(-1.0, 1.0, (MAX_LAYER_CHANNELS, 3))
+    cu = rg.uniform(size=4)
+    single = int(rg.integers(0, 4)) % nshots
+    v_seeds = [int(s) for s in rg.integers(0, 2 ** 31, size=2)]
+    cells = None
+    if layer:
+        st = strips(pb)
+        cells = []
+        directional = "das_sensitivity" in sv["shot0"]
+        if directional:     # the last channel on the LAST column of the update region: a directional channel reaches column x+1 outside it
+            place[m - 1] = 2
+        for k in range(m):
+            (z0, z1), (x0, x1) = st[("top", "left", "right")[place[k]]]
+            z, x = z0 + int(u[k, 0] * (z1 - z0 + 1)), x0 + int(u[k, 1] * (x1 - x0 + 1))
+            if k == 2:
+                x = pb["nx_pad"] - nPml      # the column inside the x strip of S and outside that of V
+            if directional and k == m - 1:
+                x = pb["nx_pad"] - 3
+            cells.append((min(z, z1), min(x, x1)))
+        counts = [min(m, 1 + int(c * m)) for c in cu[:nshots]]
+        if b["ragged"]:     # (draw_born: more than one shot) a single-channel shot and one with the whole list
+            counts[single], counts[(single + 1) % nshots] = 1, m
+        else:
+            counts = [m] * nshots
+        for k in range(nshots):
+            sh = sv["shot%d" % k]
+            directional = "das_sensitivity" in sh
+            n = counts[k]
+            sh["z_rec"], sh["x_rec"], sh["nrec"] = [int(z - nPml) for z, _ in cells[:n]], [int(x - nPml) for _, x in cells[:n]], n
+            if directional:
+                full = np.zeros((n, 6))
+                full[:, [0, 3, 1]] = sens[:n]
+                sh["das_sensitivity"] = full.tolist()
+        w_vx, w_vz = [born_raw(seed)[0][k] for k in ("w_vx", "w_vz")]
+        para = dict(pb["para"], misfit_w_ett=1.0, misfit_w_vx=w_vx, misfit_w_vz=w_vz)
+        b.update(counts=counts, weights=(1.0, w_vx, w_vz))
+        json.dump(sv, open(pb["survey_fname"], "w"))
+        json.dump(para, open(pb["para_fname"], "w"))
+        pb["para"] = para
+    return dict(layer=layer, cells=cells, v_seeds=v_seeds)
+
+
+def perturbations(d, e):
+    """v and d of that docstring -> two lists of three float32 (nz_pad, nx_pad) arrays"""
+    pb, w = d["pb"], d["water"]
+    v = [B.f32(a + c) for a, c in zip(X.smooth_v(pb, e["v_seeds"][0], w), X.white_v(pb, e["v_seeds"][1], w))]
+    dm = [t.numpy() - i.numpy() for t, i in zip(pb["lame_true"], pb["lame_init"])]
+    dm[1][:int(w)] = 0.0
+    return v, X.on_omega(pb, dm)

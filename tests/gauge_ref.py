@@ -13,6 +13,8 @@ The data-conditioning chain (windows, band-pass, cross-correlation misfit, sourc
 gauge gathers -- not on its members."""
 import numpy as np
 
+from fuzz_common import groups
+
 COND_KEYS = ("if_win", "filter", "if_cross_misfit", "if_src_update")
 
 
@@ -65,14 +67,6 @@ def centre_of(member_gather, G):
     return member_gather.reshape(g, n // ks.size, ks.size, nt)[:, :, int(np.where(ks == 0)[0][0])]
 
 
-def _groups(ids, survey):
-    """The shots of a call in runs the oracle front end can take: all at once when they share nrec, else one at a time."""
-    ids = [int(i) for i in np.asarray(ids).reshape(-1)]
-    if len({int(survey["shot%d" % i]["nrec"]) for i in ids}) <= 1:
-        return [ids]
-    return [[i] for i in ids]
-
-
 def forward(oracle, models, stf, ids, para, survey, G):
     """Member-survey forward pass.  -> per shot of ids (lists, channel counts may differ):  gauge gathers (nrec, nSteps) float64 and
     the (3, nrec, nSteps) float32 pr / vx / vz gathers of the channels' own cells."""
@@ -81,7 +75,7 @@ def forward(oracle, models, stf, ids, para, survey, G):
     msurvey = member_survey(survey, G, vertical)
     lam, mu, den = [np.asarray(m) for m in models]
     gauge, own = [], []
-    for grp in _groups(ids, survey):
+    for grp in groups(ids, survey):
         syn = oracle.cufd(lam, mu, den, np.asarray(stf), 2, np.asarray(grp, np.int32), plain, msurvey)["syn"]
         gg = gauge_of(syn[:, 3], G)
         cc = np.stack([centre_of(syn[:, k], G) for k in range(3)], axis=1)
@@ -132,7 +126,7 @@ def reference(oracle, models, stf, ids, para, survey, G, obs_gauge, cond=None):
         adj.append((w[None, :, None] * a[:, None, :]).reshape(a.shape[0] * w.size, a.shape[1]).astype(np.float32))
     out = None
     pos = 0
-    for grp in _groups(ids, survey):
+    for grp in groups(ids, survey):
         r = oracle.cufd(lam, mu, den, stf, 1, np.asarray(grp, np.int32), plain, msurvey, adj_src=np.stack(adj[pos:pos + len(grp)]))
         pos += len(grp)
         if out is None:

@@ -77,6 +77,41 @@ def make_problem(workdir, nz=44, nx=60, nPml=10, nSteps=240, nshots=2, dh=10.0, 
                 para=json.load(open(para_fname)), survey=json.load(open(survey_fname)))
 
 
+def cond_problem(tmp_path, mode, nshots=2, **kw):
+    """The problem of the data-conditioning modes (tests/test_conditioning.py); kw: further make_problem arguments (tests/test_gpu_das_gauge.py: a vertical fibre)."""
+    pb = make_problem(str(tmp_path), hetero=True, nSteps=300, nshots=nshots, f0=20.0, **kw)
+    para, sv = dict(pb["para"]), dict(pb["survey"])
+    rng = np.random.default_rng(5)
+    if mode in ("filter", "all", "srcupd_all"):
+        para["filter"] = [4.0, 8.0, 35.0, 50.0]
+    if mode in ("cross", "all"):
+        para["if_cross_misfit"] = True
+    if mode in ("srcupd", "srcupd_all"):
+        para["if_src_update"] = True
+    if mode in ("window", "all", "srcupd_all"):
+        para["if_win"] = True
+        for k in range(nshots):
+            sh = dict(sv["shot%d" % k])
+            sh["win_start"] = [float(v) for v in rng.uniform(0.02, 0.08, pb["nrec"])]
+            sh["win_end"] = [float(v) for v in rng.uniform(0.2, 0.29, pb["nrec"])]
+            sh["weights"] = [float(v) for v in rng.uniform(0.5, 1.5, pb["nrec"])]
+            sh["src_weight"] = 1.0 + 0.25 * k
+            sv["shot%d" % k] = sh
+    json.dump(para, open(pb["para_fname"], "w"))
+    json.dump(sv, open(pb["survey_fname"], "w"))
+    pb["para"], pb["survey"] = para, sv
+    return pb
+
+
+def add_water(pb, rows):
+    """A water layer (mu = 0) over the top `rows` rows of both padded models, in place"""
+    for key in ("lame_true", "lame_init"):
+        lam, mu, den = pb[key]
+        lam[:rows, :] = 1000.0 * 1500.0 ** 2 / 1e6
+        mu[:rows, :] = 0.0
+        den[:rows, :] = 1000.0
+
+
 def sustained_source(f0, nSteps, dt, period=0.31):
     """Ricker wavelets (fwi_utils.sourceGene) re-fired every `period` seconds with changing sign and size: keeps the
     wavefield alive over thousands of time steps, so a long run tests more than the decay of one pulse."""

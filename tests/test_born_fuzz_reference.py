@@ -16,25 +16,25 @@ import json
 import numpy as np
 import pytest
 
+import fuzz_common as C
+import fuzz_draws as D
 import gauge_ref as GA
-import problems as P
-import test_gpu_born_fuzz as BF
-import test_gpu_fuzz as F
+from born_ref import COMPS, ROW
+from fuzz_sides import born_oracle_side, describe_born, oracle_gathers
 
-SEEDS = range(16)
-ENV = ("SEPFWI_FUZZ_TWEAK", "SEPFWI_FUZZ_OPTS", "SEPFWI_FUZZ_NOEXTRA", "SEPFWI_FUZZ_DIAG")
+SEEDS = C.DEFAULT_SEEDS
 BORN_DRAWS_DIGEST = "c54b6efe1fb3f38bc775ebbcf0fd200daaa07f2beeb47d82890dd3972ed3463f"
 
 
 def test_born_fuzz_draws_are_what_they_were(tmp_path, monkeypatch):
     """What draw_born adds to the first 16 draws -- options, channel counts, weights, gauge, the conditioned twin -- and the two files it
     rewrites hash to the digest taken when the generator was written: a change of the generator is visible."""
-    for v in ENV:
+    for v in C.ENV:
         monkeypatch.delenv(v, raising=False)
     h = hashlib.sha256()
     for seed in SEEDS:
-        d = F.draw_problem(tmp_path / ("s%d" % seed), seed, 1)
-        b = BF.draw_born(d, seed)
+        d = D.draw_problem(tmp_path / ("s%d" % seed), seed, 1)
+        b = D.draw_born(d, seed)
         h.update(json.dumps(dict(b, cond_fname=bool(b["cond_fname"])), sort_keys=True).encode())
         h.update(json.dumps({k: v for k, v in d["pb"]["para"].items() if k not in ("survey_fname", "data_dir_name", "scratch_dir_name")}, sort_keys=True).encode())
         h.update(json.dumps(json.load(open(d["pb"]["survey_fname"])), sort_keys=True).encode())
@@ -43,22 +43,8 @@ def test_born_fuzz_draws_are_what_they_were(tmp_path, monkeypatch):
 
 @pytest.fixture(scope="module")
 def sides(oracle, oracle_nvfma, tmp_path_factory):
-    """{seed: (oracle_side's dict or None, scale)} of the default seeds, with the re-draw of the GPU test"""
-    import os
-    saved = {v: os.environ.pop(v) for v in ENV if v in os.environ}
-    out = {}
-    try:
-        tmp = tmp_path_factory.mktemp("born_fuzz")
-        for seed in SEEDS:
-            o = None
-            for scale in (1, 2, 4):
-                o = BF.oracle_side(tmp / ("s%d_x%d" % (seed, scale)), oracle, oracle_nvfma, seed, scale)
-                if o is not None:
-                    break
-            out[seed] = (o, scale)
-    finally:
-        os.environ.update(saved)
-    return out
+    """{seed: (born_oracle_side's dict or None, scale)} of the default seeds, with the re-draw of the GPU test"""
+    return C.default_sides(born_oracle_side, tmp_path_factory.mktemp("born_fuzz"), oracle, oracle_nvfma)
 
 
 def test_born_fuzz_draws_have_parity_targets(sides):
@@ -70,7 +56,7 @@ def test_born_fuzz_draws_have_parity_targets(sides):
         o, scale = sides[seed]
         assert o is not None, "seed %d: the wave does not reach the channels" % seed
         b, d = o["b"], o["d"]
-        print("born fuzz seed %d (%s): build spread %.1e, cond_g %.1e, oracle v^T H v / |W^1/2 J v|^2 %.4f" % (seed, BF.describe(o, scale), o["noise_rel"], o["cond_g"], o["ratio"]))
+        print("born fuzz seed %d (%s): build spread %.1e, cond_g %.1e, oracle v^T H v / |W^1/2 J v|^2 %.4f" % (seed, describe_born(o, scale), o["noise_rel"], o["cond_g"], o["ratio"]))
         assert o["target"], (seed, o["noise_rel"], o["cond_g"])
         para = d["pb"]["para"]
         assert not any(k in para for k in GA.COND_KEYS), seed
@@ -88,15 +74,6 @@ def test_born_fuzz_draws_have_parity_targets(sides):
     assert len(structures) >= 4, structures
 
 
-def _oracle_gathers(oracle, m, stf, ids, para, sv):
-    """oracle.cufd(calc_id 2) per shot of ids -> list of (4, nrec, nSteps) float64 (the front end takes one nrec per call)"""
-    out = []
-    for grp in GA._groups([int(i) for i in ids], sv):
-        syn = oracle.cufd(*m, stf, 2, np.asarray(grp, np.int32), para, sv)["syn"].astype(np.float64)
-        out.extend(list(syn))
-    return out
-
-
 def test_born_ref_is_the_derivative_of_the_oracle_s_gathers_on_every_draw(oracle, sides):
     worst = 0.0
     for seed in SEEDS:
@@ -111,16 +88,16 @@ def test_born_ref_is_the_derivative_of_the_oracle_s_gathers_on_every_draw(oracle
         best = {}
         for eps in (1.0, 0.1):
             e = np.float32(eps)
-            hi = _oracle_gathers(oracle, [a + e * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
-            lo = _oracle_gathers(oracle, [a - e * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
-            for c in BF.COMPS:
-                k = BF.ROW[c]
+            hi = oracle_gathers(oracle, [a + e * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
+            lo = oracle_gathers(oracle, [a - e * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
+            for c in COMPS:
+                k = ROW[c]
                 fd = np.concatenate([((p[k] - q[k]) / (2.0 * eps)).ravel() for p, q in zip(hi, lo)])
                 got = np.concatenate([r[k].astype(np.float64).ravel() for r in ref])
                 assert fd.shape == got.shape and np.abs(fd).max() > 0, (seed, c)
-                best[c] = min(best.get(c, np.inf), P.rel_l2(got, fd))
+                best[c] = min(best.get(c, np.inf), C.rel(C.d64(got, fd), fd))
         print("born fuzz seed %2d: born_ref against the finite difference of the oracle's gathers (vx, vz, ett) %s" % (seed, " ".join("%.1e" % best[c] for c in ("vx", "vz", "ett"))))
         worst = max(worst, max(best.values()))
-        for c in BF.COMPS:
+        for c in COMPS:
             assert best[c] <= 1e-2, (seed, c, best[c])
     print("worst %.1e" % worst)

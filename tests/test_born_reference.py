@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 import born_ref as B
+import oracle_loop as OL
 import problems as P
-import pseudo_hessian_ref as R
 
 COMPS = ("pr", "vx", "vz", "ett")
 LADDER = (10.0, 1.0, 0.1, 0.01, 0.001)
@@ -30,38 +30,14 @@ MEASURED = {
 LINEARITY_MEASURED = 4.8e-7
 
 
-def make(tmp, name):
-    """Problem A of the pseudo-Hessian tests, or W: the same with water over the top 12 physical rows (source in the water, fibre below
-    the sea bed, as tests/test_gpu_parity.py::test_water_layer_mu_zero builds it).  -> (problem, first row below the water)."""
-    kw = dict(R.PROBLEM_A)
-    if name == "W":
-        kw.update(src_z=5, rec_z=22)
-    pb = P.make_problem(str(tmp), **kw)
-    w = 0
-    if name == "W":
-        w = pb["nPml"] + 12
-        for key in ("lame_true", "lame_init"):
-            lam, mu, den = pb[key]
-            lam[:w, :] = 1000.0 * 1500.0 ** 2 / 1e6
-            mu[:w, :] = 0.0
-            den[:w, :] = 1000.0
-    return pb, w
-
-
-def perturbation(pb, w, only=None):
-    v = B.perturbation(pb, only=only)
-    v[1][:w] = 0.0      # a fluid stays a fluid: the harmonic mean is not differentiable at mu = 0
-    return v
-
-
 @pytest.fixture(scope="module")
 def setups(oracle, tmp_path_factory):
     out = {}
     for name in ("A", "W"):
-        pb, w = make(tmp_path_factory.mktemp("born_" + name), name)
+        pb, w = B.water_problem(tmp_path_factory.mktemp("born_" + name), name)
         m = [t.numpy() for t in pb["lame_init"]]
         rest = (pb["Stf"].numpy(), pb["Shot_ids"].numpy(), pb["para"], pb["survey"])
-        out[name] = dict(pb=pb, w=w, m=m, rest=rest, v=perturbation(pb, w))
+        out[name] = dict(pb=pb, w=w, m=m, rest=rest, v=B.perturbation(pb, water_rows=w))
         out[name]["ref"] = B.born(oracle, *m, *out[name]["v"], *rest)
     return out
 
@@ -98,7 +74,7 @@ def fd_ladder(oracle, s, v, ladder):
 @pytest.mark.parametrize("name", ["A", "W"])
 def test_scattered_gathers_are_the_derivative_of_the_oracle_s(oracle, setups, name, only):
     s = setups[name]
-    v = s["v"] if only is None else perturbation(s["pb"], s["w"], only)
+    v = s["v"] if only is None else B.perturbation(s["pb"], only=only, water_rows=s["w"])
     ref = s["ref"]["dsyn"] if only is None else B.born(oracle, *s["m"], *v, *s["rest"])["dsyn"]
     fd = fd_ladder(oracle, s, v, LADDER if only is None else LADDER[1:4])
     best = []
@@ -118,7 +94,7 @@ def test_a_dropped_coupling_term_is_an_order_one_error(oracle, setups, only, ter
     """What the finite-difference check must be able to see: without the (lam, mu) / averaged-mu / density term of the parameter's own
     perturbation the gathers are wrong by 0.35 ... 1.0, thousands of times the finite-difference agreement above."""
     s = setups["A"]
-    v = perturbation(s["pb"], s["w"], only)
+    v = B.perturbation(s["pb"], only=only, water_rows=s["w"])
     full = B.born(oracle, *s["m"], *v, *s["rest"])["dsyn"]
     cut = B.born(oracle, *s["m"], *v, *s["rest"], terms=terms)["dsyn"]
     for k in range(4):
@@ -132,8 +108,8 @@ def test_perturbed_media_are_the_derivative_of_the_oracle_s_averages(oracle, set
     s = setups[name]
     pb = s["pb"]
     nz, nx = pb["nz_pad"], pb["nx_pad"]
-    hi = B.internal_media(oracle, *[a + b for a, b in zip(s["m"], s["v"])], nz, nx)
-    lo = B.internal_media(oracle, *[a - b for a, b in zip(s["m"], s["v"])], nz, nx)
+    hi = OL.internal_media(oracle, *[a + b for a, b in zip(s["m"], s["v"])], nz, nx)
+    lo = OL.internal_media(oracle, *[a - b for a, b in zip(s["m"], s["v"])], nz, nx)
     fd = {k: (hi[j].astype(np.float64) - lo[j].astype(np.float64)) / 2.0 for k, j in (("dlam", 0), ("dmu", 1), ("damu", 3), ("dba", 4), ("dbb", 5))}
     for k, got in zip(("dlam", "dmu", "damu", "dba", "dbb"), s["ref"]["dmedia"]):
         err = P.rel_l2(got, fd[k])

@@ -5,36 +5,33 @@ fuzz is for; on the layer draws born_ref is the derivative of the oracle's gathe
 reference's own adjoint misses <W J v, J d> on a layer draw by at least 5 x the tolerance."""
 import hashlib
 import json
-import os
 
 import numpy as np
 import pytest
 
 import exact_adjoint_ref as X
-import problems as P
-import test_born_fuzz_reference as BR
-import test_gpu_born_fuzz as BF
-import test_gpu_exact_adjoint_fuzz as EF
-import test_gpu_fuzz as F
+import fuzz_common as C
+import fuzz_draws as D
+from born_ref import COMPS, GRADS, ROW, shifted_gradient
+from fuzz_sides import channel_peaks, describe_exact, exact_oracle_side, oracle_gathers
 
-SEEDS = range(16)
-ENV = BR.ENV
+SEEDS = C.DEFAULT_SEEDS
 EXACT_DRAWS_DIGEST = "9bb263de52c84a96bc52f061cdadf7ce736d4fe53a17f665ef819449283953c3"
 
 
 def test_exact_fuzz_draws_are_what_they_were(tmp_path, monkeypatch):
     """What draw_exact adds to the first 16 draws -- layer mode and its cells, the seeds of v, the counts and weights it changes in
-    draw_born's dict -- and the two files it rewrites hash to the digest taken when the generator was written.  draw_born's own weights
-    are replayed, not returned: where draw_born uses them they must be the same."""
-    for v in ENV:
+    draw_born's dict -- and the two files it rewrites hash to the digest taken when the generator was written.  The weights of a layer draw
+    are draw_born's own (fuzz_draws.born_raw): where draw_born uses them they must be the same."""
+    for v in C.ENV:
         monkeypatch.delenv(v, raising=False)
     h = hashlib.sha256()
     for seed in SEEDS:
-        d = F.draw_problem(tmp_path / ("s%d" % seed), seed, 1)
-        b = BF.draw_born(d, seed)
+        d = D.draw_problem(tmp_path / ("s%d" % seed), seed, 1)
+        b = D.draw_born(d, seed)
         if b["weights"]:
-            assert tuple(b["weights"][1:]) == EF.born_weights(seed), seed
-        e = EF.draw_exact(d, b, seed)
+            assert tuple(b["weights"][1:]) == tuple(D.born_raw(seed)[0][k] for k in ("w_vx", "w_vz")), seed
+        e = D.draw_exact(d, b, seed)
         h.update(json.dumps(e, sort_keys=True).encode())
         h.update(json.dumps(dict(b, cond_fname=bool(b["cond_fname"])), sort_keys=True).encode())
         h.update(json.dumps({k: v for k, v in d["pb"]["para"].items() if k not in ("survey_fname", "data_dir_name", "scratch_dir_name")}, sort_keys=True).encode())
@@ -44,25 +41,12 @@ def test_exact_fuzz_draws_are_what_they_were(tmp_path, monkeypatch):
 
 @pytest.fixture(scope="module")
 def sides(oracle, oracle_nvfma, tmp_path_factory):
-    """{seed: (oracle_side's dict or None, scale)} of the default seeds, with the re-draw of the GPU test"""
-    saved = {v: os.environ.pop(v) for v in ENV if v in os.environ}
-    out = {}
-    try:
-        tmp = tmp_path_factory.mktemp("exact_fuzz")
-        for seed in SEEDS:
-            o = None
-            for scale in (1, 2, 4):
-                o = EF.oracle_side(tmp / ("s%d_x%d" % (seed, scale)), oracle, oracle_nvfma, seed, scale)
-                if o is not None:
-                    break
-            out[seed] = (o, scale)
-    finally:
-        os.environ.update(saved)
-    return out
+    """{seed: (exact_oracle_side's dict or None, scale)} of the default seeds, with the re-draw of the GPU test"""
+    return C.default_sides(exact_oracle_side, tmp_path_factory.mktemp("exact_fuzz"), oracle, oracle_nvfma)
 
 
 def _strip_of(pb, z, x):
-    for name, ((z0, z1), (x0, x1)) in EF.strips(pb).items():
+    for name, ((z0, z1), (x0, x1)) in D.strips(pb).items():
         if z0 <= z <= z1 and x0 <= x <= x1:
             yield name
 
@@ -77,7 +61,7 @@ def test_exact_fuzz_draws_have_targets_and_cover_what_the_fuzz_is_for(sides):
         b, d, e, ref = o["b"], o["d"], o["e"], o["ref"]
         pb = d["pb"]
         print("exact fuzz seed %d (%s): build spread %r, cond_g %.1e, cos(W^1/2 J d, W^1/2 r) %.3f, cos(J v, J d) %.3f"
-              % (seed, EF.describe(o, scale), {k: "%.1e" % y for k, y in o["yard"].items()}, o["cond_g"], ref["cos_dr"],
+              % (seed, describe_exact(o, scale), {k: "%.1e" % y for k, y in o["yard"].items()}, o["cond_g"], ref["cos_dr"],
                  ref["vw"] / o["cmp"]["<v,JTw>"][2]))
         assert o["target"], (seed, o["yard"], o["cond_g"])
         assert ref["cos_dr"] >= 0.5, (seed, ref["cos_dr"])
@@ -103,8 +87,8 @@ def test_exact_fuzz_draws_have_targets_and_cover_what_the_fuzz_is_for(sides):
                 count["directional layer"] += 1
             count["edge"] += any(z == 2 or x == 2 for z, x in e["cells"])      # a channel that reaches row or column 1
             # every channel is alive: its own peak (over the shots that hold it) against the largest, per weighted component
-            peaks = EF.channel_peaks(ref["syn"], b)
-            for c in EF.COMPS:
+            peaks = channel_peaks(ref["syn"], b)
+            for c in COMPS:
                 print("    %s peaks / largest: %s" % (c, " ".join("%.1e" % peaks[(c, ch)] for ch in range(len(e["cells"])))))
             assert min(peaks.values()) >= 1e-3, (seed, peaks)
         if b["ragged"]:
@@ -134,15 +118,15 @@ def test_born_ref_is_the_derivative_of_the_oracle_s_gathers_in_the_layers(oracle
         best = {}
         for eps in (1.0, 0.1):
             s = np.float32(eps)
-            hi = BR._oracle_gathers(oracle, [a + s * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
-            lo = BR._oracle_gathers(oracle, [a - s * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
+            hi = oracle_gathers(oracle, [a + s * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
+            lo = oracle_gathers(oracle, [a - s * c for a, c in zip(o["m"], o["v"])], stf, ids, para, sv)
             for i, (p, q, r) in enumerate(zip(hi, lo, ref)):
-                for c in EF.COMPS:
-                    k = BF.ROW[c]
+                for c in COMPS:
+                    k = ROW[c]
                     fd = (p[k] - q[k]) / (2.0 * eps)
                     for ch in range(fd.shape[0]):
                         assert np.abs(fd[ch]).max() > 0, (seed, i, c, ch)
-                        best[(i, c, ch)] = min(best.get((i, c, ch), np.inf), P.rel_l2(r[k][ch].astype(np.float64), fd[ch]))
+                        best[(i, c, ch)] = min(best.get((i, c, ch), np.inf), C.rel(C.d64(r[k][ch], fd[ch]), fd[ch]))
         print("exact fuzz seed %2d: born_ref against the finite difference of the oracle's gathers, worst channel %.1e, median %.1e"
               % (seed, max(best.values()), float(np.median(list(best.values())))))
         worst = max(worst, max(best.values()))
@@ -161,8 +145,8 @@ def test_the_reference_adjoint_misses_the_cross_product_on_a_layer_draw(oracle, 
         if o is None or not o["e"]["layer"]:
             continue
         pb, sv, b, ref = o["d"]["pb"], o["d"]["sv"], o["b"], o["ref"]
-        g = BF.shifted_gradient(oracle, pb, sv, b, o["m"], ref["syn"], ref["jd"])
+        g = shifted_gradient(oracle, pb, sv, b, o["m"], ref["syn"], ref["jd"])
         r, _, s = o["cmp"]["<v,JTw>"]
-        misses[seed] = abs(X.model_dot(o["v"], [g[k] for k in BF.GRADS]) - r) / s
+        misses[seed] = abs(X.model_dot(o["v"], [g[k] for k in GRADS]) - r) / s
         print("exact fuzz seed %d: the reference's adjoint misses <W J v, J d> by %.2e of |W^1/2 J v| |W^1/2 J d|" % (seed, misses[seed]))
     assert misses and max(misses.values()) >= 5.0 * X.TOL, misses

@@ -18,8 +18,7 @@ import pytest
 import exact_adjoint_ref as X
 import problems as P
 import pseudo_hessian_ref as R
-import test_gpu_born_fuzz as BF
-import test_gpu_exact_adjoint as G
+from born_ref import GRADS, born_side, shifted_gradient
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,15 +37,15 @@ def test_omega_is_the_interior_without_its_first_row_and_column(prob_a):
     assert m.sum() == (pb["nz_pad"] - nPad - 2 * nPml - 1) * (pb["nx_pad"] - 2 * nPml - 1)
     assert m[nPml + 1, nPml + 1] and not m[nPml, nPml + 1] and not m[nPml + 1, nPml] and m[pb["nz_pad"] - nPad - nPml - 1, pb["nx_pad"] - nPml - 1]
     assert all(np.abs(a[m]).max() > 0 and not np.any(a[~m]) for v in vs for a in v)
-    assert all(m[z, x] for _, z, x in G.PROBE_CELLS)
-    assert max(z for _, z, _ in G.PROBE_CELLS) <= nPml + 30
+    assert all(m[z, x] for _, z, x in X.PROBE_CELLS)
+    assert max(z for _, z, _ in X.PROBE_CELLS) <= nPml + 30
 
 
 def test_the_pairs_of_the_gpu_tests_are_neither_parallel_nor_orthogonal(prob_a):
     _, _, jv = prob_a
     for k, c in enumerate(X.COMPS):     # (printed: vz alone is not a pair any GPU test uses)
         print("cos(J v1, J v2), %s alone: %.3f" % (c, X.cosine(jv[0], jv[1], [float(j == k) for j in range(3)])))
-    for weights in G.WEIGHTS:
+    for weights in X.WEIGHTS:
         cos = X.cosine(jv[0], jv[1], weights)
         print("cos(W^1/2 J v1, W^1/2 J v2), weights %r: %.3f" % (weights, cos))
         assert 0.1 <= abs(cos) <= 0.9, (weights, cos)
@@ -57,9 +56,9 @@ def test_the_reference_adjoint_misses_the_norm_by_more_than_the_tolerance(oracle
     pb, vs, _ = prob_a
     b = dict(G=0, vertical=False, weights=None)
     m = [t.numpy() for t in pb["lame_init"]]
-    syn, dsyn, _ = BF.born_side(oracle, pb, pb["survey"], b, m, vs[0])
-    ref = BF.shifted_gradient(oracle, pb, pb["survey"], b, m, syn, dsyn)
-    vhv = X.model_dot(vs[0], [ref[k] for k in BF.GRADS])
+    syn, dsyn, _ = born_side(oracle, pb, pb["survey"], b, m, vs[0])
+    ref = shifted_gradient(oracle, pb, pb["survey"], b, m, syn, dsyn)
+    vhv = X.model_dot(vs[0], [ref[k] for k in GRADS])
     miss = abs(vhv / ref["jv2"] - 1.0)
     print("the reference's adjoint on v masked to Omega: v^T H v / |J v|^2 = %.5f (misses by %.2e)" % (vhv / ref["jv2"], miss))
     assert miss >= 5.0 * X.TOL, miss
@@ -70,7 +69,7 @@ def test_probe_cells_are_reached_by_the_wave(oracle, prob_a):
     norms = []
     for param in range(3):
         scale = 0.01 * float(np.abs(pb["lame_init"][param].numpy()).mean())
-        norms.append(X.probe_dots(oracle, pb, param, G.PROBE_CELLS, None, scale=scale, norms=True))
+        norms.append(X.probe_dots(oracle, pb, param, X.PROBE_CELLS, None, scale=scale, norms=True))
         print("|J e_k| of parameter %d at the probe cells: %s" % (param, " ".join("%.2e" % n for n in norms[-1])))
         assert np.all(norms[-1] > 1e-6 * norms[-1].max()), (param, norms[-1])
     far = X.probe_dots(oracle, pb, 0, [(0, 59, 99)], None, scale=0.01 * float(np.abs(pb["lame_init"][0].numpy()).mean()), norms=True)[0]

@@ -2,15 +2,17 @@
 adjoint-source hook is the oracle's residual path, a one-cell gauge is the plain oracle, the member-survey gradient is the gradient of
 the gauge misfit (finite differences), the refactored fuzz draws are what they were, and every default seed of the gauge fuzz
 (tests/test_gpu_gauge_fuzz.py) has a parity target and the 16 between them cover the draw space."""
-import contextlib
 import hashlib
 import json
 
 import numpy as np
 import pytest
 
+import fuzz_common as C
+import fuzz_draws as D
 import gauge_ref as R
 import problems as P
+from fuzz_sides import gauge_oracle_side
 
 
 def _problem(tmp_path, **kw):
@@ -133,55 +135,30 @@ FUZZ_DRAWS_DIGEST = "a9dddcb0733c30ac13c0eae4234f8917a34601c66d66ca4a2fac2976e90
 
 
 def test_fuzz_draws_are_what_they_were(tmp_path, monkeypatch):
-    """tests/test_gpu_fuzz.py's drawing part is a function of its own now (draw_problem, shared with the gauge fuzz): what _attempt hands
-    to its first oracle call -- models, source function, shots, parameter file, survey -- and its kernel options, seeds 0 ... 15, hash to
-    the digest taken from the file before it was refactored."""
-    import test_gpu_fuzz as F
-    h = hashlib.sha256()
-    seen = {}
-
-    class Stop(Exception):
-        pass
-
-    class FakeOracle:
-        @staticmethod
-        def cufd(lam, mu, den, stf, calc_id, ids, para, sv, **kw):
-            for a in (lam, mu, den, stf, ids):
-                h.update(np.ascontiguousarray(a).tobytes())
-            h.update(json.dumps({k: v for k, v in para.items() if k not in ("survey_fname", "data_dir_name", "scratch_dir_name")}, sort_keys=True).encode())
-            h.update(json.dumps(sv, sort_keys=True).encode())
-            h.update(json.dumps(seen["opts"], sort_keys=True).encode())
-            raise Stop()
-
-    @contextlib.contextmanager
-    def fake_options(**opts):
-        seen["opts"] = opts
-        yield
-
-    monkeypatch.setattr(P, "kernel_options", fake_options)
-    for v in ("SEPFWI_FUZZ_TWEAK", "SEPFWI_FUZZ_OPTS", "SEPFWI_FUZZ_NOEXTRA", "SEPFWI_FUZZ_DIAG"):
+    """What tests/test_gpu_fuzz.py hands to its first oracle call -- the observed model, source function, shots, parameter file, survey of
+    fuzz_draws.draw_problem -- and its kernel options, seeds 0 ... 15, hash to the digest taken from that file before its drawing part
+    became a function of its own."""
+    for v in C.ENV:
         monkeypatch.delenv(v, raising=False)
+    h = hashlib.sha256()
     for seed in range(16):
-        with pytest.raises(Stop):
-            F._attempt(tmp_path / ("s%d" % seed), FakeOracle, None, None, seed, 1)
+        d = D.draw_problem(tmp_path / ("s%d" % seed), seed, 1)
+        pb = d["pb"]
+        for a in [t.numpy() for t in D.observed_model(pb)] + [pb["Stf"].numpy(), pb["Shot_ids"].numpy()]:
+            h.update(np.ascontiguousarray(a).tobytes())
+        h.update(json.dumps({k: v for k, v in pb["para"].items() if k not in ("survey_fname", "data_dir_name", "scratch_dir_name")}, sort_keys=True).encode())
+        h.update(json.dumps(d["sv"], sort_keys=True).encode())
+        h.update(json.dumps(d["opts"], sort_keys=True).encode())
     assert h.hexdigest() == FUZZ_DRAWS_DIGEST
 
 
-def test_gauge_fuzz_draws_have_parity_targets(tmp_path, oracle, oracle_nvfma, monkeypatch):
+def test_gauge_fuzz_draws_have_parity_targets(tmp_path, oracle, oracle_nvfma):
     """The default seeds of test_random_problem_matches_oracle_with_gauge, oracle side only: NONE lacks a parity target (signal at the
     channels with the record at scale 1, 2 or 4; the two oracle builds within 1e-2 of each other; conditioning term <= 1e-2), and the
     16 draws between them contain every axis / kind, odd and even G, an overlapping line, a ragged shot list, a bound-touching channel,
     a conditioned draw and a water layer."""
-    import test_gpu_gauge_fuzz as GF
-    for v in ("SEPFWI_FUZZ_TWEAK", "SEPFWI_FUZZ_OPTS", "SEPFWI_FUZZ_NOEXTRA"):
-        monkeypatch.delenv(v, raising=False)
     seen = set()
-    for seed in range(16):
-        o = None
-        for scale in (1, 2, 4):
-            o = GF.oracle_side(tmp_path / ("s%d_x%d" % (seed, scale)), oracle, oracle_nvfma, seed, scale)
-            if o is not None:
-                break
+    for seed, (o, scale) in C.default_sides(gauge_oracle_side, tmp_path, oracle, oracle_nvfma).items():
         assert o is not None, "seed %d: the wave does not reach the channels" % seed
         g = o["g"]
         print("gauge fuzz seed %d: %s G %d %s ragged %r touch %r conditioned %r water %d scale %d noise %.1e cond %.1e"
@@ -191,5 +168,5 @@ def test_gauge_fuzz_draws_have_parity_targets(tmp_path, oracle, oracle_nvfma, mo
         seen.update(name for name, on in (("ragged", g["ragged"]), ("touch", g["touch"]), ("conditioned", o["conditioned"]), ("water", o["d"]["water"])) if on)
         if g["ragged"]:
             assert 1 in g["counts"] and len(set(g["counts"])) > 1
-    want = set(GF.MODES) | {"odd", "even", "overlapping line", "ragged", "touch", "conditioned", "water"}
+    want = set(D.MODES) | {"odd", "even", "overlapping line", "ragged", "touch", "conditioned", "water"}
     assert want <= seen, sorted(want - seen)

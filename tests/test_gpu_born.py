@@ -8,35 +8,24 @@ derivative several 1e-2 (tests/test_born_reference.py).
 
 Measured on the MI355X (profiles/r09_born.txt): see the prints of each test."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import born_ref as B
+import fuzz_common as FC
 import problems as P
 import pseudo_hessian_ref as R
+from born_ref import COMPS, GRADS, ROW, born_side, shifted_gradient
+from fuzz_common import write_para
 from gauge_ref import gauge_of, member_survey
 from sepfwi import utils as ft
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-COMPS = ("ett", "vx", "vz")
-ROW = {"ett": 3, "vx": 1, "vz": 2}      # row of the component in the reference's gathers [pr, vx, vz, ett]
 PROBLEM_B3 = dict(R.PROBLEM_B, nshots=3)    # 40 x 150, three row segments, three Born shots in a row in one session
 LINEARITY_REF = 4.8e-7                      # born_ref(2 v) against 2 born_ref(v), tests/test_born_reference.py
-
-
-def write_para(pb, name, **keys):
-    """A parameter file next to pb's (a session of its own): same grid and survey, data directory <name>_Data, extra / changed keys."""
-    para = dict(pb["para"], data_dir_name=os.path.join(os.path.dirname(pb["para_fname"]), name + "_Data"), **keys)
-    os.makedirs(para["data_dir_name"], exist_ok=True)
-    fn = os.path.join(os.path.dirname(pb["para_fname"]), name + ".json")
-    with open(fn, "w") as fp:
-        json.dump(para, fp)
-    return fn, para
 
 
 def gpu_born(hip_ops, pb, v, para_fname=None, ids=None, components=COMPS):
@@ -279,28 +268,23 @@ def test_refusals_are_error_codes(tmp_path, hip_ops):
 # ---- water, kernel structures, the pseudo-Hessian, img_every --------------------------------------------------------------------
 def product_against_the_oracle(oracle, oracle_nvfma, pb, v, hv, water, tag):
     """hv (three numpy arrays) against the oracle's gradient at obs = syn - J v formed from born_ref on the CPU, on both oracle builds:
-    the bound and the yardstick of tests/test_gpu_born_fuzz.py (those of tests/test_gpu_fuzz.py)."""
-    import test_gpu_born_fuzz as BF
+    the bound and the yardstick of tests/test_gpu_born_fuzz.py (tests/fuzz_common.py)."""
     b = dict(G=0, vertical=False, weights=None)
     m = [t.numpy() for t in pb["lame_init"]]
     sides = []
     for lib in (oracle, oracle_nvfma):
-        syn, dsyn, _ = BF.born_side(lib, pb, pb["survey"], b, m, v)
-        sides.append(BF.shifted_gradient(lib, pb, pb["survey"], b, m, syn, dsyn))
+        syn, dsyn, _ = born_side(lib, pb, pb["survey"], b, m, v)
+        sides.append(shifted_gradient(lib, pb, pb["survey"], b, m, syn, dsyn))
     ref, alt = sides
-    cond_g = 4.0 * 2.0 ** -24 * float(np.sqrt(ref["E"] / ref["misfit"]))
-    l2 = lambda a: float(np.linalg.norm(np.asarray(a, np.float64)))
-    for name, g in zip(BF.GRADS, hv):
+    cond_g = FC.conditioning(ref["E"], ref["misfit"])[1]
+    for name, g in zip(GRADS, hv):
         r, a = ref[name], alt[name]
         print("gauss-newton %s hv%s: rel-L2 deviation from the oracle's gradient at obs = syn - J v %.2e (the two oracle builds %.2e, cond_g %.1e)"
-              % (tag, name[1:], l2(g - r) / l2(r), l2(a - r) / l2(r), cond_g))
-    for name, g in zip(BF.GRADS, hv):
-        r, a = ref[name], alt[name]
-        assert np.isfinite(g).all() and l2(r) > 0, (tag, name)
-        assert l2(g - r) <= (1e-3 + cond_g) * l2(r) + 3.0 * l2(a - r), (tag, name)
-        if water:   # below a water layer the image is held on its own (against the larger of its own norm and 3 % of the whole image's)
-            yard = max(l2(r[water:]), 3e-2 * l2(r))
-            assert l2(g[water:] - r[water:]) <= (1e-3 + cond_g) * yard + 3.0 * l2(a[water:] - r[water:]), (tag, name, "below the water")
+              % (tag, name[1:], FC.rel(FC.d_own(g, r), r), FC.rel(FC.d_own(a, r), r), cond_g))
+    for name, g in zip(GRADS, hv):
+        assert np.isfinite(g).all() and FC.l2(ref[name]) > 0, (tag, name)
+        miss = FC.gradient_miss(g, ref[name], alt[name], FC.GRAD_TOL, cond_g, water, FC.d_own)
+        assert not miss, (tag, name, miss)
 
 
 def test_water_layer_50x90(tmp_path, oracle, oracle_nvfma, hip_ops):
@@ -308,9 +292,8 @@ def test_water_layer_50x90(tmp_path, oracle, oracle_nvfma, hip_ops):
     bed; dMu = 0 in the water.  The gathers against the reference; the scattered sxz is exactly 0 wherever one of the four mu taps of
     its average is a fluid cell (the am != 0 guard of k_born_media next to the average rebuilt on the fly); the product against the
     oracle's gradient at shifted data."""
-    import test_born_reference as TB
-    pb, w = TB.make(tmp_path, "W")
-    v = TB.perturbation(pb, w)
+    pb, w = B.water_problem(tmp_path, "W")
+    v = B.perturbation(pb, water_rows=w)
     hip_ops.release()
     close(gpu_born(hip_ops, pb, v), ref_born(oracle, pb, v), "50x90 water")
     sxz = hip_ops.debug_field(pb["para_fname"], 14).numpy()

@@ -12,6 +12,7 @@ import torch
 
 import problems as P
 import gauge_ref as R
+from fuzz_common import write_para
 from gauge_ref import gauge_of, member_survey, members
 from sepfwi import _native
 from sepfwi import utils as ft
@@ -20,16 +21,6 @@ pytestmark = pytest.mark.gpu
 
 GRAD_TOL = 1e-3
 CASES = {"horizontal-3": ("horizontal", 3), "horizontal-4": ("horizontal", 4), "vertical-3": ("vertical", 3), "directional-2": ("directional", 2)}
-
-
-def write_para(pb, name, **keys):
-    """A parameter file next to pb's: same grid and survey, data directory <name>_Data, extra / changed keys."""
-    para = dict(pb["para"], data_dir_name=os.path.join(os.path.dirname(pb["para_fname"]), name + "_Data"), **keys)
-    os.makedirs(para["data_dir_name"], exist_ok=True)
-    fn = os.path.join(os.path.dirname(pb["para_fname"]), name + ".json")
-    with open(fn, "w") as fp:
-        json.dump(para, fp)
-    return fn, para
 
 
 def gauge_problem(tmp_path, fiber, G, nshots=2, **kw):
@@ -232,9 +223,8 @@ def test_gauge_conditioning_matches_oracle(tmp_path, oracle, oracle_nvfma, hip_o
     problem, its keys, its tolerances and its gStf yardstick) with G = 3 on a horizontal and G = 4 on a vertical fibre, against
     gauge_ref.reference -- windows, band-pass, cross-correlation misfit and source update act on the GAUGE gathers, and member j of
     channel c is handed w_j times the conditioned adjoint source of c."""
-    from test_conditioning import _cond_problem
     fiber, G = COND_GAUGES[gauge]
-    pb = _cond_problem(tmp_path, mode, **(dict(das_fiber="vertical") if fiber == "vertical" else {}))
+    pb = P.cond_problem(tmp_path, mode, **(dict(das_fiber="vertical") if fiber == "vertical" else {}))
     para, sv = pb["para"], pb["survey"]
     para["das_gauge_length"] = G * (para["dz"] if fiber == "vertical" else para["dx"])
     json.dump(para, open(pb["para_fname"], "w"))

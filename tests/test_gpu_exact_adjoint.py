@@ -3,7 +3,7 @@ fwi_ops.gauss_newton(exact=True) / born_adjoint / backward(exact_adjoint=True), 
 (tests/exact_adjoint_ref.py: <J_ref v, w> in float64, nothing on the adjoint side restated).
 
 Tolerance, none new: the suite's gradient tolerance 1e-3, relative, plus 3 x the difference of the same reference quantity between the two
-oracle builds (plain and nvfma), the yardstick of tests/test_gpu_born_fuzz.py for float32 rounding:
+oracle builds (plain and nvfma), the yardstick of tests/fuzz_common.py for float32 rounding:
     |got - ref| <= 1e-3 |ref| + 3 |alt - ref|
 Every dot product is accumulated in float64 on the host.  Each comparison prints its deviation before it asserts
 (profiles/r11_exact_adjoint.txt holds the figures measured on the MI355X).  The problems here are hand-picked;
@@ -13,41 +13,25 @@ channel counts with the caller's w, w in host memory, joint and gauge misfits).
 Every test fails on the parent (the entry point is missing); 1, 3, 4 and 6 would also fail on the parent's adjoint if it were merely
 re-exported: v^T H v / |W^1/2 J v|^2 reads 0.9923 and 0.9844 there on the fixed problems, residual column nSteps-1 is dropped."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-import born_ref as B
 import exact_adjoint_ref as X
 import problems as P
 import pseudo_hessian_ref as R
+from exact_adjoint_ref import PROBE_CELLS, WEIGHTS, capi, cuda, held, outside_is_zero
+from fuzz_common import write_para
 from gauge_ref import gauge_of, member_survey
 
 pytestmark = pytest.mark.gpu
 TOL = X.TOL
 COMPS = X.COMPS
-WEIGHTS = [(1.0, 0.0, 0.0), (1.0, 0.5, 0.25)]
-
-
-def write_para(pb, name, **keys):
-    """A parameter file next to pb's (a session of its own): same grid and survey, data directory <name>_Data, extra / changed keys."""
-    para = dict(pb["para"], data_dir_name=os.path.join(os.path.dirname(pb["para_fname"]), name + "_Data"), **keys)
-    os.makedirs(para["data_dir_name"], exist_ok=True)
-    fn = os.path.join(os.path.dirname(pb["para_fname"]), name + ".json")
-    with open(fn, "w") as fp:
-        json.dump(para, fp)
-    return fn, para
 
 
 def weight_keys(w):
     return {} if w == (1.0, 0.0, 0.0) else dict(misfit_w_ett=w[0], misfit_w_vx=w[1], misfit_w_vz=w[2])
-
-
-def cuda(arrs):
-    return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda() for a in arrs]
 
 
 def gn(hip_ops, pb, v, fn=None, exact=True, ids=None):
@@ -67,22 +51,6 @@ def jtw(hip_ops, pb, w, fn=None, ids=None):
     per_shot = [{c: torch.from_numpy(np.ascontiguousarray(a[i], dtype=np.float32)) for c, a in w.items()} for i in range(int(ids.numel()))]
     g = hip_ops.born_adjoint(*[t.cuda() for t in pb["lame_init"]], per_shot, pb["Stf"], 1, ids, fn or pb["para_fname"])
     return [a.cpu().numpy() for a in g]
-
-
-def held(got, ref, alt, what, scale=None):
-    """|got - ref| <= 1e-3 scale + 3 |alt - ref|  (scale: |ref| unless given); prints the deviation first"""
-    scale = abs(ref) if scale is None else scale
-    dev, yard = abs(got - ref), abs(alt - ref)
-    print("exact adjoint %s: got %.8e, reference %.8e, deviation %.2e of the scale (the two oracle builds %.2e)"
-          % (what, got, ref, dev / max(scale, 1e-300), yard / max(scale, 1e-300)))
-    assert np.isfinite(got) and dev <= TOL * scale + 3.0 * yard, (what, got, ref, dev / max(scale, 1e-300), yard / max(scale, 1e-300))
-
-
-def outside_is_zero(pb, g, what):
-    m = X.mask_omega(pb)
-    for a in g:
-        assert np.isfinite(a).all() and not np.any(a[~m]), what
-    assert all(np.abs(a[m]).max() > 0 for a in g), what
 
 
 @pytest.fixture(scope="module")
@@ -125,11 +93,6 @@ def test_gauss_newton_product_is_symmetric_and_equals_the_norm_of_jv(hip_ops, pr
     ratio = X.model_dot(vs[0], old) / X.data_dot(ref[0], ref[0], weights)
     print("exact adjoint 1 %s: the reference's adjoint on the same v: v^T H v / |W^1/2 J v|^2 = %.4f (exact: %.6f)"
           % (tag, ratio, vhv[0] / X.data_dot(ref[0], ref[0], weights)))
-
-
-PROBE_CELLS = [(0, 11, 40), (0, 30, 11), (1, 35, 99), (0, 13, 17), (0, 39, 50), (0, 38, 60), (0, 25, 45), (0, 25, 46)]
-# (shot, row, column) of the padded 50 x 90 grid: Omega's first row, first column, last column (seen from shot 1: the wave of shot 0 does
-# not reach it within the record); diagonal to the source of shot 0 (12, 16); next to the fibre row (40); one deep; an adjacent pair
 
 
 @pytest.mark.parametrize("param", [0, 1, 2])
@@ -292,21 +255,6 @@ def test_kernel_structures(probes_lib, hip_ops, prob_a):
         held(X.model_dot(vs[0], hv), r, a, "7 %r" % (opts,))
         if "rho_fly" not in opts and "amu_fly" not in opts:
             assert all(np.array_equal(x, y) for x, y in zip(hv, base)), opts
-
-
-def capi(pb, fn, model, v=None, w=None, host_out=False):
-    from sepfwi import _native
-    L = _native.lib()
-    shape = (pb["nz_pad"], pb["nx_pad"])
-    g = [np.zeros(shape, np.float32) for _ in range(3)] if host_out else [torch.zeros(shape, dtype=torch.float32, device="cuda") for _ in range(3)]
-    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
-    stf = np.ascontiguousarray(pb["Stf"].numpy(), dtype=np.float32)
-    ids = np.ascontiguousarray(pb["Shot_ids"].numpy(), dtype=np.int32)
-    torch.cuda.synchronize()
-    rc = L.sepfwi_adjoint_exact(None, *[ptr(a) for a in g], *[ptr(a) for a in (w or [None] * 3)], *[ptr(a) for a in (v or [None] * 3)],
-                                *[ptr(a) for a in model], ptr(stf), 0, int(ids.size), C.c_void_p(ids.ctypes.data), fn.encode(), None)
-    torch.cuda.synchronize()
-    return rc, [a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in g]
 
 
 def test_a_grid_of_loop_size(tmp_path, hip_ops):

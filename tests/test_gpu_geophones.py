@@ -5,13 +5,14 @@ The oracle's driver injects the axial strain only; the reference here is tests/g
 over its exported kernels with the geophone adds (pinned to the oracle bit for bit by tests/test_geophone_reference.py).
 Tolerances: the suite's -- misfit rtol 1e-4, gradients and gStf rel-L2 <= 1e-3 and max-norm <= 1e-3 max|g|."""
 import ctypes as C
-import json
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import fuzz_common as FC
 import geophone_ref as G
 import problems as P
 from sepfwi import _native
@@ -25,18 +26,7 @@ WEIGHTS = {"vx": (0.0, 1.0, 0.0), "vz": (0.0, 0.0, 1.0), "joint": (1.0, 0.5, 2.0
 FIBERS = {"horizontal": {}, "vertical": dict(das_fiber="vertical"), "directional": dict(das_sensitivity="random", nrec_stride=2)}
 
 
-def write_para(pb, name, weights=None, data_dir=None, **keys):
-    """A parameter file next to pb's: same grid and survey, pb's data directory unless another is named, the weight keys, extra keys."""
-    para = dict(pb["para"], **keys)
-    if weights is not None:
-        para.update(misfit_w_ett=weights[0], misfit_w_vx=weights[1], misfit_w_vz=weights[2])
-    if data_dir is not None:
-        para["data_dir_name"] = os.path.join(os.path.dirname(pb["para_fname"]), data_dir)
-        os.makedirs(para["data_dir_name"], exist_ok=True)
-    fn = os.path.join(os.path.dirname(pb["para_fname"]), name + ".json")
-    with open(fn, "w") as fp:
-        json.dump(para, fp)
-    return fn, para
+write_para = functools.partial(FC.write_para, data_dir=None)      # pb's own data directory unless another is named
 
 
 def write_obs(data_dir, ids, obs, comps=COMPS):

@@ -28,7 +28,7 @@ def live():
     return d.value, p.value
 
 
-def write_para(pb, **keys):
+def rewrite_para(pb, **keys):
     para = dict(pb["para"], **keys)
     with open(pb["para_fname"], "w") as fp:
         json.dump(para, fp)
@@ -56,7 +56,7 @@ def test_a_refused_session_holds_nothing(tmp_path, hip_ops):
     hip_ops.release()
     base = live()
     pb = P.make_problem(str(tmp_path / "here"), nz=60, nx=80, nPml=10, nSteps=50, nshots=1, hetero=False)
-    write_para(pb, das_gauge_length=310.0)
+    rewrite_para(pb, das_gauge_length=310.0)
     lt, mt, dt_ = pb["lame_true"]
     with pytest.raises(_native.SepFwiError) as e:
         hip_ops.obscalc(lt, mt, dt_, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
@@ -64,7 +64,7 @@ def test_a_refused_session_holds_nothing(tmp_path, hip_ops):
     after = live()
     print("live bytes after the refused session: device %+d, pinned %+d" % (after[0] - base[0], after[1] - base[1]))
     assert after == base
-    write_para(pb)
+    rewrite_para(pb)
     hip_ops.obscalc(lt, mt, dt_, pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
     lam, mu, den = pb["lame_init"]
     got = hip_ops.forward((lam * 1.05).contiguous(), mu, den, pb["Stf"], 0, pb["Shot_ids"], pb["para_fname"])[0].numpy().tobytes().hex()
@@ -137,7 +137,7 @@ def test_every_session_gives_everything_back(tmp_path, hip_ops, probes_lib):
 
     # a gauge length, in both schedules (taps, adjoint plan; the batched schedule's side table)
     pb = P.make_problem(str(tmp_path / "gauge"), nz=60, nx=80, nPml=10, nSteps=50, nshots=2, hetero=False)
-    pb["para"] = write_para(pb, das_gauge_length=3 * pb["para"]["dx"])
+    pb["para"] = rewrite_para(pb, das_gauge_length=3 * pb["para"]["dx"])
     observe(pb)
     for batch in (0, 1):
         with P.kernel_options(batch=batch):
@@ -146,7 +146,7 @@ def test_every_session_gives_everything_back(tmp_path, hip_ops, probes_lib):
 
     # joint weights in the batched schedule (the residual table and the backward twin of the shot table)
     pb = P.make_problem(str(tmp_path / "joint"), nshots=3)
-    pb["para"] = write_para(pb, misfit_w_ett=1.0, misfit_w_vx=0.5, misfit_w_vz=2.0)
+    pb["para"] = rewrite_para(pb, misfit_w_ett=1.0, misfit_w_vx=0.5, misfit_w_vz=2.0)
     with P.kernel_options(batch=1):
         observe(pb)
         hip_ops.backward(*model(pb), pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
@@ -163,7 +163,7 @@ def test_every_session_gives_everything_back(tmp_path, hip_ops, probes_lib):
 
     # a conditioning key with the source update (the conditioner's six blocks)
     pb = P.make_problem(str(tmp_path / "conditioned"), nshots=2)
-    pb["para"] = write_para(pb, filter=[3.0, 7.0, 40.0, 60.0], if_src_update=True)
+    pb["para"] = rewrite_para(pb, filter=[3.0, 7.0, 40.0, 60.0], if_src_update=True)
     observe(pb)
     hip_ops.backward(*model(pb), pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
     done("conditioning", pb)
