@@ -68,19 +68,17 @@ void Session::alloc_arrays() {
     const Grid &g = g_;
     const size_t n = (size_t)(g.nzc + 4) * (size_t)g.pitch;  // 4 spare rows
     cells_ = n;
-    // [5 fields | 8 pml memories | 5 adjoint fields] contiguous so one memset clears a group
-    state_ = dalloc<float>(18 * n);
-    float *s = state_;
-    fld_ = Fields{s, s + n, s + 2 * n, s + 3 * n, s + 4 * n};
-    mem_ = PmlMem{s + 5 * n, s + 6 * n, s + 7 * n, s + 8 * n, s + 9 * n, s + 10 * n, s + 11 * n, s + 12 * n};
-    adj_ = Fields{s + 13 * n, s + 14 * n, s + 15 * n, s + 16 * n, s + 17 * n};
+    state_ = dalloc<float>(kOwnArrays * n);
+    fld_ = fields_at(state_, n);
+    mem_ = mem_at(state_mem(state_, n), n);
+    adj_ = fields_at(own_adj(state_, n), n);
     media_ = dalloc<float>(6 * n);
     HIP_OK(hipMemset(media_, 0, 6 * n * sizeof(float)));
     HIP_OK(hipDeviceSynchronize());  // the fill runs on the null stream and does not block the host; a caller's non-blocking stream would not wait for it
-    md_ = Media{media_, media_ + n, media_ + 2 * n, media_ + 3 * n, media_ + 4 * n, media_ + 5 * n};
-    acc_buf_ = dalloc<float>(5 * n);
+    md_ = media_at(media_, n);
+    acc_buf_ = dalloc<float>(kAccArrays * n);
     quiet_pool_ = dalloc<unsigned int>((size_t)kQuietSlots * 4 * (size_t)g.qn);
-    acc_ = ImgAcc{acc_buf_, acc_buf_ + n, acc_buf_ + 2 * n, acc_buf_ + 3 * n, acc_buf_ + 4 * n};
+    acc_ = acc_at(acc_buf_, n);
     const size_t dense = (size_t)par.nz * (size_t)par.nx;
     in_stage_ = dalloc<float>(3 * dense);
     grad_stage_ = dalloc<float>(3 * dense);
@@ -228,12 +226,31 @@ void Session::ensure_lanes(int n_lanes, bool with_frames) {
         XLane &L = xl_[k];
         ensure_lane_stream(L);
         if (!L.state) {
-            L.state = dev<float>(13 * n);
+            L.state = dev<float>(kStateArrays * n);
             L.syn = dev<float>(4 * data_len_);
             L.res = dev<float>(res_len_);
         }
-        if (with_frames && !L.frame) L.frame = dev<float>((size_t)par_.nSteps * 5 * (size_t)g_.frame_len);
+        if (with_frames && !L.frame) L.frame = dev<float>(frame_lane_len());
     }
+}
+
+Session::Lane Session::stream_lane(int k, hipStream_t call_st) const {
+    if (k == 0) return Lane{state_, frame_.get(), syn_, res_, quiet_slot(0), call_st};
+    if (k < 0 || k >= kMaxLanes) return Lane{};
+    const XLane &L = xl_[k];
+    return Lane{L.state.get(), L.frame.get(), L.syn.get(), L.res.get(), quiet_slot(k), L.stream.get()};
+}
+
+Session::Lane Session::batch_lane(int k, hipStream_t call_st) const {
+    const size_t n = cells_, j = (size_t)k;
+    if (k < 0 || j >= ba_.state.size() / (kStateArrays * n)) return Lane{};
+    float *frame = j < ba_.frame.size() / frame_lane_len() ? ba_.frame.get() + j * frame_lane_len() : nullptr;
+    return Lane{ba_.state.get() + j * kStateArrays * n, frame, ba_.syn.get() + j * 4 * data_len_, ba_.res.get() + j * res_len_, quiet_slot(kMaxLanes + k), call_st};
+}
+
+float *Session::batch_bwd(int k) const {
+    const size_t n = cells_, j = (size_t)k;
+    return k >= 0 && j < ba_.bwd.size() / (kBwdArrays * n) ? ba_.bwd.get() + j * kBwdArrays * n : nullptr;
 }
 
 // Batched mode: n_fwd lanes of forward state, the first n_bwd of them with backward state too; shot table and source rows
@@ -243,22 +260,11 @@ void Session::ensure_lanes(int n_lanes, bool with_frames) {
 // nothing from one call to the next.
 void Session::ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots) {
     const size_t n = cells_;
-    const size_t frame_lane = (size_t)par_.nSteps * 5 * (size_t)g_.frame_len;
-    ba_.state.ensure((size_t)n_fwd * 13 * n);
+    ba_.state.ensure((size_t)n_fwd * kStateArrays * n);
     ba_.syn.ensure((size_t)n_fwd * 4 * data_len_);
     ba_.res.ensure((size_t)n_fwd * res_len_);
-    if (with_frames) ba_.frame.ensure((size_t)n_fwd * frame_lane);
-    ba_.bwd.ensure((size_t)n_bwd * 18 * n);
-    const size_t n_state = ba_.state.size() / (13 * n), n_frame = ba_.frame.size() / frame_lane, n_bwd_have = ba_.bwd.size() / (18 * n);
-    bl_.assign(std::max<size_t>(n_state, 1), BLane{});
-    for (size_t k = 0; k < n_state; k++) {
-        BLane &L = bl_[k];
-        L.state = ba_.state.get() + k * 13 * n;
-        L.syn = ba_.syn.get() + k * 4 * data_len_;
-        L.res = ba_.res.get() + k * res_len_;
-        L.frame = k < n_frame ? ba_.frame.get() + k * frame_lane : nullptr;
-        L.bwd = k < n_bwd_have ? ba_.bwd.get() + k * 18 * n : nullptr;
-    }
+    if (with_frames) ba_.frame.ensure((size_t)n_fwd * frame_lane_len());
+    ba_.bwd.ensure((size_t)n_bwd * kBwdArrays * n);
     d_shots_.ensure((size_t)n_shots);
     d_stf_.ensure((size_t)n_shots * par_.nSteps);
 }
@@ -310,42 +316,37 @@ void Session::copy_field(int lane, int which, float *out) {
         if (!born_) throw std::invalid_argument("debug_field: no Born call yet");
         base = born_.get() + (size_t)(which - 10) * cells_;
     } else if (which >= 5) {  // adjoint fields: one set per session (stream mode) or per backward lane (batched mode)
-        if (last_batched_) {
-            if (lane < 0 || lane >= (int)bl_.size() || !bl_[lane].bwd) throw std::invalid_argument("debug_field: no such backward lane");
-            base = bl_[lane].bwd + (8 + (which - 5)) * cells_;
-        } else {
-            base = adj_.vz + (size_t)(which - 5) * cells_;
-        }
-    } else if (last_batched_) {
-        if (lane < 0 || lane >= (int)bl_.size() || !bl_[lane].state) throw std::invalid_argument("debug_field: no such lane");
-        base = bl_[lane].state + (size_t)which * cells_;
+        const float *adj = last_batched_ ? (batch_bwd(lane) ? bwd_adj(batch_bwd(lane), cells_) : nullptr) : adj_.vz;
+        if (!adj) throw std::invalid_argument("debug_field: no such backward lane");
+        base = adj + (size_t)(which - 5) * cells_;
     } else {
-        if (lane < 0 || lane >= kMaxLanes || (lane > 0 && !xl_[lane].state)) throw std::invalid_argument("debug_field: no such lane");
-        base = (lane ? xl_[lane].state.get() : state_) + (size_t)which * cells_;
+        const Lane L = last_batched_ ? batch_lane(lane) : stream_lane(lane);
+        if (!L.state) throw std::invalid_argument("debug_field: no such lane");
+        base = L.state + (size_t)which * cells_;
     }
     HIP_OK(hipMemcpy2D(out, (size_t)g_.nx * sizeof(float), base, (size_t)g_.pitch * sizeof(float), (size_t)g_.nx * sizeof(float),
                        (size_t)g_.nzc, hipMemcpyDefault));
 }
 
 void Session::stats(sepfwi_stats *out) const {
-    out->fwd_ms = fwd_ms_;
-    out->bwd_ms = bwd_ms_;
+    out->fwd_ms = cs_.fwd_ms;
+    out->bwd_ms = cs_.bwd_ms;
     out->total_ms = total_ms_;
     out->n_c = g_.nzc * g_.nx;
-    out->fwd_steps = fwd_steps_;
-    out->bwd_steps = bwd_steps_;
-    out->launches = launches_;
+    out->fwd_steps = cs_.fwd_steps;
+    out->bwd_steps = cs_.bwd_steps;
+    out->launches = cs_.launches;
     out->device_bytes = device_bytes_ + (cond_ ? cond_->device_bytes() : 0) + obs_->device_bytes();
     out->obs_device_bytes = obs_->device_bytes();
     out->obs_host_bytes = obs_->host_bytes();
     out->obs_evictions = obs_->evictions();
-    out->persist_steps = persist_steps_;
-    out->quiet_active = quiet_active_;
-    out->quiet_total = quiet_total_;
-    out->probe_kernel_us = probe_calls_ ? probe_us_ / (double)probe_calls_ : 0.0;
-    out->probe_calls = probe_calls_;
+    out->persist_steps = cs_.persist_steps;
+    out->quiet_active = cs_.quiet_active;
+    out->quiet_total = cs_.quiet_total;
+    out->probe_kernel_us = cs_.probe_calls ? cs_.probe_us / (double)cs_.probe_calls : 0.0;
+    out->probe_calls = cs_.probe_calls;
     // one forward pass = N_c*(nSteps-1); fwd+adj = 3x (forward, reconstruction, adjoint)
-    out->cell_updates = (double)out->n_c * ((double)fwd_steps_ + 2.0 * (double)bwd_steps_);
+    out->cell_updates = (double)out->n_c * ((double)cs_.fwd_steps + 2.0 * (double)cs_.bwd_steps);
 }
 
 // ------------------------------------------------------------------------------------------------

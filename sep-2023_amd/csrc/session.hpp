@@ -21,6 +21,7 @@
 #include "obs_store.hpp"
 #include "persist_plan.hpp"
 #include "pseudo_hessian.hpp"
+#include "schedule.hpp"
 
 namespace sepfwi {
 
@@ -119,7 +120,20 @@ class Session {
     void read_misfit(const Call &c, float *misfit, bool parts);
     struct GaugeDev;
     struct InjDev;
-    struct ShotCtx {  // one shot of the call in the lane it runs in
+    // A shot's working set: forward state (schedule.hpp: [5 fields | 8 memories]), boundary frames (null until a gradient call needs
+    // them), seismograms, residual, its slot of the quiet-map pool, its stream.  state null: there is no such lane.
+    struct Lane {
+        float *state = nullptr, *frame = nullptr, *syn = nullptr, *res = nullptr;
+        unsigned int *quiet = nullptr;  // ShotCtx: null unless the shot runs with option quiet_skip
+        hipStream_t st = nullptr;
+    };
+    // lane k of the stream schedule (0: the session's own arrays on the call's stream; k >= 1: xl_[k]) and of the batched schedule (the
+    // arenas ba_ at their constant strides), with the backward block of a batch lane (null: none)
+    Lane stream_lane(int k, hipStream_t call_st = nullptr) const;
+    Lane batch_lane(int k, hipStream_t call_st = nullptr) const;
+    float *batch_bwd(int k) const;
+    size_t frame_lane_len() const { return (size_t)par_.nSteps * 5 * (size_t)g_.frame_len; }
+    struct ShotCtx : Lane {  // one shot of the call in the lane it runs in
         int is, id, nrec, comps;
         int nres;               // row length of `res`: nrec, or C nrec for a joint misfit (geophone.hpp)
         const float *obs_c[4];  // joint misfit: the observed gathers of the active components, by component id
@@ -131,13 +145,10 @@ class Session {
         const InjDev *ginj;     // ... and their adjoint plan (gradient calls)
         bool scratch;
         LineRec line;
-        float *state;  // [5 fields | 8 memory variables] of this lane
-        unsigned int *quiet;  // option quiet_skip: the lane's four quiet-segment maps (forward v, forward s, adjoint v, adjoint s), or null
+        // (Lane::quiet, option quiet_skip: the lane's four quiet-segment maps -- forward v, forward s, adjoint v, adjoint s -- or null)
         float *ph;            // armed call: the pseudo-Hessian accumulator set of the shot's stream lane, else null
-        Fields fld;
+        Fields fld;           // views of Lane::state
         PmlMem mem;
-        float *frame, *syn, *res;
-        hipStream_t st;
     };
     struct BwdLane {  // stream + backward-pass memory variables + adjoint fields + imaging accumulators
         hipStream_t s;
@@ -147,9 +158,8 @@ class Session {
     };
     void prepare_media(Call &c, const float *Lambda, const float *Mu, const float *Den);
     void prepare_buffers(Call &c, const float *stf);
-    ShotCtx make_ctx(const Call &c, int is, int lane, hipStream_t lane_st, bool with_obs = true);
-    void use_state(ShotCtx &x, float *state) const;
-    static constexpr int kQuietSlots = 4 + 64;  // one per stream lane (kMaxLanes) and batch lane (option batch_f <= 64)
+    ShotCtx make_ctx(const Call &c, int is, const Lane &lane, bool with_obs = true);
+    static constexpr int kQuietSlots = kMaxLanes + 64;  // one per stream lane and batch lane (option batch_f <= 64)
     unsigned int *quiet_slot(int slot) const { return quiet_pool_ + (size_t)slot * 4 * (size_t)g_.qn; }
     bool quiet_wanted(const Call &c, const ShotCtx &x) const { return c.opt.quiet_skip != 0 && !joint_ && (x.nrec == 0 || (x.line.n > 0 && c.opt.line_fuse != 0)); }
     // the residual of a fused line enters inside the field kernels -- unless the misfit is a joint one, whose adjoint source goes through the plan
@@ -173,6 +183,7 @@ class Session {
     void backward_init(const BwdLane &L);
     void backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it);
     void inject_column(const ShotCtx &x, const BwdLane &L, const float *res_t);
+    Grid step_grid(const KernelOptions &opt, int it) const;  // the grid with backward step it's imaging weight (option img_every)
     void backward(Call &c, const ShotCtx &x);
     // the exact transposed time loop of one shot and its finalisation on Omega (session_exact.cpp); the persistent loop is not used
     void backward_exact(Call &c, const ShotCtx &x);
@@ -183,6 +194,7 @@ class Session {
     bool persist_prepare(Persist &k, const KernelOptions &opt, int nshots);
     bool backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L);
     bool batched_backward_persistent(Call &c, const std::vector<ShotDev> &tab, int first, int nbb);
+    ShotDev shot_dev(const Call &c, const ShotCtx &x) const;  // what the loop's record of a shot and the batched schedule's share
     bool persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st);
     const InjArgs *persist_inject(const Call &c, const ShotCtx &x, hipStream_t st);
     InjDev &inj_dev(const ShotCtx &x);
@@ -191,15 +203,18 @@ class Session {
     const Event *probe_pair(Call &c, int it);
     void collect_probes(Call &c);
     // the two schedules of a call's shots
-    void run_streams(Call &c);
+    void run_streams(Call &c, int n_lanes);
     // batched schedule (session_batched.cpp)
-    void run_batched(Call &c, int Bf, int Bb);
+    void run_batched(Call &c, const Schedule &s);
     ShotCtx batch_ctx(const Call &c, int is, int Bf, bool with_obs);
     std::vector<ShotDev> batch_table(const Call &c, int Bf, int Bb);
-    void batch_streams(hipStream_t st, int ns, hipStream_t *sub);
+    struct SubBatch : SubRange {  // a sub-batch (schedule.hpp) and the stream it runs on
+        hipStream_t st;
+    };
+    std::vector<SubBatch> batch_streams(hipStream_t st, const std::vector<ShotFacts> &shots, int ns);
     void batch_join(hipStream_t st, int ns);
-    void batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0, int nb, const std::vector<ShotCtx> &cx);
-    void batched_backward(Call &c, const std::vector<ShotDev> &tab, int first, int nbb, const ShotCtx *cx);
+    void batched_forward(Call &c, const std::vector<ShotDev> &tab, int is0, int nb, int split, const std::vector<ShotCtx> &cx);
+    void batched_backward(Call &c, const std::vector<ShotDev> &tab, int first, int nbb, int split, const ShotCtx *cx);
     void ph_begin(Call &c, int nsets);  // armed call: the accumulator sets of its lanes / sub-batch streams, zeroed on the call's stream
     PhAcc ph_acc(const float *set) const { float *s = const_cast<float *>(set); return PhAcc{s, s + cells_, s + 2 * cells_}; }
     void write_outputs(Call &c, float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_Den, float *grad_stf);
@@ -229,8 +244,6 @@ class Session {
     static constexpr int kProbePairs = 64;
     Event probe_ev_[2 * kProbePairs];
     Event ev_[4];
-    double probe_us_ = 0.0;
-    long long probe_calls_ = 0;
     PinBuf<float> h_io_;
     DevBuf<float> stf_grad_{&device_bytes_}, frame_;
     std::vector<DevBuf<char>> allocs_;  // the constructor's blocks (dalloc): what state_, media_ ... below are views of
@@ -282,6 +295,8 @@ class Session {
     std::map<int, InjDev> inj_;
     // persistent backward time loop: the tiling in use, its device copy, synchronisation words, what the census of the grid said
     struct Persist {
+        explicit Persist(bool multi_shot) : multi(multi_shot) {}
+        const bool multi;  // the batched schedule's loop: the multi-shot kernel instance, also for a sub-batch of one
         PersistPlan plan;
         DevBuf<uint32_t> d_seg;
         DevBuf<TileHdr> d_hdr;
@@ -295,11 +310,10 @@ class Session {
         std::string why;                 // when state == 0
         int plan_gen = 0;                // counts the tilings built (what depends on one is rebuilt when it changes)
         int retry_in = 0, aborts = 0;    // passes until the loop is tried again after a start rendezvous that failed; how often it did
-    } pk_ms_, pk_;  // the shots of a backward sub-batch in one launch (batched schedule) / one shot per launch (stream schedule)
+    } pk_ms_{true}, pk_{false};  // the shots of a backward sub-batch in one launch (batched schedule) / one shot per launch (stream schedule)
     std::unique_ptr<ObservedStore> obs_;
     // extra forward lanes (lane 0 = state_/frame_/syn_/res_ on the call's stream): stream, join event, fields + memories, frames,
     // seismograms, residual
-    static constexpr int kMaxLanes = 4;
     struct XLane {
         Stream stream;
         Event join;
@@ -308,11 +322,7 @@ class Session {
     XLane xl_[kMaxLanes];
     void ensure_lane_stream(XLane &L);
     // batched mode: lanes of per-shot state (forward: fields + memories, frames, seismograms, residual; backward: memories,
-    // adjoint fields, accumulators) and the device tables of the call's shots and source rows
-    struct BLane {
-        float *state = nullptr, *bwd = nullptr, *frame = nullptr, *syn = nullptr, *res = nullptr;
-    };
-    std::vector<BLane> bl_;
+    // adjoint fields, accumulators; batch_lane, batch_bwd) and the device tables of the call's shots and source rows
     DevBuf<float> d_stf_{&device_bytes_};
     DevBuf<GeoResShot> d_geo_res_{&device_bytes_};
     DevBuf<ShotDev> d_shots_bwd_{&device_bytes_}, d_shots_{&device_bytes_};
@@ -321,7 +331,6 @@ class Session {
         DevBuf<float> state, syn, res, frame, bwd;
     } ba_{&device_bytes_};
     bool last_batched_ = false;
-    bool last_exact_ = false;  // the last call's backward passes were exact ones (loop_status)
     float *state_ = nullptr, *media_ = nullptr, *acc_buf_ = nullptr, *in_stage_ = nullptr, *grad_stage_ = nullptr;
     float *syn_ = nullptr, *res_ = nullptr, *xpose_ = nullptr;
     double *scal_ = nullptr;
@@ -339,12 +348,15 @@ class Session {
     PmlCoef pc_{};
     ImgAcc acc_{};
     unsigned int *quiet_pool_ = nullptr;  // kQuietSlots x 4 maps of Grid::qn words (Fields::q)
-    long long persist_steps_ = 0;
-    long long quiet_active_ = 0, quiet_total_ = 0;
-    unsigned int *quiet_last_ = nullptr;  // maps of the shot whose forward pass started last in this call
-
-    double fwd_ms_ = 0, bwd_ms_ = 0, total_ms_ = 0;
-    long long fwd_steps_ = 0, bwd_steps_ = 0, launches_ = 0;
+    // What a call counts (sepfwi_stats): begin_call starts every call from CallStats{} -- a new counter cannot carry over.
+    struct CallStats {
+        double fwd_ms = 0, bwd_ms = 0, probe_us = 0;
+        long long fwd_steps = 0, bwd_steps = 0, launches = 0, persist_steps = 0, probe_calls = 0;
+        long long quiet_active = 0, quiet_total = 0;
+        unsigned int *quiet_last = nullptr;  // maps of the shot whose forward pass started last in this call
+        bool exact = false;                  // the call's backward passes are exact ones (loop_status)
+    } cs_;
+    double total_ms_ = 0;
     int last_shots_ = 0, last_calc_ = -1;
 };
 

@@ -42,14 +42,14 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files; the observed store is not touched)
     hipStream_t st = c.st;
     last_batched_ = false;
-    last_exact_ = exact && want_hv;
+    cs_.exact = exact && want_hv;
 
     prepare_media(c, Lambda, Mu, Den);  // (the Courant guard: the background model only)
     prepare_buffers(c, stf);
 
     const size_t n = cells_, dense = (size_t)par_.nz * (size_t)par_.nx;
     const int nSteps = par_.nSteps;
-    if (!born_) born_ = dev<float>(18 * n);
+    if (!born_) born_ = dev<float>((kStateArrays + 5) * n);
     const float *dv[3] = {dLambda, dMu, dDen};
     for (int k = 0; k < 3; k++) {
         if (!exact && ptr_device(dv[k]) == gpu_id_) continue;  // (the exact product reads v on Omega only: it masks a copy)
@@ -59,12 +59,12 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     }
     if (exact) {
         launch_exact_mask(st, g_, born_stage_.get(), 3, dense);
-        launches_++;
+        cs_.launches++;
     }
     const float *mu_dense = ptr_device(Mu) == gpu_id_ ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
-    float *dstate = born_.get(), *dmedia = born_.get() + 13 * n;
+    float *dstate = born_.get(), *dmedia = born_.get() + kStateArrays * n;  // [5 scattered fields | 8 memories] like a lane's state, then the media
     launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
-    launches_++;
+    cs_.launches++;
 
     // which scattered gathers the call needs: the requested ones, and for the product the components with a weight
     int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
@@ -73,32 +73,32 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     size_t out_off = 0;
     const BornArgs args{state_, dstate, media_, dmedia, pc_.a_z, n};
     for (int is = 0; is < group_size; is++) {
-        ShotCtx x = make_ctx(c, is, 0, st, false);
+        ShotCtx x = make_ctx(c, is, stream_lane(0, st), false);
         x.scratch = false;
         x.comps = comps;
         ShotCtx xd = x;  // the samplers' view: the scattered fields
-        xd.fld = Fields{dstate, dstate + n, dstate + 2 * n, dstate + 3 * n, dstate + 4 * n};
+        xd.fld = fields_at(dstate, n);
 
         HIP_OK(hipEventRecord(ev_[0], st));
         forward_init(x);  // background state, column 0 of the gathers
-        HIP_OK(hipMemsetAsync(dstate, 0, 13 * n * sizeof(float), st));
+        HIP_OK(hipMemsetAsync(dstate, 0, kStateArrays * n * sizeof(float), st));
         for (int it = 0; it <= nSteps - 2; it++) {
             float *frame_t = want_hv ? x.frame + (size_t)it * 5 * (size_t)g_.frame_len : nullptr;
             const float amp = c.src_scale * x.stf_s[it] * par_.dt;
             launch_born_stress(st, g_, c.opt, args, frame_t, x.sh->z_src, x.sh->x_src, amp);
             launch_born_velocity(st, g_, c.opt, args);
-            launches_ += 2;
+            cs_.launches += 2;
             if (x.nrec > 0 && comps) record_column(xd, it + 1);
         }
         HIP_OK(hipEventRecord(ev_[1], st));
-        fwd_steps_ += (long long)(nSteps - 1);
+        cs_.fwd_steps += (long long)(nSteps - 1);
 
         const size_t cnt = (size_t)x.nrec * nSteps;
         for (int k = 1; k <= 3 && cnt; k++) {
             if (!out[k]) continue;
             launch_transpose(st, syn_of(x, k), xpose_, nSteps, x.nrec);  // [it][rec] -> [rec][it]
             HIP_OK(hipMemcpyAsync(out[k] + out_off, xpose_, cnt * sizeof(float), hipMemcpyDefault, st));
-            launches_++;
+            cs_.launches++;
         }
         out_off += cnt;
         if (want_hv && x.nrec > 0) {
@@ -108,9 +108,9 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
                 q.scale[b] = par_.weight(comp);
             });
             launch_adjoint_source(st, q, nSteps);
-            launches_++;
+            cs_.launches++;
         }
-        fwd_ms_ += bracket_ms(0, st);  // (the time loop alone: ev_[1] was recorded before the gathers left)
+        cs_.fwd_ms += bracket_ms(0, st);  // (the time loop alone: ev_[1] was recorded before the gathers left)
         if (want_hv && exact)
             backward_exact(c, x);
         else if (want_hv)

@@ -35,7 +35,7 @@ void Session::backward_exact(Call &c, const ShotCtx &x) {
     if (x.nrec > 0) {  // the column a gradient call never injects, and the adjoint memories of the velocity update that see it
         inject_column(x, L, x.res + (size_t)(nSteps - 1) * x.nres);
         launch_exact_b(st, g_, c.opt, a, nullptr, 0, 0, 0.0f, true);
-        launches_ += 2;
+        cs_.launches += 2;
     }
     for (int it = nSteps - 2; it >= 0; it--) {
         float *frame_t = x.frame + (size_t)it * 5 * (size_t)g_.frame_len;
@@ -43,21 +43,21 @@ void Session::backward_exact(Call &c, const ShotCtx &x) {
         launch_exact_a(st, g_, c.opt, a, frame_t);
         if (it >= 1 && x.nrec > 0) {
             inject_column(x, L, x.res + (size_t)it * x.nres);
-            launches_++;
+            cs_.launches++;
         }
         launch_exact_b(st, g_, c.opt, a, frame_t, x.sh->z_src, x.sh->x_src, amp, false);
-        launches_ += 2;
+        cs_.launches += 2;
     }
     HIP_OK(hipEventRecord(ev_[3], st));
-    bwd_steps_ += (long long)(nSteps - 1);
-    bwd_ms_ += bracket_ms(2, st);
+    cs_.bwd_steps += (long long)(nSteps - 1);
+    cs_.bwd_ms += bracket_ms(2, st);
 }
 
 // the finalisation on Omega; in place or staged as write_outputs does it (grad_out)
 void Session::write_outputs_exact(Call &c, float *g_Lambda, float *g_Mu, float *g_Den) {
     const GradOut o = grad_out(g_Lambda, g_Mu, g_Den);
     launch_exact_finalize(c.st, g_, md_, acc_, o.dev[0], o.dev[1], o.dev[2]);
-    launches_++;
+    cs_.launches++;
     copy_staged(o, c.st);
 }
 
@@ -82,7 +82,7 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
     c.if_res = !have_w;  // (ph_every stays 0: an armed pseudo-Hessian is not accumulated by this call)
     hipStream_t st = c.st;
     last_batched_ = false;
-    last_exact_ = true;
+    cs_.exact = true;
     if (c.if_res) obs_begin(c);
 
     prepare_media(c, Lambda, Mu, Den);  // (the Courant guard)
@@ -91,7 +91,7 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
     const int nSteps = par_.nSteps;
     size_t w_off = 0;
     for (int is = 0; is < group_size; is++) {
-        ShotCtx x = make_ctx(c, is, 0, st, c.if_res);
+        ShotCtx x = make_ctx(c, is, stream_lane(0, st), c.if_res);
         x.scratch = false;
         x.comps = c.if_res ? (x.comps & ~1) : 8;  // the gathers the residual needs; with the caller's w none is read (one is sampled, as in a misfit call)
 
@@ -116,12 +116,12 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
                 q.scale[b] = 1.0f;
             });
             launch_adjoint_source(st, q, nSteps);
-            launches_++;
+            cs_.launches++;
         }
         w_off += cnt;
         HIP_OK(hipEventRecord(ev_[1], st));
-        fwd_steps_ += (long long)(nSteps - 1);
-        fwd_ms_ += bracket_ms(0, st);
+        cs_.fwd_steps += (long long)(nSteps - 1);
+        cs_.fwd_ms += bracket_ms(0, st);
         if (c.if_res) obs_->release_all();
         backward_exact(c, x);
     }

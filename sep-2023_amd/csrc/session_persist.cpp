@@ -67,7 +67,7 @@ bool Session::persist_prepare(Persist &k, const KernelOptions &opt, int nshots) 
     if (!k.why.empty()) return false;
     const int nseg = (g_.nx + 63) / 64;
     k.nwg = (ncu / nband) * nband * opt.pk_wpc;
-    const bool multi = &k == &pk_ms_;  // the batched schedule's loop: the multi-shot kernel instance, also for a sub-batch of one
+    const bool multi = k.multi;
     // One shot per launch: tiles of a handful of row segments lose to the batched per-step launches (which that schedule would have
     // chosen).  The batched schedule itself: any sub-batch that gives every tile work (remainders of one or two small shots included).
     if (k.nwg <= 0 || (long long)g_.nzc * nshots * nseg < (multi ? 3LL * k.nwg / 2 : 4LL * k.nwg)) {
@@ -179,7 +179,7 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
     launch_inject_values(st, x.res, x.nres, par_.nSteps, d.tgt_start.get(), d.ent_rec.get(), d.ent_w.get(), d.ntgt, inj_val_.get());
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) throw HipError(std::string("k_inject_values launch failed: ") + hipGetErrorString(le));
-    launches_++;
+    cs_.launches++;
     if (it->second.tile_gen != pk_.plan_gen) {  // which tiles of the CURRENT tiling own target cells (a new tiling: rebuilt)
         InjDev &dd = it->second;
         std::vector<unsigned char> has((size_t)pk_.nwg, 0);
@@ -202,7 +202,7 @@ const InjArgs *Session::persist_inject(const Call &c, const ShotCtx &x, hipStrea
 
 std::string Session::loop_status() {
     std::lock_guard<std::mutex> lock(mu_);
-    if (last_exact_) return "the exact adjoint runs two launches per time step: the persistent loop is not used (exact_adjoint.hpp)";
+    if (cs_.exact) return "the exact adjoint runs two launches per time step: the persistent loop is not used (exact_adjoint.hpp)";
     const Persist &k = last_batched_ ? pk_ms_ : pk_;  // the schedule of the last call: multi-shot loop (batched) or one loop per shot (streams)
     if (k.state < 0) return "not considered yet (no gradient call, bwd_fuse != 4, or shots whose channels are not fused lines in a batched call)";
     return k.state == 1 ? std::string() : k.why;
@@ -216,6 +216,22 @@ void Session::persist_demote(Persist &k, const std::string &why, int retry_in) {
     if (k.aborts++ == 0) fprintf(stderr, "sepfwi: persistent backward loop not started (%s); this pass runs as per-step launches\n", why.c_str());
 }
 
+// The device record of shot x, the half that the persistent loop and the batched schedule's table (batch_table) fill alike: where the
+// shot's lane lies, its row of the source gradient, its source cell, where a line of channels starts.
+ShotDev Session::shot_dev(const Call &c, const ShotCtx &x) const {
+    ShotDev d{};
+    d.fields = x.state;
+    d.frame = x.frame;
+    d.res = x.res;
+    d.stf_grad = c.with_adj ? stf_grad_.get() + (size_t)x.is * par_.nSteps : nullptr;
+    d.z_src = x.sh->z_src;
+    d.x_src = x.sh->x_src;
+    d.src_rxz = (float)x.sh->src_rxz;
+    d.lr_z = x.line.z;
+    d.lr_x0 = x.line.x0;
+    return d;
+}
+
 // One shot's backward pass as one launch.  Returns false when the loop did not run -- the launch was refused, or the start
 // rendezvous found the grid not resident at once / a band spread over several XCDs: in both cases NOTHING has been touched, and the
 // caller runs the per-step launches.  Synchronises the stream (the verdict of the rendezvous is read on the host).
@@ -225,21 +241,12 @@ bool Session::backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L) {
     hipStream_t st = L.s;
     HIP_OK(hipMemcpyAsync(k.d_stf.get(), x.stf_s, (size_t)nSteps * sizeof(float), hipMemcpyHostToDevice, st));
     PersistArgs a{};
-    ShotDev &d = a.s;
-    d.fields = x.state;
-    d.frame = x.frame;
-    d.stf = k.d_stf.get();
-    d.bmem = L.bm.dvz_dz;
+    ShotDev &d = a.s = shot_dev(c, x);
+    d.stf = k.d_stf.get();  // this pass's source row, uploaded above (the table: the rows of all the call's shots)
+    d.bmem = L.bm.dvz_dz;   // the session's own backward arrays (the table: the block of the shot's batch lane)
     d.adj = L.adj.vz;
     d.acc = L.acc.lam;
-    d.res = x.res;
-    d.stf_grad = stf_grad_.get() + (size_t)x.is * nSteps;
-    d.z_src = x.sh->z_src;
-    d.x_src = x.sh->x_src;
-    d.lr_z = x.line.z;
-    d.lr_x0 = x.line.x0;
-    d.nrec = x.nrec;
-    d.src_rxz = (float)x.sh->src_rxz;
+    d.nrec = x.nrec;        // also for gauge channels: no generic receiver kernel reads it here (the table: 0 for them)
     a.injp = persist_inject(c, x, st);
     d.lr_n = a.injp ? 0 : x.line.n;  // a line that is not fused (line_fuse=0) goes through the plan: the bodies must not inject it again
     if (x.quiet && k.d_qnbr && !a.injp) {  // option quiet_skip (fused line of channels, or none): the quiet variant of the loop
@@ -247,7 +254,7 @@ bool Session::backward_persistent(Call &c, const ShotCtx &x, const BwdLane &L) {
         a.q.nbr = k.d_qnbr.get();
     }
     if (!persist_launch(k, c, a, st)) return false;
-    persist_steps_ += (long long)(nSteps - 1);
+    cs_.persist_steps += (long long)(nSteps - 1);
     return true;
 }
 
@@ -276,7 +283,7 @@ bool Session::batched_backward_persistent(Call &c, const std::vector<ShotDev> &t
         if (!ok) throw std::logic_error("multi-shot loop: the batch lanes do not lie at constant strides");
     }
     if (!persist_launch(k, c, a, c.st)) return false;
-    persist_steps_ += (long long)nbb * (nSteps - 1);
+    cs_.persist_steps += (long long)nbb * (nSteps - 1);
     return true;
 }
 
@@ -312,7 +319,7 @@ bool Session::persist_launch(Persist &k, Call &c, PersistArgs &a, hipStream_t st
         persist_demote(k, "the launch was refused (code " + std::to_string(rc) + (e != hipSuccess ? std::string(", ") + hipGetErrorString(e) : std::string()) + ")", 0);
         return false;
     }
-    launches_++;
+    cs_.launches++;
     HIP_OK(hipMemcpyAsync(k.h_err.get(), err, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(k.h_err.get() + 1, band_xcc + 9, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));

@@ -57,8 +57,10 @@ void Session::prepare_media(Call &c, const float *Lambda, const float *Mu, const
     if (ptr_device(Mu) != gpu_id_) { HIP_OK(hipMemcpyAsync(in_stage_ + dense, Mu, dense * sizeof(float), hipMemcpyDefault, st)); dM = in_stage_ + dense; }
     if (ptr_device(Den) != gpu_id_) { HIP_OK(hipMemcpyAsync(in_stage_ + 2 * dense, Den, dense * sizeof(float), hipMemcpyDefault, st)); dD = in_stage_ + 2 * dense; }
     HIP_OK(hipMemsetAsync(cp2_bits_, 0, sizeof(unsigned int), st));
-    launch_model_prep(st, g_, c.opt, dL, dM, dD, media_, media_ + n, media_ + 2 * n, media_ + 3 * n, media_ + 4 * n, media_ + 5 * n, cp2_bits_);
-    launches_++;
+    float *m[6];  // the arrays of md_, to be written
+    for (int k = 0; k < 6; k++) m[k] = media_ + (size_t)k * n;
+    launch_model_prep(st, g_, c.opt, dL, dM, dD, m[0], m[1], m[2], m[3], m[4], m[5], cp2_bits_);
+    cs_.launches++;
     unsigned int bits = 0;
     HIP_OK(hipMemcpyAsync(&bits, cp2_bits_, sizeof(bits), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -76,8 +78,8 @@ void Session::prepare_buffers(Call &c, const float *stf) {
     hipStream_t st = c.st;
     const int nSteps = par_.nSteps;
     const size_t n = cells_;
-    if (c.with_adj && !frame_) frame_ = dev<float>((size_t)nSteps * 5 * (size_t)g_.frame_len);
-    if (c.with_adj) HIP_OK(hipMemsetAsync(acc_buf_, 0, 5 * n * sizeof(float), st));
+    if (c.with_adj && !frame_) frame_ = dev<float>(frame_lane_len());
+    if (c.with_adj) HIP_OK(hipMemsetAsync(acc_buf_, 0, kAccArrays * n * sizeof(float), st));
     if (c.if_res) HIP_OK(hipMemsetAsync(scal_, 0, 4 * sizeof(double), st));
     if (c.if_res && joint_) HIP_OK(hipMemsetAsync(geo_sums_, 0, 4 * sizeof(double), st));
     c.stf_rows.resize((size_t)c.group_size * nSteps);
@@ -93,20 +95,12 @@ void Session::prepare_buffers(Call &c, const float *stf) {
     }
 }
 
-void Session::use_state(ShotCtx &x, float *state) const {
-    const size_t n = cells_;
-    x.state = state;
-    float *b = state;
-    x.fld = Fields{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n};
-    x.fld.q = x.quiet;
-    x.mem = PmlMem{b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n, b + 9 * n, b + 10 * n, b + 11 * n, b + 12 * n};
-}
-
-// Shot `is` of the call in stream lane `lane` (0: the session's own state on the call's stream).  Acquires the shot's observed
-// gather (held in HBM until the group of shots is through: ObservedStore::release_all) unless with_obs is false (geometry only).
-Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t lane_st, bool with_obs) {
+// Shot `is` of the call in `lane` (stream_lane, batch_lane).  Acquires the shot's observed gather (held in HBM until the group of
+// shots is through: ObservedStore::release_all) unless with_obs is false (geometry only).
+Session::ShotCtx Session::make_ctx(const Call &c, int is, const Lane &lane, bool with_obs) {
     const Grid &g = g_;
     ShotCtx x{};
+    static_cast<Lane &>(x) = lane;
     x.is = is;
     x.id = c.shot_ids[is];
     x.sh = &survey_.shots[x.id];
@@ -133,23 +127,20 @@ Session::ShotCtx Session::make_ctx(const Call &c, int is, int lane, hipStream_t 
     }
     if (gauge) x.gauge = &gauge_taps(x);
     if ((gauge || (joint_ && x.nrec > 0)) && c.with_adj) x.ginj = &inj_dev(x);  // (a joint misfit: every shot's adjoint source goes through its plan)
-    x.quiet = quiet_wanted(c, x) ? quiet_slot(lane) : nullptr;
-    x.ph = c.ph_every > 0 ? ph_set_[lane].get() : nullptr;
-    use_state(x, lane ? xl_[lane].state.get() : state_);
-    x.frame = lane ? xl_[lane].frame.get() : frame_.get();
-    x.syn = lane ? xl_[lane].syn.get() : syn_;
-    x.res = lane ? xl_[lane].res.get() : res_;
-    x.st = lane_st;
+    if (!quiet_wanted(c, x)) x.quiet = nullptr;
+    x.fld = fields_at(x.state, cells_);
+    x.fld.q = x.quiet;
+    x.mem = mem_at(state_mem(x.state, cells_), cells_);
     return x;
 }
 
 // ---- forward pass of one shot (stream form) ------------------------------------------------------------------------------
 // zero the 5 fields + 8 memory variables (libCUFD.cu:175-194); data column 0 stays 0 (:205-209)
 void Session::forward_init(const ShotCtx &x) {
-    HIP_OK(hipMemsetAsync(x.state, 0, 13 * cells_ * sizeof(float), x.st));
+    HIP_OK(hipMemsetAsync(x.state, 0, kStateArrays * cells_ * sizeof(float), x.st));
     if (x.quiet) {
         HIP_OK(hipMemsetAsync(x.quiet, 0, 2 * (size_t)g_.qn * sizeof(unsigned int), x.st));  // nothing holds a value yet
-        quiet_last_ = x.quiet;
+        cs_.quiet_last = x.quiet;
     }
     for (int k = 0; k < 4; k++)
         if ((x.comps >> k) & 1) HIP_OK(hipMemsetAsync(syn_of(x, k), 0, (size_t)x.nrec * sizeof(float), x.st));
@@ -163,7 +154,7 @@ void Session::record_column(const ShotCtx &x, int column) {
                             syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps);
     else
         launch_record(x.st, g_, x.fld, x.nrec, x.rec, syn_of(x, 0) + col, syn_of(x, 1) + col, syn_of(x, 2) + col, syn_of(x, 3) + col, x.comps, x.sens);
-    launches_++;
+    cs_.launches++;
 }
 
 // taps of a shot's gauge channels (das_gauge.hpp), uploaded once per session and shot
@@ -198,10 +189,10 @@ void Session::forward_step(const Call &c, const ShotCtx &x, int it, bool inl) {
     launch_stress_fwd(x.st, g_, c.opt, x.fld, x.mem, md_, pc_, frame_t, x.sh->z_src, x.sh->x_src, amp, lr);
     if (x.ph && it % c.ph_every == 0) {  // armed: velocities of the start of the step, stresses after update and source add (pseudo_hessian.hpp)
         launch_pseudo_hessian(x.st, g_, x.fld, md_, ph_acc(x.ph), (float)c.ph_every);
-        launches_++;
+        cs_.launches++;
     }
     launch_velocity_fwd(x.st, g_, c.opt, x.fld, x.mem, md_, pc_);
-    launches_ += 2;
+    cs_.launches += 2;
     if (!inl) record_column(x, it + 1);
 }
 
@@ -209,11 +200,11 @@ void Session::forward_step(const Call &c, const ShotCtx &x, int it, bool inl) {
 void Session::residual(const ShotCtx &x) {
     if (joint_) {  // geophone.hip: the weighted residuals of the active components as one array [it][C nrec], sum r_c^2 per component
         launch_geo_residual(x.st, geo_res_shot(x), par_.nSteps, geo_sums_);
-        launches_++;
+        cs_.launches++;
         return;
     }
     launch_residual(x.st, x.d_obs, syn_of(x, 3), x.res, x.nrec, (long long)x.nrec * par_.nSteps, scal_);
-    launches_++;
+    cs_.launches++;
 }
 
 GeoResShot Session::geo_res_shot(const ShotCtx &x) const {
@@ -241,7 +232,7 @@ void Session::residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int 
     d_geo_res_.ensure((size_t)nb);
     HIP_OK(hipMemcpyAsync(d_geo_res_.get(), geo_res_tab_.data(), (size_t)nb * sizeof(GeoResShot), hipMemcpyHostToDevice, c.st));
     launch_geo_residual_batch(c.st, d_geo_res_.get(), nb, max_nrec, geo_ncomp_, par_.nSteps, geo_sums_);
-    launches_++;
+    cs_.launches++;
 }
 
 // the same with the data-conditioning chain (libCUFD.cu:353-457 as its commented lines compose it), on the MAIN stream:
@@ -265,7 +256,7 @@ void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
     else
         cond_->window(st, xpose2_, x.nrec, par_.dt, nullptr, nullptr, nullptr, 1.0f, 0.005f);
     launch_transpose(st, xpose2_, x.res, x.nrec, nSteps);  // [rec][it] -> [it][rec]: the adjoint source
-    launches_ += 8;
+    cs_.launches += 8;
 }
 
 // ---- what a forward pass leaves behind -----------------------------------------------------------------------------------
@@ -339,8 +330,8 @@ void Session::after_forward(Call &c, const ShotCtx &x) {
 // adjoint fields + all eight memory variables restart from zero (:503-515); the two pre-loop adjoint launches (:520-542) act on
 // all-zero arrays and change nothing.
 void Session::backward_init(const BwdLane &L) {
-    HIP_OK(hipMemsetAsync(L.bm.dvz_dz, 0, 8 * cells_ * sizeof(float), L.s));
-    HIP_OK(hipMemsetAsync(L.adj.vz, 0, 5 * cells_ * sizeof(float), L.s));
+    HIP_OK(hipMemsetAsync(L.bm.dvz_dz, 0, kMemArrays * cells_ * sizeof(float), L.s));
+    HIP_OK(hipMemsetAsync(L.adj.vz, 0, kFieldArrays * cells_ * sizeof(float), L.s));
 }
 
 // HIP-event pair for this step's k_bwd_b launch (option probe: every probe-th step), or null
@@ -353,10 +344,16 @@ void Session::collect_probes(Call &c) {  // after a synchronisation of the main 
     for (int k = 0; k < c.n_probe; k++) {
         float ms = 0.f;
         HIP_OK(hipEventElapsedTime(&ms, probe_ev_[2 * k], probe_ev_[2 * k + 1]));
-        probe_us_ += 1e3 * ms;
-        probe_calls_++;
+        cs_.probe_us += 1e3 * ms;
+        cs_.probe_calls++;
     }
     c.n_probe = 0;
+}
+
+Grid Session::step_grid(const KernelOptions &opt, int it) const {
+    Grid gs = g_;
+    if (opt.img_every > 1) gs.dt_img = (it % opt.img_every == 0) ? (float)opt.img_every * g_.dt : 0.0f;
+    return gs;
 }
 
 // one backward time step, the reference's order (libCUFD.cu:545-631)
@@ -374,8 +371,7 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
         lr = x.line;
         lr.res = res_t;
     }
-    Grid gs = g;  // this step's imaging weight (option img_every)
-    if (opt.img_every > 1) gs.dt_img = (it % opt.img_every == 0) ? (float)opt.img_every * g.dt : 0.0f;
+    const Grid gs = step_grid(opt, it);
     if (opt.bwd_fuse != 0) {
         const Event *ev = probe_pair(c, it);
         Fields adj = L.adj;  // (the adjoint maps follow the shot's lane; the residual enters inside k_bwd_b, which marks the channels' segments)
@@ -384,14 +380,14 @@ void Session::backward_step(Call &c, const ShotCtx &x, const BwdLane &L, int it)
         launch_bwd_b(L.s, gs, opt, x.fld, L.bm, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, (float)sh.src_rxz, sg, adj, L.acc, lr, ev ? ev[0].get() : nullptr,
                      ev ? ev[1].get() : nullptr);
         if (!inj_inl) inject_column(x, L, res_t);
-        launches_ += inj_inl ? 2 : 3;
+        cs_.launches += inj_inl ? 2 : 3;
     } else {  // the reference's launch structure
         launch_velocity_rev(L.s, gs, opt, x.fld, md_, pc_, frame_t, sh.z_src, sh.x_src, (float)sh.src_rxz, sg, L.adj, L.acc);
         launch_stress_rev(L.s, gs, opt, x.fld, md_, pc_, frame_t, sh.z_src, sh.x_src, amp, L.adj, L.acc);
         launch_velocity_adj(L.s, g, opt, L.adj, L.bm, md_, pc_);
         inject_column(x, L, res_t);
         launch_stress_adj(L.s, g, opt, L.adj, L.bm, md_, pc_);
-        launches_ += 5;
+        cs_.launches += 5;
     }
 }
 
@@ -417,8 +413,8 @@ void Session::backward(Call &c, const ShotCtx &x) {
     if (!looped)
         for (int it = par_.nSteps - 2; it >= 0; it--) backward_step(c, x, L, it);
     HIP_OK(hipEventRecord(ev_[3], st));
-    bwd_steps_ += (long long)(par_.nSteps - 1);
-    bwd_ms_ += bracket_ms(2, st);
+    cs_.bwd_steps += (long long)(par_.nSteps - 1);
+    cs_.bwd_ms += bracket_ms(2, st);
     collect_probes(c);
     if (looped) persist_check_pass(pk_);
 }
@@ -426,19 +422,18 @@ void Session::backward(Call &c, const ShotCtx &x) {
 // ---- stream schedule: up to fwd_lanes forward passes side by side (their kernel-boundary gaps and tails fill each other:
 // x1.28 on the forward loops with three lanes), then their backward passes one after the other (two of them together lose
 // 13-20 %)
-void Session::run_streams(Call &c) {
+void Session::run_streams(Call &c, int n_lanes) {
     hipStream_t st = c.st;
     const int nSteps = par_.nSteps;
-    int n_lanes = c.opt.pair_fwd ? c.opt.fwd_lanes : 1;
-    n_lanes = std::max(1, std::min(std::min(n_lanes, c.group_size), (int)kMaxLanes));
-    if (c.if_res) n_lanes = obs_->max_group((size_t)std::max(1, survey_.max_nrec) * nSteps * sizeof(float) * (size_t)geo_ncomp_, n_lanes);
     if (n_lanes >= 2) ensure_lanes(n_lanes, c.with_adj);
     if (c.ph_every > 0) ph_begin(c, n_lanes);  // (before ev_[0]: the extra lanes start after the sets are zeroed)
     for (int is = 0; is < c.group_size;) {
         const int np = std::min(n_lanes, c.group_size - is);
         ShotCtx ctx[kMaxLanes];
-        ctx[0] = make_ctx(c, is, 0, st);
-        for (int k = 1; k < np; k++) ctx[k] = make_ctx(c, is + k, k, xl_[k].stream);
+        for (int k = 0; k < np; k++) {
+            ctx[k] = make_ctx(c, is + k, stream_lane(k, st));
+            if (c.ph_every > 0) ctx[k].ph = ph_set_[k].get();  // armed: the accumulator set of the lane
+        }
 
         // forward time loop(s), libCUFD.cu:268-332
         HIP_OK(hipEventRecord(ev_[0], st));
@@ -452,15 +447,12 @@ void Session::run_streams(Call &c) {
             if (inl[k]) record_column(ctx[k], nSteps - 1);
         if (c.if_res && !cond_on_)
             for (int k = 0; k < np; k++) residual(ctx[k]);
-        for (int k = 1; k < np; k++) {  // join: the main stream continues when the extra lanes are done
-            HIP_OK(hipEventRecord(xl_[k].join, xl_[k].stream));
-            HIP_OK(hipStreamWaitEvent(st, xl_[k].join, 0));
-        }
+        batch_join(st, np);
         if (c.if_res && cond_on_)
             for (int k = 0; k < np; k++) residual_conditioned(c, ctx[k]);
         HIP_OK(hipEventRecord(ev_[1], st));
-        fwd_steps_ += (long long)np * (nSteps - 1);
-        fwd_ms_ += bracket_ms(0, st);
+        cs_.fwd_steps += (long long)np * (nSteps - 1);
+        cs_.fwd_ms += bracket_ms(0, st);
         obs_->release_all();  // the residuals are formed: the group's observed gathers may leave HBM again
 
         for (int k = 0; k < np; k++) after_forward(c, ctx[k]);
@@ -517,7 +509,7 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
     if (c.with_adj) {
         const GradOut o = grad_out(grad_Lambda, grad_Mu, grad_Den);
         launch_finalize_gradients(st, g_, md_, acc_, o.dev[0], o.dev[1], o.dev[2]);
-        launches_++;
+        cs_.launches++;
         copy_staged(o, st);
     }
     if (c.ph_every > 0) {  // the sets summed in lane order, the constants of pseudo_hessian.hpp
@@ -527,7 +519,7 @@ void Session::write_outputs(Call &c, float *misfit, float *grad_Lambda, float *g
         const double mdt = 1e6 * (double)g_.dt;
         launch_pseudo_hessian_finalize(st, g_, sets, cells_, 2.0 * mdt * mdt, mdt * mdt, (double)g_.dt * (double)g_.dt, ph_out_.get(), ph_out_.get() + dense,
                                        ph_out_.get() + 2 * dense);
-        launches_++;
+        cs_.launches++;
         ph_valid_ = true;
     }
     if (c.if_res && misfit) read_misfit(c, misfit, true);
@@ -582,14 +574,7 @@ Session::Call Session::begin_call(hipStream_t ext_stream, int group_size, const 
     if (!ext_stream) order_after_null_stream(c.st);
     c.group_size = group_size;
     c.shot_ids = shot_ids;
-    last_exact_ = false;
-    launches_ = 0;
-    fwd_ms_ = bwd_ms_ = 0.0;
-    probe_us_ = 0.0;
-    probe_calls_ = 0;
-    fwd_steps_ = bwd_steps_ = persist_steps_ = 0;
-    quiet_active_ = quiet_total_ = 0;
-    quiet_last_ = nullptr;
+    cs_ = CallStats{};
     check_shot_ids(group_size, shot_ids);
     return c;
 }
@@ -634,28 +619,30 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
             for_active([&](int comp, int) { (void)obs_->acquire(shot_ids[is], survey_.shots[shot_ids[is]].nrec, c.st, comp); });
     obs_->release_all();
 
-    // Batch sizes from the Infinity-Cache budget: a forward batch keeps 5 fields per shot + 5 media arrays resident, a backward
-    // batch 15 arrays per shot + 5 (2000x500: 7 and 2; a 101x201 notebook problem: all its shots at once).  Where fewer than three
-    // backward passes fit (two-launch step: two) the stream schedule runs them one by one -- as the persistent loop where it is
-    // eligible: measured fwd+adj at 1000 steps, batched / streams in Gcell-updates/s: 2000x500 (2 fit) 73.5 / 79.6, 1500x500 (3) 77.1 /
-    // 75.0, 1000x700 (3) 73.2 / 72.5, 2000x300 (4) 73.7 / 66.1, 1000x500 (5) 69.0 / 63.9 (profiles/r05_other_grids.txt).
-    const double arr_mb = (double)cells_ * sizeof(float) / 1.0e6, budget = (double)c.opt.batch_mb;
-    int Bf = (int)((budget / arr_mb - 5.0) / 5.0), Bb = (int)((budget / arr_mb - 5.0) / 15.0);
-    const int bb_min = c.opt.bwd_fuse == 4 ? 3 : 2;
-    const bool batched = c.opt.bwd_fuse != 0 && group_size >= 1 &&
-                         (c.opt.batch == 1 || (c.opt.batch == 2 && (c.with_adj ? Bb >= bb_min : Bf >= 8)));  // forward-only calls: streams until kernels are launch-bound
-    last_batched_ = batched;
-    if (batched) {
-        if (c.opt.batch_f > 0) Bf = c.opt.batch_f;
-        if (c.opt.batch_b > 0) Bb = c.opt.batch_b;
-        Bf = std::max(1, std::min(std::min(Bf, 32), group_size));
-        if (c.if_res) Bf = obs_->max_group(gather_bytes, Bf);
-        Bb = std::max(1, std::min(Bb, Bf));
-        if (!c.opt.pair_fwd) Bf = Bb = 1;
-        run_batched(c, Bf, Bb);
-    } else {
-        run_streams(c);
-    }
+    // The schedule (schedule.hpp plan_schedule; tests/native/schedule_check.cpp pins the grids named here).  Backward passes that fit
+    // the budget together: 2000x500: 2 (and 7 forward); a 101x201 notebook problem: all its shots at once.  Where fewer than three fit
+    // the stream schedule runs them one by one -- as the persistent loop where it is eligible: measured fwd+adj at 1000 steps, batched /
+    // streams in Gcell-updates/s: 2000x500 (2 fit) 73.5 / 79.6, 1500x500 (3) 77.1 / 75.0, 1000x700 (3) 73.2 / 72.5, 2000x300 (3) 73.7 /
+    // 66.1, 1000x500 (5) 69.0 / 63.9 (profiles/r05_other_grids.txt).
+    ScheduleIn in;
+    in.array_bytes = cells_ * sizeof(float);
+    in.batch = c.opt.batch;
+    in.batch_f = c.opt.batch_f;
+    in.batch_b = c.opt.batch_b;
+    in.batch_mb = c.opt.batch_mb;
+    in.bwd_fuse = c.opt.bwd_fuse;
+    in.pair_fwd = c.opt.pair_fwd;
+    in.fwd_lanes = c.opt.fwd_lanes;
+    in.batch_split = c.opt.batch_split;
+    in.group_size = group_size;
+    in.with_adj = c.with_adj;
+    in.if_res = c.if_res;
+    const Schedule s = plan_schedule(in, [&](int want) { return obs_->max_group(gather_bytes, want); });
+    last_batched_ = s.batched;
+    if (s.batched)
+        run_batched(c, s);
+    else
+        run_streams(c, s.lanes);
     write_outputs(c, misfit, grad_Lambda, grad_Mu, grad_Den, grad_stf);
     if (!async) {
         HIP_OK(hipStreamSynchronize(c.st));
@@ -663,12 +650,12 @@ void Session::run(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad
         HIP_OK(hipEventRecord(ev_order_, c.st));
         HIP_OK(hipStreamWaitEvent(nullptr, ev_order_, 0));
     }
-    if (quiet_last_) {  // how much of the grid the last shot's forward field reached (sepfwi_stats)
+    if (cs_.quiet_last) {  // how much of the grid the last shot's forward field reached (sepfwi_stats)
         std::vector<unsigned int> bits((size_t)g_.qn);
-        HIP_OK(hipMemcpyAsync(bits.data(), quiet_last_ + g_.qn, bits.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c.st));
+        HIP_OK(hipMemcpyAsync(bits.data(), cs_.quiet_last + g_.qn, bits.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c.st));
         HIP_OK(hipStreamSynchronize(c.st));
-        for (unsigned int w : bits) quiet_active_ += __builtin_popcount(w);
-        quiet_total_ = (long long)(g_.nzc - 4) * ((g_.nx + 63) / 64);
+        for (unsigned int w : bits) cs_.quiet_active += __builtin_popcount(w);
+        cs_.quiet_total = (long long)(g_.nzc - 4) * ((g_.nx + 63) / 64);
     }
     end_call(c, false);  // (synchronised above, or left running: async)
     last_calc_ = calc_id;

@@ -84,3 +84,20 @@ def test_owning_buffers_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     out = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_schedule_and_lane_layouts_under_asan_ubsan(tmp_path):
+    """The schedule of a call, the sub-batches of a batch and the lane layouts (csrc/schedule.cpp): over a dense sweep of array sizes,
+    group sizes, call kinds, options and store caps the schedule is the one Session::run used to work out in place (kept in the check
+    word for word); the grids that the comment in Session::run names get the backward batch sizes it states, the notebook problem all
+    its 19 shots at once; the sub-batches of every batch of 1 ... 64 shots are non-empty, contiguous, cover it and carry the facts of
+    exactly their shots; the layout views give the offsets they replace."""
+    exe = str(tmp_path / "schedule_check")
+    src = [os.path.join(ROOT, "tests", "native", "schedule_check.cpp"), os.path.join(ROOT, "sep-2023_amd", "csrc", "schedule.cpp")]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-o", exe] + src)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([exe, "1"], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+    assert int(out.stdout.split()[1]) > 10 ** 7, out.stdout      # the sweep ran in full
