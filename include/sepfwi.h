@@ -193,8 +193,8 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
  *       NULL) is that value, as sepfwi_cufd(calc_id 1) reports it.
  * Every receiver geometry and parameter key of the forward pass applies (das_fiber, directional channels, das_gauge_length, misfit_w_*).
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
- * shot list; a live data-conditioning key; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  No
- * gradient of the source time function is returned.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
+ * shot list; a live data-conditioning key; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
+ * gradient of the source time function is returned by sepfwi_adjoint_exact_src (below), not here.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
  * are read but never written; sepfwi_get_stats afterwards describes this call.  Schedule: one shot after the other on the call's
  * stream, synchronous, two launches and one injection per backward time step; the persistent backward loop and the batched schedule
  * are not used (sepfwi_loop_status says so), options img_every and quiet_skip are not consulted.  A process that never calls this
@@ -203,6 +203,32 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
 int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
                          const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
                          const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream);
+
+/*
+ * Extension (no counterpart in the reference; no reference run pins it): the source time function in Born modelling and in the exact
+ * adjoint.  The wavefield is exactly linear in the source, J_s = F (1500^2 dt) T with F the map from injected amplitudes to gathers and T
+ * the end taper of the source rows (sepfwi_stf_taper, ratio 0.001: a pointwise window, its own transpose); column nSteps-1 of the
+ * source never enters the forward pass.  The yardstick is the forward operator itself: J_s ds is the gathers of stf = ds.
+ * sepfwi_born and sepfwi_adjoint_exact are these two functions with the source arguments NULL, launch for launch and bit for bit.
+ *   dStf    (group_size, nSteps) float32, host or device; row i belongs to shot_ids[i] -- the local layout of sepfwi_cufd's grad_stf.  A
+ *           shot's source couples to that shot only.  The scattered field gets 1500^2 T[it] dStf[it] dt at the source cell where the
+ *           background gets its amplitude: the gathers are J [v; ds] = J_m v + J_s ds.  dLambda, dMu, dDen may then be all NULL (v = 0).
+ *   g_stf   (group_size, nSteps) float32, host or device, may be NULL; the same layout, so the operator is square.  Overwritten with
+ *           the source block of the result:  J_s^T w  /  the fourth block of [P; I] J^T W J [P v; ds]  /  d misfit / d stf =
+ *           J_s^T W (syn - obs), by the mode.  Column nSteps-1 is 0.  Formed inside the transposed time loop's own launches: a call
+ *           with g_stf issues the launches of the call without it.
+ * sepfwi_born_src: the arguments of sepfwi_born, then dStf.  SEPFWI_EINVAL before anything is touched: a partial v; no v and no dStf;
+ * dStf together with hv_* (the reference's backward pass is not the transpose of J: use sepfwi_adjoint_exact_src).
+ * sepfwi_adjoint_exact_src: the arguments of sepfwi_adjoint_exact, then dStf and g_stf.  v (all three) or dStf or both: the product;
+ * w_*: J^T w; none of v, dStf, w: the gradient mode.  SEPFWI_EINVAL before anything is touched: dStf together with w_*; a partial v.
+ */
+int sepfwi_born_src(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
+                    const int *shot_ids, const char *para_fname, void *hip_stream, const float *dStf);
+int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                             const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
+                             const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream,
+                             const float *dStf, float *g_stf);
 
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);

@@ -55,8 +55,12 @@ __device__ __forceinline__ VelD velocity_derivs(const Grid &g, const Fields &f, 
 
 }  // namespace
 
-template <bool SAVE>
-__global__ __launch_bounds__(MAXT) void k_born_stress(Grid g, BornArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp) {
+// SRC: the scattered field has a source term of its own (a perturbation ds of the source time function: dsrc_amp = scale T ds[it] dt,
+// added to dszz and dsxx of the source cell where the background gets src_amp).  Without one the instance adds nothing -- not even a
+// +0.0f, which would turn a -0 into +0.
+template <bool SAVE, bool SRC>
+__global__ __launch_bounds__(MAXT) void k_born_stress(Grid g, BornArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp,
+                                                      float dsrc_amp) {
     const Fields f = fields_of(b.state, b.n), df = fields_of(b.dstate, b.n);
     const PmlMem m = b_mem(b.state, b.n), dm = b_mem(b.dstate, b.n);
     const Media md = media_of(b.media, b.n);
@@ -117,9 +121,17 @@ __global__ __launch_bounds__(MAXT) void k_born_stress(Grid g, BornArgs b, float 
         dm.dvz_dx[i] = e_s;
     }
     const float l2m = lam + 2.0f * mu, dl2m = dlam + 2.0f * dmu;
-    // propagation term, then the coupling term (no source: its amplitude does not depend on the model)
-    df.szz[i] = (dszz0 + (l2m * E.vz_z + lam * E.vx_x) * g.dt) + (dl2m * D.vz_z + dlam * D.vx_x) * g.dt;
-    df.sxx[i] = (dsxx0 + (lam * E.vz_z + l2m * E.vx_x) * g.dt) + (dlam * D.vz_z + dl2m * D.vx_x) * g.dt;
+    // propagation term, then the coupling term (the background's source amplitude does not depend on the model), then the source term
+    float dszz = (dszz0 + (l2m * E.vz_z + lam * E.vx_x) * g.dt) + (dl2m * D.vz_z + dlam * D.vx_x) * g.dt;
+    float dsxx = (dsxx0 + (lam * E.vz_z + l2m * E.vx_x) * g.dt) + (dlam * D.vz_z + dl2m * D.vx_x) * g.dt;
+    if constexpr (SRC) {
+        if (z == (zx_src >> 16) && x == (zx_src & 0xffff)) {
+            dszz += dsrc_amp;
+            dsxx += dsrc_amp;
+        }
+    }
+    df.szz[i] = dszz;
+    df.sxx[i] = dsxx;
     df.sxz[i] = (dsxz0 + amu * (E.vx_z + E.vz_x) * g.dt) + damu * (D.vx_z + D.vz_x) * g.dt;
 }
 
@@ -212,10 +224,11 @@ __global__ void k_born_media(Grid g, const float *__restrict__ Mu_in, const floa
     dbb[i] = b_d;
 }
 
-void launch_born_stress(hipStream_t st, const Grid &g0, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp) {
+void launch_born_stress(hipStream_t st, const Grid &g0, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
+                        const float *dsrc_amp) {
     const Grid g = tiled(g0, o, 0);  // the forward kernels' tiling: the background takes the paths of a plain forward pass
-    auto k = frame_t ? k_born_stress<true> : k_born_stress<false>;
-    hipLaunchKernelGGL(k, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, (z_src << 16) | x_src, src_amp);
+    auto k = dsrc_amp ? (frame_t ? k_born_stress<true, true> : k_born_stress<false, true>) : (frame_t ? k_born_stress<true, false> : k_born_stress<false, false>);
+    hipLaunchKernelGGL(k, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, (z_src << 16) | x_src, src_amp, dsrc_amp ? *dsrc_amp : 0.0f);
 }
 
 void launch_born_velocity(hipStream_t st, const Grid &g0, const KernelOptions &o, const BornArgs &b) {

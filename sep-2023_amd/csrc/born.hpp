@@ -10,10 +10,15 @@
 // all 0 outside [2, n-3]^2, where the averages are constants.
 //
 // Scattered field d(vz, vx, szz, sxx, sxz) with eight C-PML memories of its own: same stencils, same recursion (a, b, 1/K do not
-// depend on the model), no source term, and the cross terms with the background's C-PML-modified derivatives D~ of the same step:
+// depend on the model), no source term unless the call perturbs the source time function (below), and the cross terms with the
+// background's C-PML-modified derivatives D~ of the same step:
 //   dszz += dt [(lam + 2 mu) D~z dvz + lam D~x dvx] + dt [(dlam + 2 dmu) D~z vz + dlam D~x vx]            (dsxx likewise)
 //   dsxz += dt [amu (D~z dvx + D~x dvz)]            + dt [damu (D~z vx + D~x vz)]
 //   dvz  += dt [ba (D~z dszz + D~x dsxz)]           + dt [dba (D~z szz + D~x sxz)]                        (dvx likewise with bb / dbb)
+// Source block (sepfwi_born_src, dStf): the wavefield is linear in the source time function, so a perturbation ds of it is a source of
+// the scattered field -- dszz and dsxx of the source cell get 1500^2 T[it] ds[it] dt (T: the end taper of the source rows) after the
+// update of step it, where the background gets its amplitude.  J [v; ds] = J_m v + J_s ds in one pass; J_s ds alone is the forward
+// operator with stf = ds (tests/stf_ref.py).  Without ds the kernel instance is the one that adds nothing.
 // The background is advanced by the forward bodies themselves (stress_body / velocity_body, kernels_bodies.hpp): bit for bit a plain
 // forward pass, boundary-frame save included.
 //
@@ -44,8 +49,10 @@ struct BornArgs {
 // dense (nz, nx) v + the session's media -> the five perturbed-media arrays
 void launch_born_media(hipStream_t st, const Grid &g, const float *Mu_in, const float *dLam_in, const float *dMu_in, const float *dDen_in, Media md,
                        float *dmedia, size_t n);
-// one time step: stresses (frame_t non-null: the background's boundary frame of this step is saved first), then velocities
-void launch_born_stress(hipStream_t st, const Grid &g, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp);
+// one time step: stresses (frame_t non-null: the background's boundary frame of this step is saved first; dsrc_amp non-null: the
+// scattered field's own source amplitude of this step, the instance without one writes the bits it always wrote), then velocities
+void launch_born_stress(hipStream_t st, const Grid &g, const KernelOptions &o, const BornArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
+                        const float *dsrc_amp = nullptr);
 void launch_born_velocity(hipStream_t st, const Grid &g, const KernelOptions &o, const BornArgs &b);
 
 }  // namespace sepfwi

@@ -129,24 +129,38 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
     });
 }
 
-int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
-                const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
-                const int *shot_ids, const char *para_fname, void *hip_stream) {
+int sepfwi_born_src(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
+                    const int *shot_ids, const char *para_fname, void *hip_stream, const float *dStf) {
     return guarded([&] {
         if (!para_fname) throw std::invalid_argument("para_fname is NULL");
         if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
-        if (!dLambda || !dMu || !dDen) throw std::invalid_argument("born: dLambda, dMu and dDen must not be NULL");
+        const int n_v = (dLambda ? 1 : 0) + (dMu ? 1 : 0) + (dDen ? 1 : 0);
+        if (!dStf && n_v != 3) throw std::invalid_argument("born: dLambda, dMu and dDen must not be NULL");
+        if (dStf && n_v != 0 && n_v != 3) throw std::invalid_argument("born: with dStf, dLambda, dMu, dDen must be all NULL or all set");
         if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
         const int n_hv = (hv_Lambda ? 1 : 0) + (hv_Mu ? 1 : 0) + (hv_Den ? 1 : 0);
         if (n_hv != 0 && n_hv != 3) throw std::invalid_argument("born: hv_Lambda, hv_Mu, hv_Den must be all NULL (J v only) or all set");
+        if (dStf && n_hv == 3)
+            throw std::invalid_argument("born: the product with dStf needs the exact adjoint (sepfwi_adjoint_exact_src): the reference's backward pass is "
+                                        "not the transpose of J");
         std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
-        s->born(d_ett, d_vx, d_vz, hv_Lambda, hv_Mu, hv_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids, (hipStream_t)hip_stream);
+        s->born(d_ett, d_vx, d_vz, hv_Lambda, hv_Mu, hv_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids, (hipStream_t)hip_stream,
+                false, dStf, nullptr);
     });
 }
 
-int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
-                         const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
-                         const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream) {
+int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
+                const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
+                const int *shot_ids, const char *para_fname, void *hip_stream) {
+    return sepfwi_born_src(d_ett, d_vx, d_vz, hv_Lambda, hv_Mu, hv_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, gpu_id, group_size, shot_ids, para_fname,
+                           hip_stream, nullptr);
+}
+
+int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                             const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
+                             const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream,
+                             const float *dStf, float *g_stf) {
     return guarded([&] {
         if (!para_fname) throw std::invalid_argument("para_fname is NULL");
         if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
@@ -155,14 +169,22 @@ int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_D
         if (n_v != 0 && n_v != 3) throw std::invalid_argument("adjoint_exact: dLambda, dMu, dDen must be all NULL or all set");
         const bool have_w = w_ett || w_vx || w_vz;
         if (n_v == 3 && have_w) throw std::invalid_argument("adjoint_exact: either v (the product) or w (J^T w), not both");
+        if (dStf && have_w) throw std::invalid_argument("adjoint_exact: either dStf (the product) or w (J^T w), not both");
         if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
         std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
-        if (n_v == 3)
+        if (n_v == 3 || dStf)
             s->born(nullptr, nullptr, nullptr, g_Lambda, g_Mu, g_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids,
-                    (hipStream_t)hip_stream, true);
+                    (hipStream_t)hip_stream, true, dStf, g_stf);
         else
-            s->adjoint_exact(misfit, g_Lambda, g_Mu, g_Den, w_ett, w_vx, w_vz, Lambda, Mu, Den, stf, group_size, shot_ids, (hipStream_t)hip_stream);
+            s->adjoint_exact(misfit, g_Lambda, g_Mu, g_Den, w_ett, w_vx, w_vz, Lambda, Mu, Den, stf, group_size, shot_ids, (hipStream_t)hip_stream, g_stf);
     });
+}
+
+int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
+                         const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
+                         const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream) {
+    return sepfwi_adjoint_exact_src(misfit, g_Lambda, g_Mu, g_Den, w_ett, w_vx, w_vz, dLambda, dMu, dDen, Lambda, Mu, Den, stf, gpu_id, group_size, shot_ids,
+                                    para_fname, hip_stream, nullptr, nullptr);
 }
 
 void sepfwi_invalidate_observed(void) {

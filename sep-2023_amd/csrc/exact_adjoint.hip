@@ -181,8 +181,13 @@ __global__ __launch_bounds__(MAXT) void k_exact_a(Grid g, ExactArgs b, const flo
     exact_vt_apply(q, g, c, adj, m, md, pc);
 }
 
+// SRC: the transpose of the source add, a gather -- the lane that owns the source cell stores s_zz + s_xx of the adjoint stresses as they
+// stand between V^T and S^T of this step (this kernel reads them through its taps and never writes them) to g_amp_it.  They are loaded
+// with the taps, before the reverse-time body's first store, and stored after the last one: a store keeps later may-alias loads behind
+// it.  The instance without the gather is the kernel as it always was.
+template <bool SRC>
 __global__ __launch_bounds__(MAXT) void k_exact_b(Grid g, ExactArgs b, float *__restrict__ frame_t, int zx_src /* z<<16 | x */, float src_amp,
-                                                  int adjoint_only) {
+                                                  int adjoint_only, float *__restrict__ g_amp_it) {
     const Fields f = fields_of(b.fields, b.n), adj = fields_of(b.adj, b.n);
     const PmlMem m = mem_of(b.mem, b.n);
     const Media md = media_of(b.media, b.n);
@@ -190,9 +195,18 @@ __global__ __launch_bounds__(MAXT) void k_exact_b(Grid g, ExactArgs b, float *__
     const PmlCoef pc = coef_of(b.cz, b.cz + 6 * g.nzc, g.nzc, g.nx);
     const Cell c = my_cell(g);
     const StIn q = exact_st_load(g, c, adj, m, md, pc);
+    bool at_src = false;
+    float g_amp = 0.0f;
+    if constexpr (SRC) {
+        at_src = c.z == (zx_src >> 16) && c.x == (zx_src & 0xffff);
+        if (at_src) g_amp = adj.szz[c.i] + adj.sxx[c.i];
+    }
     if (!adjoint_only)  // launch-uniform
         stress_body<false, false>(g, c, f, m, md, pc, frame_t, zx_src >> 16, zx_src & 0xffff, src_amp, adj, AccG{acc}, LineRec{});
     exact_st_apply(q, g, c, adj, m, md, pc);
+    if constexpr (SRC) {
+        if (at_src) *g_amp_it = g_amp;
+    }
 }
 
 // The transposes of k_born_media's maps on Omega (exact_adjoint.hpp), in the launch shape of k_finalize_gradients: dense (nz, nx) outputs.
@@ -235,10 +249,12 @@ void launch_exact_a(hipStream_t st, const Grid &g0, const KernelOptions &o, cons
 }
 
 void launch_exact_b(hipStream_t st, const Grid &g0, const KernelOptions &o, const ExactArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
-                    bool adjoint_only) {
+                    bool adjoint_only, float *g_amp_it) {
     const Grid g = tiled(g0, o, 1);  // the backward kernels' tiling: the reverse-time bodies take the paths of a gradient call
     const int zx = adjoint_only ? 0 : (z_src << 16) | x_src;
-    hipLaunchKernelGGL(k_exact_b, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, zx, src_amp, adjoint_only ? 1 : 0);
+    if (adjoint_only) g_amp_it = nullptr;  // (no amplitude follows the last velocity update: the priming launch gathers nothing)
+    auto k = g_amp_it ? k_exact_b<true> : k_exact_b<false>;
+    hipLaunchKernelGGL(k, dim3(g.nblk), dim3(BX * g.bz), 0, st, g, b, frame_t, zx, src_amp, adjoint_only ? 1 : 0, g_amp_it);
 }
 
 void launch_exact_finalize(hipStream_t st, const Grid &g, Media md, ImgAcc acc, float *gLam, float *gMu, float *gDen) {

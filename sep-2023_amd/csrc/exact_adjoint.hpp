@@ -37,7 +37,17 @@
 //   gLambda = 1e6 acc_lam      gMu = 1e6 (acc_mu + sum over the four amu points p touching the cell of (amu_p^2 / 4 mu^2) acc_xz_p), 0 where amu_p = 0
 //   gDen    = -(ba^2 / 2) acc_a at (z, x) and (z-1, x)  -  (bb^2 / 2) acc_b at (z, x) and (z, x-1)
 // and 0 elsewhere.  Accumulators exist on the interior only; a perturbation on Omega couples only at staggered points inside it, and
-// every point a cell of Omega gathers from is an interior one -- no edge test is left.  No gradient of the source time function.
+// every point a cell of Omega gathers from is an interior one -- no edge test is left.
+//
+// Source block (sepfwi_adjoint_exact_src): the forward pass adds amp[it] = 1500^2 T[it] stf[it] dt to szz and sxx of the source cell after
+// S of step it = 0 ... nSteps-2 (T: the end taper of the source rows, a pointwise window, so its own transpose).  The transpose of that
+// add is a gather of the adjoint stresses at the source cell as they stand after V^T (k_exact_a) and before S^T of the same step; S^T
+// reads them through its taps and never writes them, so ONE lane of k_exact_b(it) stores  g_amp[it] = s_zz + s_xx  -- no launch of its
+// own, a plain vector store.  The adjoint-only k_exact_b that primes column nSteps-1 stores nothing: no amplitude follows the last
+// velocity update.  The adjoint fields carry the sign of a gradient call's residual (the adjoint source is -w, the imaging condition
+// takes the other minus), hence on the host
+//   gStf[it] = -1500^2 dt T[it] g_amp[it]   for it <= nSteps-2,      gStf[nSteps-1] = 0
+// one row per shot of the call (a shot's source couples to that shot only), the layout of sepfwi_cufd's grad_stf.
 //
 // A translation unit of its own (exact_adjoint.hip): the field kernels are untouched, and a process that never calls
 // sepfwi_adjoint_exact issues exactly the launches and allocates exactly the memory it did before.  The persistent backward loop and
@@ -62,9 +72,10 @@ struct ExactArgs {
 };
 
 void launch_exact_a(hipStream_t st, const Grid &g, const KernelOptions &o, const ExactArgs &b, const float *frame_t);
-// adjoint_only: S^T and the Q update alone (no reverse-time body, no imaging; frame_t may be null)
+// adjoint_only: S^T and the Q update alone (no reverse-time body, no imaging; frame_t may be null, g_amp_it is not written)
+// g_amp_it non-null: one lane stores the source gather of this step there (the header comment, "Source block")
 void launch_exact_b(hipStream_t st, const Grid &g, const KernelOptions &o, const ExactArgs &b, float *frame_t, int z_src, int x_src, float src_amp,
-                    bool adjoint_only);
+                    bool adjoint_only, float *g_amp_it = nullptr);
 // dense (nz, nx) outputs, zero outside Omega
 void launch_exact_finalize(hipStream_t st, const Grid &g, Media md, ImgAcc acc, float *gLam, float *gMu, float *gDen);
 // P_Omega in place on k dense (nz, nx) arrays at stride `dense`

@@ -55,15 +55,17 @@ class Session {
     void pseudo_hessian_get(float *hLambda, float *hMu, float *hDen);
     // Born modelling and the Gauss-Newton product (session_born.cpp, sepfwi_born): the scattered gathers of v = (dLambda, dMu, dDen),
     // shot after shot as [nrec][nSteps], each output optional; hv_* all null (J v only) or all set (J^T W J v, summed over the shots)
+    // dStf (sepfwi_born_src; (group_size, nSteps), row i the call's shot i, host or device): the scattered field's own source term, J [v; ds];
+    // v may then be absent (all three null).  hv_stf (exact only): the source block of the product, the layout of dStf
     void born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
               const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
-              hipStream_t ext_stream, bool exact = false);
+              hipStream_t ext_stream, bool exact = false, const float *dStf = nullptr, float *hv_stf = nullptr);
     // The exact discrete adjoint (exact_adjoint.hpp, session_exact.cpp, sepfwi_adjoint_exact): g = J^T w for the caller's w (any of
     // w_ett, w_vx, w_vz set; gathers as born() writes them), or, with all of them null, the exact gradient on Omega of the session's
     // misfit and the misfit itself.  (The product P J^T W J P v is born(..., exact = true).)
     void adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
                        const float *Lambda, const float *Mu, const float *Den, const float *stf, int group_size, const int *shot_ids,
-                       hipStream_t ext_stream);
+                       hipStream_t ext_stream, float *g_stf = nullptr);  // g_stf: the source block J_s^T (.), (group_size, nSteps), or null
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
@@ -186,8 +188,9 @@ class Session {
     Grid step_grid(const KernelOptions &opt, int it) const;  // the grid with backward step it's imaging weight (option img_every)
     void backward(Call &c, const ShotCtx &x);
     // the exact transposed time loop of one shot and its finalisation on Omega (session_exact.cpp); the persistent loop is not used
-    void backward_exact(Call &c, const ShotCtx &x);
+    void backward_exact(Call &c, const ShotCtx &x, bool src_gather = false);
     void write_outputs_exact(Call &c, float *g_Lambda, float *g_Mu, float *g_Den);
+    void write_stf_exact(Call &c, float *g_stf);
     // the same pass as ONE persistent launch (option bwd_fuse = 4; kernels.hip k_bwd_persist)
     struct Persist;
     bool persist_ready(const Call &c, const ShotCtx &x);

@@ -13,8 +13,12 @@
 // state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
 // exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
 // finalisation the exact one on Omega (exact_adjoint.hpp) -- the product P J^T W J P v, symmetric and non-negative.
+// dStf (sepfwi_born_src, sepfwi_adjoint_exact_src): the scattered field takes a source term of its own (born.hpp, "Source block"), so the
+// gathers are J_m v + J_s ds; v may be absent (the perturbed media are zeroed, k_born_media is not launched).  With exact and hv_stf the
+// product has a fourth block, J_s^T W J u (Session::write_stf_exact).  Without dStf every launch and every bit is what it was.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "born.hpp"
 #include "das_gauge.hpp"
@@ -29,9 +33,9 @@ namespace sepfwi {
 
 void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
-                   hipStream_t ext_stream, bool exact) {
+                   hipStream_t ext_stream, bool exact, const float *dStf, float *hv_stf) {
     std::lock_guard<std::mutex> lock(mu_);
-    const bool want_hv = hv_Lambda != nullptr;
+    const bool want_hv = hv_Lambda != nullptr, have_v = dLambda != nullptr;
     // refusals first: nothing is touched
     if (want_hv && cond_on_)
         throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit (if_win / filter / if_cross_misfit / if_src_update); "
@@ -51,20 +55,31 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     const int nSteps = par_.nSteps;
     if (!born_) born_ = dev<float>((kStateArrays + 5) * n);
     const float *dv[3] = {dLambda, dMu, dDen};
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < 3 && have_v; k++) {
         if (!exact && ptr_device(dv[k]) == gpu_id_) continue;  // (the exact product reads v on Omega only: it masks a copy)
         if (!born_stage_) born_stage_ = dev<float>(3 * dense);
         HIP_OK(hipMemcpyAsync(born_stage_.get() + (size_t)k * dense, dv[k], dense * sizeof(float), hipMemcpyDefault, st));
         dv[k] = born_stage_.get() + (size_t)k * dense;
     }
-    if (exact) {
+    if (exact && have_v) {
         launch_exact_mask(st, g_, born_stage_.get(), 3, dense);
         cs_.launches++;
     }
     const float *mu_dense = ptr_device(Mu) == gpu_id_ ? Mu : in_stage_ + dense;  // (prepare_media staged it there)
     float *dstate = born_.get(), *dmedia = born_.get() + kStateArrays * n;  // [5 scattered fields | 8 memories] like a lane's state, then the media
-    launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
-    cs_.launches++;
+    if (have_v) {
+        launch_born_media(st, g_, mu_dense, dv[0], dv[1], dv[2], md_, dmedia, n);
+        cs_.launches++;
+    } else {  // the source block alone: the perturbed media are zero
+        HIP_OK(hipMemsetAsync(dmedia, 0, 5 * n * sizeof(float), st));
+    }
+    // the perturbation of the source time function, row i the call's shot i: tapered like the source rows themselves (prepare_buffers)
+    std::vector<float> ds_rows;
+    if (dStf) {
+        ds_rows.resize((size_t)group_size * nSteps);
+        if (!ds_rows.empty()) HIP_OK(hipMemcpy(ds_rows.data(), dStf, ds_rows.size() * sizeof(float), hipMemcpyDefault));
+        for (int i = 0; i < group_size; i++) stf_taper(ds_rows.data() + (size_t)i * nSteps, nSteps, par_.dt, 0.001f);
+    }
 
     // which scattered gathers the call needs: the requested ones, and for the product the components with a weight
     int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
@@ -85,7 +100,8 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         for (int it = 0; it <= nSteps - 2; it++) {
             float *frame_t = want_hv ? x.frame + (size_t)it * 5 * (size_t)g_.frame_len : nullptr;
             const float amp = c.src_scale * x.stf_s[it] * par_.dt;
-            launch_born_stress(st, g_, c.opt, args, frame_t, x.sh->z_src, x.sh->x_src, amp);
+            const float damp = dStf ? c.src_scale * ds_rows[(size_t)is * nSteps + it] * par_.dt : 0.0f;  // (the expression of amp)
+            launch_born_stress(st, g_, c.opt, args, frame_t, x.sh->z_src, x.sh->x_src, amp, dStf ? &damp : nullptr);
             launch_born_velocity(st, g_, c.opt, args);
             cs_.launches += 2;
             if (x.nrec > 0 && comps) record_column(xd, it + 1);
@@ -112,13 +128,14 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         }
         cs_.fwd_ms += bracket_ms(0, st);  // (the time loop alone: ev_[1] was recorded before the gathers left)
         if (want_hv && exact)
-            backward_exact(c, x);
+            backward_exact(c, x, hv_stf != nullptr);
         else if (want_hv)
             backward(c, x);  // (a shot without channels: nothing is injected, as in a gradient call)
     }
-    if (want_hv && exact)
+    if (want_hv && exact) {
         write_outputs_exact(c, hv_Lambda, hv_Mu, hv_Den);
-    else if (want_hv)
+        if (hv_stf) write_stf_exact(c, hv_stf);
+    } else if (want_hv)
         write_outputs(c, nullptr, hv_Lambda, hv_Mu, hv_Den, nullptr);
     end_call(c, true);
 }

@@ -11,10 +11,13 @@
 //   column nSteps-1 injected, Q primed by k_exact_b in its adjoint-only form, and for it = nSteps-2 ... 0
 //   k_exact_a, injection of column it (it >= 1; the plans and k_inject of a gradient call), k_exact_b
 // with the imaging condition on every step (option img_every is not consulted).  After the last shot k_exact_finalize writes g on Omega.
-// The session's observed data, misfit parts and pseudo-Hessian state are read but never written; no gradient of the source time
-// function is formed.  Stats (fwd_ms, bwd_ms, launches, steps) and device_bytes describe this call.
+// Source block (g_stf set, sepfwi_adjoint_exact_src): one lane of k_exact_b(it) stores the adjoint stresses of the source cell into the
+// shot's row of the source-gradient buffer a gradient call uses (prepare_buffers allocates and zeroes it for every call with a backward
+// pass: nothing new is allocated, no launch is added per step), and write_stf_exact scales the rows on the host after the last shot.
+// The session's observed data, misfit parts and pseudo-Hessian state are read but never written.  Stats (fwd_ms, bwd_ms, launches, steps) and device_bytes describe this call.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "device_alloc.hpp"
 #include "exact_adjoint.hpp"
@@ -25,8 +28,10 @@
 
 namespace sepfwi {
 
-void Session::backward_exact(Call &c, const ShotCtx &x) {
+void Session::backward_exact(Call &c, const ShotCtx &x, bool src_gather) {
     hipStream_t st = c.st;
+    // the shot's row of source gathers g_amp (prepare_buffers zeroed it; column nSteps-1 is never written: no amplitude follows the last V)
+    float *g_amp = src_gather ? stf_grad_.get() + (size_t)x.is * par_.nSteps : nullptr;
     const BwdLane L{st, mem_, adj_, acc_};
     const int nSteps = par_.nSteps;
     const ExactArgs a{x.fld.vz, mem_.dvz_dz, adj_.vz, md_.lam, acc_.lam, pc_.a_z, cells_};
@@ -45,7 +50,7 @@ void Session::backward_exact(Call &c, const ShotCtx &x) {
             inject_column(x, L, x.res + (size_t)it * x.nres);
             cs_.launches++;
         }
-        launch_exact_b(st, g_, c.opt, a, frame_t, x.sh->z_src, x.sh->x_src, amp, false);
+        launch_exact_b(st, g_, c.opt, a, frame_t, x.sh->z_src, x.sh->x_src, amp, false, g_amp ? g_amp + it : nullptr);
         cs_.launches += 2;
     }
     HIP_OK(hipEventRecord(ev_[3], st));
@@ -61,9 +66,27 @@ void Session::write_outputs_exact(Call &c, float *g_Lambda, float *g_Mu, float *
     copy_staged(o, c.st);
 }
 
+// The source block of the result from the rows of source gathers (exact_adjoint.hpp): gStf[i][it] = -1500^2 dt T[it] g_amp[i][it], row i
+// the call's shot i, T the end taper of prepare_buffers applied to a trace of ones (a pointwise window is its own transpose).  A few
+// thousand floats: formed on the host, as write_outputs hands out grad_stf.
+void Session::write_stf_exact(Call &c, float *g_stf) {
+    const int nSteps = par_.nSteps;
+    std::vector<float> h((size_t)c.group_size * nSteps), T((size_t)nSteps, 1.0f);
+    if (h.empty()) return;
+    HIP_OK(hipMemcpyAsync(h.data(), stf_grad_.get(), h.size() * sizeof(float), hipMemcpyDeviceToHost, c.st));
+    HIP_OK(hipStreamSynchronize(c.st));
+    stf_taper(T.data(), nSteps, par_.dt, 0.001f);
+    for (int i = 0; i < c.group_size; i++)
+        for (int it = 0; it < nSteps; it++) {
+            float &q = h[(size_t)i * nSteps + it];
+            q = it <= nSteps - 2 ? (float)(-(double)c.src_scale * (double)par_.dt * (double)T[it] * (double)q) : 0.0f;
+        }
+    HIP_OK(hipMemcpy(g_stf, h.data(), h.size() * sizeof(float), hipMemcpyDefault));
+}
+
 void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
                             const float *Lambda, const float *Mu, const float *Den, const float *stf, int group_size, const int *shot_ids,
-                            hipStream_t ext_stream) {
+                            hipStream_t ext_stream, float *g_stf) {
     std::lock_guard<std::mutex> lock(mu_);
     const float *w[4] = {nullptr, w_vx, w_vz, w_ett};  // by component id
     const bool have_w = w_ett || w_vx || w_vz;
@@ -123,9 +146,10 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
         cs_.fwd_steps += (long long)(nSteps - 1);
         cs_.fwd_ms += bracket_ms(0, st);
         if (c.if_res) obs_->release_all();
-        backward_exact(c, x);
+        backward_exact(c, x, g_stf != nullptr);
     }
     write_outputs_exact(c, g_Lambda, g_Mu, g_Den);
+    if (g_stf) write_stf_exact(c, g_stf);
     if (c.if_res && misfit) read_misfit(c, misfit, false);  // as write_outputs forms it -- without touching what sepfwi_get_misfit_parts reports
     end_call(c, true);
 }

@@ -142,6 +142,22 @@ def _nrec_per_shot(para_fname, ids):
     return nrec
 
 
+def _local_rows(dStf, Stf, ids, gdev):
+    """A source perturbation in Stf's shape (nSrc, nSteps) -> its rows of Shot_ids, the library's local layout (row i: ids[i])."""
+    dStf = _f32c(dStf, "dStf")
+    if dStf.shape != Stf.shape:
+        raise ValueError("dStf must have the shape of Stf %s, got %s" % (tuple(Stf.shape), tuple(dStf.shape)))
+    return dStf[torch.as_tensor(ids, dtype=torch.long, device=dStf.device)].to(gdev).contiguous()
+
+
+def _global_rows(g_loc, Stf, ids):
+    """The library's (len(ids), nSteps) source block -> Stf's shape on the host (as gStf of backward): rows of Shot_ids scattered (a shot
+    named twice adds up), all other rows zero."""
+    out = torch.zeros(tuple(Stf.shape), dtype=torch.float32)
+    out.index_add_(0, torch.as_tensor(ids, dtype=torch.long), g_loc.cpu())
+    return out
+
+
 class _FwiOps:
     """Module object: fwi_ops.forward / backward / obscalc."""
 
@@ -213,11 +229,12 @@ class _FwiOps:
         return i
 
     # -- reference surface -------------------------------------------------------------------
-    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0, exact_adjoint=False):
+    def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0, exact_adjoint=False, source_gradient=False):
         """-> [misfit(1,), gLambda, gMu, gDen, gStf]   (fwi_backward, Src/Torch_Fwi.cpp:38-104).
         Extension `exact_adjoint=True` (include/sepfwi.h, sepfwi_adjoint_exact): the same list, the gradients being the exact ones of
-        the misfit on Omega (0 outside) and gStf ZEROS -- the exact pass forms no gradient of the source time function.  One GPU, not
-        together with pseudo_hessian.
+        the misfit on Omega (0 outside) and gStf ZEROS unless `source_gradient=True`: then gStf is the exact d misfit / d Stf
+        (sepfwi_adjoint_exact_src), in Stf's shape with zero rows for shots not in Shot_ids.  One GPU, not together with
+        pseudo_hessian.
         Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
         shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
         and ranks like the gradients; under torch.distributed through ONE more all-reduce, of the fused [hL | hM | hD] buffer).
@@ -226,8 +243,10 @@ class _FwiOps:
         if exact_adjoint:
             if k:
                 raise ValueError("exact_adjoint and pseudo_hessian cannot be combined in one call")
-            m, gL, gM, gD = self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname)
-            return [m, gL, gM, gD, torch.zeros_like(_f32c(Stf, "Stf").cpu())]
+            m, gL, gM, gD, *gS = self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, with_source=bool(source_gradient))
+            return [m, gL, gM, gD, gS[0] if gS else torch.zeros_like(_f32c(Stf, "Stf").cpu())]
+        if source_gradient:
+            raise ValueError("source_gradient needs exact_adjoint=True (the reference's pass returns its own gStf)")
         kw = {"pseudo_hessian": k} if k else {}     # (not armed: _cufd is called exactly as the reference surface calls it)
         ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
         n = int(ids.numel())
@@ -303,7 +322,7 @@ class _FwiOps:
         return None
 
     # -- Born modelling and the Gauss-Newton product (sepfwi_born) -------------------------------
-    def _born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, with_hv):
+    def _born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, with_hv, dStf=None):
         if int(ngpu) != 1:
             raise ValueError("born / gauss_newton run on ONE GPU (ngpu = 1): the multi-GPU shot split is not implemented for them")
         if _dist.active():
@@ -314,8 +333,13 @@ class _FwiOps:
             if c not in comp_id:
                 raise ValueError("components must be among 'ett', 'vx', 'vz', got %r" % (c,))
         L = _native.lib()
-        Lambda, Mu, Den, Stf, (dLambda, dMu, dDen), ids, nSteps = _checked(Lambda, Mu, Den, Stf, Shot_ids, para_fname, "the model and its perturbation are",
-                                                                         v=(dLambda, dMu, dDen))
+        v = (dLambda, dMu, dDen)
+        if dStf is not None and all(t is None for t in v):
+            v = ()
+        elif dStf is not None and any(t is None for t in v):
+            raise ValueError("with dStf, dLambda, dMu, dDen must all be given or all be None")
+        Lambda, Mu, Den, Stf, v, ids, nSteps = _checked(Lambda, Mu, Den, Stf, Shot_ids, para_fname, "the model and its perturbation are", v=v)
+        dLambda, dMu, dDen = v if v else (None, None, None)
         nrec = _nrec_per_shot(para_fname, ids)
         gpu_id = self._device_for(Lambda, 0)
         gdev = _gdev(Lambda, gpu_id)
@@ -324,10 +348,12 @@ class _FwiOps:
         for c in components:
             bufs[comp_id[c]] = torch.zeros(max(total, 1), dtype=torch.float32, device=gdev)
         hv = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev) if with_hv else None
-        stream = _stream_or_sync(Lambda, Stf, gpu_id)
-        rc = L.sepfwi_born(_ptr(bufs[2]), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(hv[0]) if with_hv else None, _ptr(hv[1]) if with_hv else None,
-                           _ptr(hv[2]) if with_hv else None, _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(dLambda), _ptr(dMu), _ptr(dDen), _ptr(Stf), gpu_id,
-                           int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+        ds = None if dStf is None else _local_rows(dStf, Stf, ids, gdev)
+        stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=ds is not None)   # (ds: read with a blocking copy inside the library)
+        args = (_ptr(bufs[2]), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(hv[0]) if with_hv else None, _ptr(hv[1]) if with_hv else None,
+                _ptr(hv[2]) if with_hv else None, _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(dLambda), _ptr(dMu), _ptr(dDen), _ptr(Stf), gpu_id,
+                int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+        rc = L.sepfwi_born(*args) if ds is None else L.sepfwi_born_src(*args, _ptr(ds))
         _native.check(rc)
         out, off = [], 0
         for n in nrec:
@@ -335,38 +361,53 @@ class _FwiOps:
             off += n * nSteps
         return out, (None if hv is None else hv.to(Lambda.device))
 
-    def born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components=("ett",)):
+    def born(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components=("ett",), dStf=None):
         """Born modelling J v (include/sepfwi.h, sepfwi_born): the first-order change of every gather for the model perturbation
         v = (dLambda, dMu, dDen), propagated next to the background field -- no finite difference, no step size.
         -> a list with one dict per shot of Shot_ids, component name ("ett", "vx", "vz") -> (nrec, nSteps) float32 on the model's device.
-        One GPU only (ngpu = 1, no torch.distributed): ValueError otherwise."""
-        return self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, False)[0]
+        One GPU only (ngpu = 1, no torch.distributed): ValueError otherwise.
+        dStf (sepfwi_born_src): a perturbation of the source time function in Stf's shape (rows of shots not in Shot_ids are not read);
+        the gathers are then J [v; ds] = J_m v + J_s ds, and dLambda, dMu, dDen may be None together (v = 0)."""
+        return self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, components, False, dStf=dStf)[0]
 
-    def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, exact=False):
+    def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, exact=False, dStf=None):
         """The Gauss-Newton Hessian-vector product J^T W J v, summed over Shot_ids -> (hvLambda, hvMu, hvDen), each (nz_pad, nx_pad):
         the gradient `backward` would return at the model if the observed data were syn - J v (W: the misfit weights of the parameter
         file).  Refused (SepFwiError, SEPFWI_EINVAL) with a live data-conditioning key.  One GPU only, as born.
         exact=True (include/sepfwi.h, sepfwi_adjoint_exact): J^T is the exact transpose of J instead of the reference's backward pass,
         and the product is P J^T W J P v with P the restriction to Omega (the physical interior without its first row and column; v is
         read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding.  The default leaves every bit as
-        it was."""
+        it was.
+        dStf (exact=True only; sepfwi_adjoint_exact_src): the source block, in Stf's shape.  u = [P v; ds] -> [P; I] J^T W J u, returned
+        as (hvLambda, hvMu, hvDen, hvStf) with hvStf in Stf's shape on the host (zero rows for shots not in Shot_ids); dLambda, dMu,
+        dDen may be None together.  With exact=False: ValueError -- the reference's backward pass is not J's transpose."""
+        if dStf is not None and not exact:
+            raise ValueError("dStf needs exact=True: the reference's backward pass is not the transpose of J")
         if exact:
-            return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=(dLambda, dMu, dDen))[1:]
+            v = None if (dStf is not None and dLambda is None and dMu is None and dDen is None) else (dLambda, dMu, dDen)
+            return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=v, dStf=dStf)[1:]
         hv = self._born(Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, (), True)[1]
         return hv[0], hv[1], hv[2]
 
     # -- the exact discrete adjoint (sepfwi_adjoint_exact) ----------------------------------------
-    def _adjoint_exact(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=None, w=None):
+    def _adjoint_exact(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, v=None, w=None, dStf=None, with_source=False):
         """-> (misfit(1,), gLambda, gMu, gDen) on the model's device.  v: (dLambda, dMu, dDen) for the product; w: one dict per shot,
-        component name -> (nrec, nSteps), for J^T w; neither: the exact gradient of the session's misfit.  The shot split is _born's."""
+        component name -> (nrec, nSteps), for J^T w; neither: the exact gradient of the session's misfit.  The shot split is _born's.
+        dStf (Stf's shape; the product's source block, v may then be None) or with_source: a fifth entry, the source block of the
+        result in Stf's shape on the host.  Without either the call is sepfwi_adjoint_exact's, as before."""
         if int(ngpu) != 1:
             raise ValueError("the exact adjoint runs on ONE GPU (ngpu = 1): the multi-GPU shot split is not implemented for it")
         if _dist.active():
             raise ValueError("the exact adjoint does not run under torch.distributed: the multi-rank path is not implemented for it")
         L = _native.lib()
+        if dStf is not None and v is not None and any(t is None for t in v):
+            raise ValueError("with dStf, dLambda, dMu, dDen must all be given or all be None")
         Lambda, Mu, Den, Stf, v, ids, nSteps = _checked(Lambda, Mu, Den, Stf, Shot_ids, para_fname, "the model is", v=v or ())
         gpu_id = self._device_for(Lambda, 0)
         gdev = _gdev(Lambda, gpu_id)
+        src = dStf is not None or with_source
+        ds = None if dStf is None else _local_rows(dStf, Stf, ids, gdev)
+        g_loc = torch.zeros((int(ids.size), nSteps), dtype=torch.float32, device=gdev) if src else None
         wbuf = {"ett": None, "vx": None, "vz": None}
         if w is not None:
             w = list(w)
@@ -389,19 +430,22 @@ class _FwiOps:
         misfit = torch.zeros(1, dtype=torch.float32)
         stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=True)   # (w was assembled on this stream; the library may run on its own)
         vp = [_ptr(t) for t in v] if v else [None, None, None]
-        rc = L.sepfwi_adjoint_exact(_ptr(misfit), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(wbuf["ett"]), _ptr(wbuf["vx"]), _ptr(wbuf["vz"]), *vp,
-                                    _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data),
-                                    str(para_fname).encode(), stream)
+        args = (_ptr(misfit), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(wbuf["ett"]), _ptr(wbuf["vx"]), _ptr(wbuf["vz"]), *vp,
+                _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+        rc = L.sepfwi_adjoint_exact_src(*args, _ptr(ds), _ptr(g_loc)) if src else L.sepfwi_adjoint_exact(*args)
         _native.check(rc)
         g = g.to(Lambda.device)
+        if src:
+            return misfit.to(Lambda.device), g[0], g[1], g[2], _global_rows(g_loc, Stf, ids)
         return misfit.to(Lambda.device), g[0], g[1], g[2]
 
-    def born_adjoint(self, Lambda, Mu, Den, w, Stf, ngpu, Shot_ids, para_fname):
+    def born_adjoint(self, Lambda, Mu, Den, w, Stf, ngpu, Shot_ids, para_fname, with_source=False):
         """J^T w with the exact discrete adjoint (include/sepfwi.h, sepfwi_adjoint_exact): w is a list with one dict per shot of
         Shot_ids, component name ("ett", "vx", "vz") -> (nrec, nSteps) float32 -- what `born` returns.  No weights, no sign; column 0
         is ignored; a component needs a weight in the parameter file (ett by default).  -> (gLambda, gMu, gDen), each (nz_pad, nx_pad),
-        non-zero on Omega only.  One GPU only, as born."""
-        return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, w=w)[1:]
+        non-zero on Omega only.  One GPU only, as born.
+        with_source=True (sepfwi_adjoint_exact_src): -> (gLambda, gMu, gDen, gStf), gStf = J_s^T w in Stf's shape on the host."""
+        return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, w=w, with_source=bool(with_source))[1:]
 
     # -- extras --------------------------------------------------------------------------------
     def set_observed(self, para_fname, shot_id, ett, gpu_id=0):
