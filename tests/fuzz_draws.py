@@ -3,7 +3,8 @@ seed, used or not, and later ingredients come from generators of their own, so t
 files see; tests/test_gauge_reference.py, tests/test_born_fuzz_reference.py and tests/test_exact_adjoint_fuzz_reference.py hold digests of
 the first 16 seeds' draws
 (draw_problem; draw_gauge, draw_born and draw_exact change its draw for tests/test_gpu_gauge_fuzz.py, test_gpu_born_fuzz.py and
-test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw)."""
+test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw; draw_pseudo_hessian adds to it, and changes nothing, for
+tests/test_gpu_pseudo_hessian_fuzz.py)."""
 import json
 import os
 
@@ -355,3 +356,22 @@ def perturbations(d, e):
     dm = [t.numpy() - i.numpy() for t, i in zip(pb["lame_true"], pb["lame_init"])]
     dm[1][:int(w)] = 0.0
     return v, X.on_omega(pb, dm)
+
+
+# ---- the diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------
+PH_SEED0 = 97255      # (of the offsets 97000 ... 97399 the one whose default 16 seeds hold the most of the 17 option sets: 13, with batch = 0 and batch = 1 on multi-shot draws)
+PH_EVERY = (1, 2, 3, 5)
+PH_OPTION_SETS = OPTION_SETS + [o for o in BORN_OPTION_SETS if o not in OPTION_SETS]      # the union, every structure once
+
+
+def draw_pseudo_hessian(d, seed):
+    """What tests/test_gpu_pseudo_hessian_fuzz.py adds to the draw d (draw_problem), from a generator of its own; d and its two files
+    stay what they are -- conditioning keys, directional channels and water layer included, none of which the result may depend on.
+    -> dict(every, entry ("backward": a gradient call, "forward": a misfit-only call with pseudo_hessian=), opts, fetch ("ops": the
+    operator's return value, "capi": sepfwi_pseudo_hessian_arm / sepfwi_get_pseudo_hessian into host memory))."""
+    rg = np.random.default_rng(PH_SEED0 + seed)
+    every = PH_EVERY[int(rg.integers(0, len(PH_EVERY)))]
+    entry = ("backward", "forward")[int(rg.integers(0, 2))]
+    opts = PH_OPTION_SETS[int(rg.integers(0, len(PH_OPTION_SETS)))]
+    fetch = ("ops", "capi")[int(rg.integers(0, 2))]
+    return dict(every=every, entry=entry, opts=opts, fetch=fetch)
