@@ -7,6 +7,13 @@ and residual gathers), so a stage is just another parameter file; every stage st
 and the last one uses the unfiltered data.
 
     python examples/multiscale_fwi.py --niter 4 [--bands 3]
+    python examples/multiscale_fwi.py --gauss-newton --niter 2 [--inner 3]
+
+--gauss-newton (off by default; without it every printed line is what it was): every stage runs --niter truncated Gauss-Newton steps in
+the Lame parameters instead of L-BFGS-B -- the band's own parameter file serves the conditioned misfit, its exact gradient
+(fwi_ops.backward(exact_adjoint=True)) and the Gauss-Newton product J^T C^T Z C J v of the windowed / band-passed data
+(fwi_ops.gauss_newton(exact=True)); the diagonal pseudo-Hessian, calibrated block by block on the Gauss-Newton curvature, is damping and
+Jacobi preconditioner of the inner conjugate gradients, as in examples/gauss_newton_fwi.py.
 """
 import argparse
 import os
@@ -26,8 +33,50 @@ FILTER_TABLE = [[0.0, 0.0, 2.0, 2.5], [0.0, 0.0, 2.0, 3.5], [0.0, 0.0, 2.0, 4.5]
                 [0.0, 0.0, 2.0, 7.5]]    # Main-001-...py:46-51
 
 
-def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True):
-    """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage."""
+def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping=0.05, rtol=0.1, say=None):
+    """`outer` truncated Gauss-Newton steps on the (conditioned) misfit of para_fname, from the padded Lame model m = [Lambda, Mu, Den]:
+    (J^T C^T Z C J + damping D) p = -g by at most `inner` conjugate-gradient iterations, D the calibrated diagonal pseudo-Hessian, then
+    backtracking on the misfit.  -> (m after the last step, misfit at the start, misfit at the end, steps taken)"""
+    from sepfwi import fwi_ops
+    from sepfwi.obj_wrapper import gauss_newton_cg
+    say = say or (lambda *a: None)
+    dot = lambda x, y: float(sum((p.double() * q.double()).sum() for p, q in zip(x, y)))
+    misfit = lambda mm: float(fwi_ops.forward(*mm, Stf, 0, Shot_ids, para_fname)[0])
+    f_start = f = None
+    taken = 0
+    for k in range(outer):
+        D = [Mask * t for t in fwi_ops.forward(*m, Stf, 0, Shot_ids, para_fname, pseudo_hessian=1)[1:4]]
+        out = fwi_ops.backward(*m, Stf, 1, Shot_ids, para_fname, exact_adjoint=True)
+        f, g = float(out[0]), [Mask * t for t in out[1:4]]
+        if f_start is None:
+            f_start = f
+        hv = lambda v: [Mask * t for t in fwi_ops.gauss_newton(*m, *[Mask * x for x in v], Stf, 1, Shot_ids, para_fname, exact=True)]
+        for j in range(3):      # each block of D on the scale of the Gauss-Newton curvature along its own preconditioned gradient
+            z = [torch.zeros_like(t) for t in g]
+            z[j] = -(g[j] / D[j].clamp_min(1e-12 * float(D[j].max()))) * Mask
+            den = dot([z[j]], [D[j] * z[j]])
+            D[j] = D[j] * (max(dot(z, hv(z)) / den, 0.0) if den > 0 else 0.0)
+        p, hist = gauss_newton_cg(hv, g, damping=damping, diag=D, maxiter=inner, rtol=rtol)
+        step, f_new = 1.0, None
+        for _ in range(6):      # backtracking on the misfit
+            f_new = misfit([(mi + step * pi).contiguous() for mi, pi in zip(m, p)])
+            if f_new < f:
+                break
+            step *= 0.5
+        if not f_new < f:
+            say("  Gauss-Newton step %d: no decrease along the step, stage ends" % (k + 1))
+            break
+        m = [(mi + step * pi).contiguous() for mi, pi in zip(m, p)]
+        taken += 1
+        say("  Gauss-Newton step %d: misfit %.4e -> %.4e (step %.3g, %d cg iterations, last relative residual %.2e)" % (k + 1, f, f_new, step, len(hist) - 1, hist[-1]))
+        f = f_new
+    return m, f_start, f, taken
+
+
+def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3):
+    """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage.
+    gauss_newton: every stage is `niter` truncated Gauss-Newton steps (at most `inner` conjugate-gradient iterations each) on the stage's
+    own parameter file instead of L-BFGS-B (gauss_newton_stage)."""
     dev = torch.device(device)
     nx, nz, dx, dz, dt, nt, f0, nPml = 201, 101, 20.0, 20.0, 0.002, 1501, 10.0, 32
     vp = np.ones((nz, nx), np.float32) * 4000.0
@@ -59,7 +108,21 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True):
     M.FWI_obscalc(pad(vp), pad(vs), pad(rho), Stf, para_for("obs", None))(Shot_ids, ngpu=1)   # raw gathers, written once
 
     log = []
-    for k, band in enumerate(FILTER_TABLE[len(FILTER_TABLE) - n_bands:] + [None]):    # the widest n_bands rows: a 10 Hz Ricker has little below 4 Hz
+    bands = FILTER_TABLE[len(FILTER_TABLE) - n_bands:] + [None]      # the widest n_bands rows: a 10 Hz Ricker has little below 4 Hz
+    if gauss_newton:
+        lame = lambda c: [((pad(c[0]) ** 2 - 2.0 * pad(c[1]) ** 2) * pad(c[2]) / 1e6).contiguous(), (pad(c[1]) ** 2 * pad(c[2]) / 1e6).contiguous(), pad(c[2])]
+        m, mask = lame(cur), torch.tensor(Mask, device=dev)
+        for k, band in enumerate(bands):
+            m, f_start, f_end, taken = gauss_newton_stage(m, mask, Stf, Shot_ids, para_for("stage%d" % k, band), niter, inner, say=print if verbose else None)
+            log.append((band, f_start, f_end))
+            if verbose:
+                print("stage %d, %s: conditioned misfit %.4e -> %.4e in %d Gauss-Newton steps" %
+                      (k, "low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies", f_start, f_end, taken), flush=True)
+        inner_ = (slice(nPml, nPml + nz), slice(nPml, nPml + nx))
+        lam, mu, den = [t[inner_].double().cpu().numpy() for t in m]
+        cur = [np.sqrt((lam + 2.0 * mu) * 1e6 / den).astype(np.float32), np.sqrt(mu * 1e6 / den).astype(np.float32), den.astype(np.float32)]
+        bands = []
+    for k, band in enumerate(bands):
         opt = dict(nz=nz, nx=nx, nz_orig=nz, nx_orig=nx, nPml=nPml, nPad=nPad, para_fname=para_for("stage%d" % k, band))
         T = lambda m: torch.tensor(m, dtype=torch.float32, device=dev, requires_grad=True)
         fwi = M.FWI(T(cur[0]), T(cur[1]), T(cur[2]), Stf, opt, Mask=torch.tensor(Mask, device=dev))
@@ -85,5 +148,7 @@ if __name__ == "__main__":
     ap.add_argument("--niter", type=int, default=4, help="L-BFGS-B iterations per stage")
     ap.add_argument("--bands", type=int, default=3, help="how many rows of the filter table, counted from its wide end (then one stage on all frequencies)")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--gauss-newton", action="store_true", help="truncated Gauss-Newton steps on every band's conditioned misfit instead of L-BFGS-B (--niter: steps per band)")
+    ap.add_argument("--inner", type=int, default=3, help="with --gauss-newton: conjugate-gradient iterations per step (cap)")
     a = ap.parse_args()
-    run(a.niter, a.bands, a.workdir)
+    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner)

@@ -162,8 +162,13 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
  *                       J^T the backward pass of a gradient call.  Sign and weights: hv is the gradient that sepfwi_cufd(calc_id 1) would
  *                       return at m if the observed data were syn(m) - J v; so v^T hv >= 0 up to the inexactness of the reference's adjoint.
  *                       (nz, nx) float32 each, host or device.  One set and the others NULL: SEPFWI_EINVAL.
+ *                       Under a parameter file whose live conditioning keys are among if_win and filter the misfit is still quadratic in
+ *                       the data, and the same sentence holds for the conditioned misfit: hv = J^T C^T Z C J v, with C = B Wn (per-channel
+ *                       windows with weights, or the end taper; then the zero-phase band-pass: sepfwi_condition below) and Z the zeroing of
+ *                       time sample 0 that the conditioned residual applies.  d_* stay the raw gathers.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, perturbation, stf or para_fname; a bad shot list; the product
- * (hv_* set) with a live data-conditioning key -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
+ * (hv_* set) under if_cross_misfit (a misfit that is not quadratic in the data) or if_src_update (a matching filter that depends on the
+ * synthetics) -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
  * background model only.  The session's observed data, its misfit, sepfwi_get_misfit_parts and the pseudo-Hessian state are neither
  * read nor written; sepfwi_get_stats afterwards describes this call (fwd_ms: the Born time loops).
  * Schedule: one shot after the other on the call's stream (hip_stream, NULL: the session's own), synchronous; the batched multi-lane
@@ -192,8 +197,13 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
  *       g is the exact gradient on Omega of the session's misfit 1/2 sum_c w_c |obs_c - syn_c|^2 (all columns), and *misfit (may be
  *       NULL) is that value, as sepfwi_cufd(calc_id 1) reports it.
  * Every receiver geometry and parameter key of the forward pass applies (das_fiber, directional channels, das_gauge_length, misfit_w_*).
+ * Windowed and band-passed data (live conditioning keys among if_win and filter; C and Z as under sepfwi_born):
+ *   the product is g = P J^T C^T Z C J P v, still symmetric and non-negative (v^T g = |Z C J P v|^2);
+ *   the gradient mode returns the exact gradient on Omega of the conditioned misfit 1/2 |Z (C obs - C syn)|^2 and that value in *misfit,
+ *   as a misfit call on the same file reports it;
+ *   the w mode is untouched: g = J^T w with w in raw data space -- a caller composes C and C^T through sepfwi_condition.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
- * shot list; a live data-conditioning key; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
+ * shot list; if_cross_misfit or if_src_update in any mode; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
  * gradient of the source time function is returned by sepfwi_adjoint_exact_src (below), not here.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
  * are read but never written; sepfwi_get_stats afterwards describes this call.  Schedule: one shot after the other on the call's
  * stream, synchronous, two launches and one injection per backward time step; the persistent backward loop and the batched schedule
@@ -229,6 +239,14 @@ int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float 
                              const float *dLambda, const float *dMu, const float *dDen, const float *Lambda, const float *Mu, const float *Den,
                              const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream,
                              const float *dStf, float *g_stf);
+
+/* C (transpose = 0) or C^T (transpose != 0) of the parameter file, in place, on gathers laid out like sepfwi_born's d_ett:
+   [nrec_i][nSteps] shot after shot in the order of shot_ids; host or device.  C is what the session applies to a synthetic
+   axial-strain gather before the residual: per-channel windows with weights (if_win) or the end taper, then the band-pass
+   (filter); the identity when no conditioning key is live.  C^T: the band-pass, then the window.  Defined under every key
+   (if_cross_misfit and if_src_update select a misfit, not C).  Creates the session as sepfwi_set_observed does; touches no observed
+   data, misfit or statistics; synchronous. */
+int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream);
 
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);

@@ -187,6 +187,15 @@ int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_D
                                     para_fname, hip_stream, nullptr, nullptr);
 }
 
+int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        if (group_size > 0 && !data) throw std::invalid_argument("condition: data must not be NULL");
+        get_session(para_fname, gpu_id)->condition(data, transpose != 0, group_size, shot_ids, (hipStream_t)hip_stream);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

@@ -132,6 +132,14 @@ __global__ void k_l2_residual(int nt, int nrec, const float *__restrict__ obs, c
     if (threadIdx.x == 0) atomicAdd(acc, part[0] + part[1] + part[2] + part[3]);
 }
 
+// the same residual for observed data syn - d (the Gauss-Newton product, d = C J v): r = -d, first sample zeroed.  No misfit.
+__global__ void k_scattered_residual(int nt, int nrec, const float *__restrict__ d, float *__restrict__ res) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (it >= nt || r >= nrec) return;
+    const size_t i = (size_t)r * nt + it;
+    res[i] = it == 0 ? 0.0f : -d[i];
+}
+
 // cuda_spectrum_update (utilities.cu:905-977), first half: one block per frequency bin sums conj(C_r) O_r and |C_r|^2 over the
 // channels (double partial sums; the reference: 512 strided float partials and a tree) and divides:
 // coef = num / (den + lambda), lambda = 1e-6 added to the real denominator.
@@ -326,6 +334,11 @@ void Conditioner::source_update_adj(hipStream_t st, float *res, int nrec, float 
 void Conditioner::l2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc) {
     if (nrec <= 0) return;
     hipLaunchKernelGGL(k_l2_residual, dim3(nrec), dim3(256), 0, st, nt_, nrec, obs, syn, res, acc);
+}
+
+void Conditioner::scattered_residual(hipStream_t st, const float *d, float *res, int nrec) {
+    if (nrec <= 0) return;
+    hipLaunchKernelGGL(k_scattered_residual, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, d, res);
 }
 
 void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights,

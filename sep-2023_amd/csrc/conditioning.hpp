@@ -24,6 +24,8 @@ class Conditioner {
     void bandpass(hipStream_t st, float *data, int nrec, float dt, const float filt[4]);
     // gpuMinus + cuda_cal_objective (utilities.cu:154-205): res = obs - syn (first sample zeroed), *acc += sum res^2
     void l2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc);
+    // what l2_residual leaves in res for observed data syn - d: res = -d (first sample zeroed); no misfit is accumulated
+    void scattered_residual(hipStream_t st, const float *d, float *res, int nrec);
     // cuda_find_normfact x3 + cuda_normal_misfit + cuda_normal_adjoint_source (utilities.cu:1010-1111):
     // *acc += -2 sum_r <obs,syn>_r / (|obs|_r |syn|_r) w_r ; res = the adjoint source.  weights may be null (all ones).
     void cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight,

@@ -66,6 +66,9 @@ class Session {
     void adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_Den, const float *w_ett, const float *w_vx, const float *w_vz,
                        const float *Lambda, const float *Mu, const float *Den, const float *stf, int group_size, const int *shot_ids,
                        hipStream_t ext_stream, float *g_stf = nullptr);  // g_stf: the source block J_s^T (.), (group_size, nSteps), or null
+    // The conditioning operator of the parameter file (sepfwi_condition): C, or C^T, in place on gathers laid out like born()'s d_ett,
+    // host or device; the identity when no conditioning key is live
+    void condition(float *data, bool transpose, int group_size, const int *shot_ids, hipStream_t ext_stream);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
@@ -80,7 +83,10 @@ class Session {
     void ensure_lanes(int n_lanes, bool with_frames);
     void ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots);
     void order_after_null_stream(hipStream_t st);
+    // C of the parameter file on one [rec][it] gather in place: window (if_win: per channel, with weights; else the end taper), then
+    // band-pass (filter); and C^T: band-pass, then window
     void condition_gather(hipStream_t st, float *gather_rec_major, int shot_id, int nrec);
+    void condition_gather_t(hipStream_t st, float *gather_rec_major, int shot_id, int nrec);
 
     // ---- one cufd call (run): its state and its passes -------------------------------------------------------------------
     struct Call {  // what every pass of one call shares; ONE snapshot of the kernel options
@@ -177,6 +183,7 @@ class Session {
     GeoResShot geo_res_shot(const ShotCtx &x) const;  // joint misfit: what the residual kernel needs of one shot (geophone.hpp)
     void residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int nb);
     void residual_conditioned(const Call &c, const ShotCtx &x);
+    void adjoint_source_conditioned(const Call &c, const ShotCtx &x);  // -C^T Z C (J v) from the shot's scattered gather (if_win / filter)
     // what a forward pass leaves behind, by kind of call
     void after_forward(Call &c, const ShotCtx &x);
     void export_gathers(const Call &c, const ShotCtx &x);

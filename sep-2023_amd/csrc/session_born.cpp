@@ -8,7 +8,9 @@
 //   gathers             transposed to [nrec][nSteps] and copied out
 //   product only        the residual buffer is filled with -(w_c dsyn_c) (k_adjoint_source, geophone.hip) where a gradient call's
 //                       residual kernel would put w_c (obs_c - syn_c), and Session::backward runs as in a gradient call: persistent loop
-//                       or two-launch step, injection plans, the background's saved boundary frames
+//                       or two-launch step, injection plans, the background's saved boundary frames.  Under a parameter file with if_win
+//                       / filter (C = band-pass . window) the buffer gets -C^T Z C dsyn instead (Session::adjoint_source_conditioned):
+//                       the product is J^T C^T Z C J v; the gathers handed out stay the raw ones
 // and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
 // state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
 // exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
@@ -37,9 +39,9 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     std::lock_guard<std::mutex> lock(mu_);
     const bool want_hv = hv_Lambda != nullptr, have_v = dLambda != nullptr;
     // refusals first: nothing is touched
-    if (want_hv && cond_on_)
-        throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit (if_win / filter / if_cross_misfit / if_src_update); "
-                                    "the scattered gathers alone are served (hv_* = NULL)");
+    if (want_hv && (par_.if_cross_misfit || par_.if_src_update))
+        throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit with if_cross_misfit or if_src_update (not "
+                                    "quadratic in the data); if_win and filter are served; the scattered gathers alone are served under every key (hv_* = NULL)");
     check_shot_ids(group_size, shot_ids);  // (begin_call checks them where run does: after it has touched the statistics)
     Call c = begin_call(ext_stream, group_size, shot_ids);
     c.opt.quiet_skip = 0;
@@ -117,7 +119,9 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
             cs_.launches++;
         }
         out_off += cnt;
-        if (want_hv && x.nrec > 0) {
+        if (want_hv && cond_on_) {  // if_win / filter: -C^T Z C J v (the weights are (1, 0, 0): the axial strain alone)
+            adjoint_source_conditioned(c, x);
+        } else if (want_hv && x.nrec > 0) {
             AdjSource q{{}, {}, 1, (size_t)x.nrec, x.res, x.nrec, geo_ncomp_};  // the time-major gathers of J v, by the weights
             for_active([&](int comp, int b) {
                 q.src[b] = syn_of(x, comp);

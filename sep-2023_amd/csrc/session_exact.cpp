@@ -7,6 +7,9 @@
 //   the residual kernels (k_residual, k_geo_residual)  from the session's observed data: the exact gradient (adjoint_exact, no w)
 //   k_adjoint_source (geophone.hip)                    from J v: the product P J^T W J P v (Session::born with exact = true)
 //   the same kernel                                    from the caller's w: J^T w (adjoint_exact with w)
+// Under a parameter file with if_win / filter (C = band-pass . window, Z the zeroing of sample 0) the first becomes
+// residual_conditioned: C^T Z (C obs - C syn), the second adjoint_source_conditioned: the product P J^T C^T Z C J P v; the third is
+// untouched -- w stays in raw data space (sepfwi_condition applies C).  if_cross_misfit and if_src_update are refused.
 // Per shot: a plain forward pass with boundary-frame save (or the Born pass), the adjoint source, then backward_exact:
 //   column nSteps-1 injected, Q primed by k_exact_b in its adjoint-only form, and for it = nSteps-2 ... 0
 //   k_exact_a, injection of column it (it >= 1; the plans and k_inject of a gradient call), k_exact_b
@@ -91,8 +94,9 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
     const float *w[4] = {nullptr, w_vx, w_vz, w_ett};  // by component id
     const bool have_w = w_ett || w_vx || w_vz;
     // refusals first: nothing is touched
-    if (cond_on_)
-        throw std::invalid_argument("adjoint_exact: not defined for a conditioned misfit (if_win / filter / if_cross_misfit / if_src_update)");
+    if (par_.if_cross_misfit || par_.if_src_update)
+        throw std::invalid_argument("adjoint_exact: not defined for a conditioned misfit with if_cross_misfit or if_src_update (not quadratic in the "
+                                    "data); if_win and filter are served");
     static const char *kName[4] = {"", "vx", "vz", "ett"};
     for (int comp = 1; comp <= 3; comp++)
         if (w[comp] && geo_block_[comp] < 0)
@@ -125,7 +129,7 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
         if (inl) record_column(x, nSteps - 1);
         const size_t cnt = (size_t)x.nrec * nSteps;
         if (c.if_res) {
-            residual(x);
+            cond_on_ ? residual_conditioned(c, x) : residual(x);  // (if_win / filter: C^T Z (C obs - C syn), the misfit of a misfit call)
         } else if (x.nrec > 0) {
             AdjSource q{{}, {}, (size_t)nSteps, 1, x.res, x.nrec, geo_ncomp_};  // the caller's [nrec][nSteps] gathers as they are
             for_active([&](int comp, int b) {

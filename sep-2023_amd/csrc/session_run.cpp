@@ -250,12 +250,23 @@ void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
     else
         cond_->l2_residual(st, x.d_obs, xpose_, xpose2_, x.nrec, scal_);
     if (par_.if_src_update) cond_->source_update_adj(st, xpose2_, x.nrec, par_.dt);  // libCUFD.cu:430-433
-    if (par_.has_filter) cond_->bandpass(st, xpose2_, x.nrec, par_.dt, par_.filter);  // adjoint of the (zero-phase) filter
-    if (par_.if_win)
-        cond_->window(st, xpose2_, x.nrec, par_.dt, win_ + off, win_ + tot + off, win_ + 2 * tot + off, x.sh->src_weight, 0.005f);
-    else
-        cond_->window(st, xpose2_, x.nrec, par_.dt, nullptr, nullptr, nullptr, 1.0f, 0.005f);
+    condition_gather_t(st, xpose2_, x.id, x.nrec);
     launch_transpose(st, xpose2_, x.res, x.nrec, nSteps);  // [rec][it] -> [it][rec]: the adjoint source
+    cs_.launches += 8;
+}
+
+// The adjoint source of a Gauss-Newton product under a file whose live conditioning keys are if_win / filter: from the shot's
+// scattered axial-strain gather d = J v (time-major, where the samplers left it) the residual buffer gets -C^T Z C d -- what
+// residual_conditioned leaves for observed data syn - J v, and the sign k_adjoint_source leaves.  Z (sample 0 zeroed) and the sign
+// are one kernel, in the place of the residual kernel; no misfit, no observed data.
+void Session::adjoint_source_conditioned(const Call &c, const ShotCtx &x) {
+    if (x.nrec <= 0) return;
+    hipStream_t st = c.st;
+    launch_transpose(st, syn_of(x, 3), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
+    condition_gather(st, xpose_, x.id, x.nrec);
+    cond_->scattered_residual(st, xpose_, xpose2_, x.nrec);
+    condition_gather_t(st, xpose2_, x.id, x.nrec);
+    launch_transpose(st, xpose2_, x.res, x.nrec, par_.nSteps);  // [rec][it] -> [it][rec]
     cs_.launches += 8;
 }
 

@@ -111,10 +111,11 @@ def lib():
     L.sepfwi_adjoint_exact.argtypes = [fp] * 14 + [C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
     L.sepfwi_born_src.argtypes = L.sepfwi_born.argtypes + [fp]
     L.sepfwi_adjoint_exact_src.argtypes = L.sepfwi_adjoint_exact.argtypes + [fp, fp]
+    L.sepfwi_condition.argtypes = [fp, C.c_int, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
     for f in ("sepfwi_cufd", "sepfwi_cufd_stream", "sepfwi_cpml_profiles", "sepfwi_stf_taper", "sepfwi_shot_split",
               "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes", "sepfwi_set_observed",
               "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact", "sepfwi_born_src",
-              "sepfwi_adjoint_exact_src", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_version", "sepfwi_device_count"):
+              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_version", "sepfwi_device_count"):
         getattr(L, f).restype = C.c_int
     L.sepfwi_release_all.restype = None
     L.sepfwi_invalidate_observed.restype = None
@@ -126,7 +127,7 @@ EXPORTS = ["sepfwi_last_error", "sepfwi_version", "sepfwi_device_count", "sepfwi
            "sepfwi_release_all", "sepfwi_invalidate_observed", "sepfwi_cpml_profiles", "sepfwi_stf_taper",
            "sepfwi_shot_split", "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes",
            "sepfwi_set_observed", "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact",
-           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_param_forward", "sepfwi_param_backward"]
+           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward"]
 
 
 class SepFwiError(RuntimeError):

@@ -234,7 +234,8 @@ class _FwiOps:
         Extension `exact_adjoint=True` (include/sepfwi.h, sepfwi_adjoint_exact): the same list, the gradients being the exact ones of
         the misfit on Omega (0 outside) and gStf ZEROS unless `source_gradient=True`: then gStf is the exact d misfit / d Stf
         (sepfwi_adjoint_exact_src), in Stf's shape with zero rows for shots not in Shot_ids.  One GPU, not together with
-        pseudo_hessian.
+        pseudo_hessian.  Windowed / band-passed data (if_win, filter) are served: misfit and gradients are those of the conditioned
+        misfit 1/2 |Z (C obs - C syn)|^2; if_cross_misfit and if_src_update are refused (SepFwiError).
         Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
         shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
         and ranks like the gradients; under torch.distributed through ONE more all-reduce, of the fused [hL | hM | hD] buffer).
@@ -373,11 +374,13 @@ class _FwiOps:
     def gauss_newton(self, Lambda, Mu, Den, dLambda, dMu, dDen, Stf, ngpu, Shot_ids, para_fname, exact=False, dStf=None):
         """The Gauss-Newton Hessian-vector product J^T W J v, summed over Shot_ids -> (hvLambda, hvMu, hvDen), each (nz_pad, nx_pad):
         the gradient `backward` would return at the model if the observed data were syn - J v (W: the misfit weights of the parameter
-        file).  Refused (SepFwiError, SEPFWI_EINVAL) with a live data-conditioning key.  One GPU only, as born.
+        file).  Under a parameter file whose live conditioning keys are among if_win and filter the same holds for the conditioned
+        misfit: the product is J^T C^T Z C J v (C: `condition`; Z: time sample 0 zeroed).  Refused (SepFwiError, SEPFWI_EINVAL) under
+        if_cross_misfit or if_src_update.  One GPU only, as born.
         exact=True (include/sepfwi.h, sepfwi_adjoint_exact): J^T is the exact transpose of J instead of the reference's backward pass,
         and the product is P J^T W J P v with P the restriction to Omega (the physical interior without its first row and column; v is
-        read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding.  The default leaves every bit as
-        it was.
+        read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding (windowed / band-passed data:
+        P J^T C^T Z C J P v, v^T hv = |Z C J P v|^2).  The default leaves every bit as it was.
         dStf (exact=True only; sepfwi_adjoint_exact_src): the source block, in Stf's shape.  u = [P v; ds] -> [P; I] J^T W J u, returned
         as (hvLambda, hvMu, hvDen, hvStf) with hvStf in Stf's shape on the host (zero rows for shots not in Shot_ids); dLambda, dMu,
         dDen may be None together.  With exact=False: ValueError -- the reference's backward pass is not J's transpose."""
@@ -443,9 +446,50 @@ class _FwiOps:
         """J^T w with the exact discrete adjoint (include/sepfwi.h, sepfwi_adjoint_exact): w is a list with one dict per shot of
         Shot_ids, component name ("ett", "vx", "vz") -> (nrec, nSteps) float32 -- what `born` returns.  No weights, no sign; column 0
         is ignored; a component needs a weight in the parameter file (ett by default).  -> (gLambda, gMu, gDen), each (nz_pad, nx_pad),
-        non-zero on Omega only.  One GPU only, as born.
+        non-zero on Omega only.  One GPU only, as born.  w is in RAW data space under every parameter file this call accepts: if_win and
+        filter change nothing here (compose C and C^T with `condition`); if_cross_misfit and if_src_update are refused.
         with_source=True (sepfwi_adjoint_exact_src): -> (gLambda, gMu, gDen, gStf), gStf = J_s^T w in Stf's shape on the host."""
         return self._adjoint_exact(Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, w=w, with_source=bool(with_source))[1:]
+
+    # -- the conditioning operator of a parameter file (sepfwi_condition) -----------------------------
+    def condition(self, d, Shot_ids, para_fname, transpose=False, gpu_id=0):
+        """C d (or C^T d with transpose=True) of the parameter file: what the session applies to a synthetic axial-strain gather before
+        the residual -- per-channel windows with weights (if_win) or the end taper, then the band-pass (filter); C^T: the band-pass, then
+        the window; the identity when no conditioning key is live.  d: the per-shot dict list that `born` returns (every component of
+        every dict is conditioned; a new list comes back), or ONE float32 tensor holding the gathers [nrec_i][nSteps] shot after shot in
+        the order of Shot_ids (any shape with that many elements; a new tensor of the same shape and device comes back).  The input
+        is never changed.  With it a caller composes J^T C^T Z C J from `born` and `born_adjoint`, which stay in raw data space."""
+        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
+        dev = self.device_override if self.device_override is not None else int(gpu_id)
+        if not torch.is_tensor(d):
+            d = list(d)
+            if len(d) != ids.size:
+                raise ValueError("d must hold one dict of gathers per shot of Shot_ids")
+            comps = sorted({c for g in d for c in g})
+            out = [dict() for _ in d]
+            for c in comps:   # one call per component: the gathers of the shots that have it, shot after shot
+                have = [i for i, g in enumerate(d) if c in g]
+                flat = self.condition(torch.cat([_f32c(d[i][c], "d[%r]" % c).reshape(-1) for i in have]), ids[have], para_fname, transpose, gpu_id)
+                off = 0
+                for i in have:
+                    n = d[i][c].numel()
+                    out[i][c] = flat[off:off + n].view(d[i][c].shape)
+                    off += n
+            return out
+        dims = _para_dims(para_fname)
+        if dims is not None and d.numel() != int(sum(_nrec_per_shot(para_fname, ids))) * dims[2]:
+            raise ValueError("d must hold (nrec_i, nSteps = %d) float32 per shot of Shot_ids, %d elements in all, got %d"
+                             % (dims[2], int(sum(_nrec_per_shot(para_fname, ids))) * dims[2], d.numel()))
+        out = _f32c(d, "d").clone()
+        stream = None
+        if out.is_cuda and out.device.index == dev:
+            cs = torch.cuda.current_stream(out.device).cuda_stream
+            stream = C.c_void_p(cs) if cs else None
+        elif out.is_cuda:
+            torch.cuda.synchronize(out.device)
+        _native.check(_native.lib().sepfwi_condition(_ptr(out), int(bool(transpose)), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
+                                                     str(para_fname).encode(), stream))
+        return out
 
     # -- extras --------------------------------------------------------------------------------
     def set_observed(self, para_fname, shot_id, ett, gpu_id=0):
