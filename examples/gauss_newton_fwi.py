@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Truncated Gauss-Newton FWI of the three-box anomaly model with DAS data (the model and survey of the reference's experiment 001,
-examples/fwi_anomaly_vp_vs_den.py) in the Lame parameters (Lambda, Mu, Den): every outer iteration solves
+examples/fwi_anomaly_vp_vs_den.py) in the Lame parameters (Lambda, Mu, Den) on the padded grid or, with --param vp_vs_den, in the
+parameters of the `FWI` module (Vp, Vs, Den on the physical grid, behind replicate padding and the mask blend): every outer iteration solves
     (J^T J + damping D) p = -g
 with a few matrix-free conjugate-gradient iterations (sepfwi.obj_wrapper.gauss_newton_cg over fwi_ops.gauss_newton, one Born pass and one
 backward pass per product), D the diagonal pseudo-Hessian of the same gradient call -- each parameter's block calibrated on the
@@ -8,6 +9,10 @@ Gauss-Newton curvature -- as damping matrix and preconditioner, and takes a back
 
     python examples/gauss_newton_fwi.py --device cuda
     python examples/gauss_newton_fwi.py --device cuda --outer 2 --inner 3 --nsteps 600 --shot-stride 3
+    python examples/gauss_newton_fwi.py --device cuda --param vp_vs_den --exact-adjoint
+
+With --param vp_vs_den the gradient is module(ids).backward(), D is module.diag(pseudo-Hessian) and the product is module.gauss_newton
+(P^T J^T J P v with P the tangent of the parameter chain); calibration, CG and backtracking are the same.
 
 Prints the CG residual of every inner iteration and the misfit of every outer one."""
 import argparse
@@ -37,6 +42,8 @@ def main():
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--exact-adjoint", action="store_true",
                     help="the CG operator uses the exact discrete adjoint (fwi_ops.gauss_newton(exact=True)): symmetric and non-negative on Omega")
+    ap.add_argument("--param", default="lame", choices=["lame", "vp_vs_den"],
+                    help="the unknowns: (Lambda, Mu, Den) on the padded grid, or the FWI module's (Vp, Vs, Den) on the physical grid")
     a = ap.parse_args()
     dev = torch.device(a.device)
 
@@ -70,26 +77,56 @@ def main():
         return [((t[0] ** 2 - 2.0 * t[1] ** 2) * t[2] / 1e6).contiguous(), (t[1] ** 2 * t[2] / 1e6).contiguous(), t[2].contiguous()]
 
     fwi_ops.obscalc(*lame(vp, vs, rho), Stf, 1, ids, para_fname, to_store=True)   # observed data straight into the session's store
-    m = lame(vp0, vs0, rho0)
-    misfit = lambda mm: float(fwi_ops.forward(*mm, Stf, 0, ids, para_fname)[0])
+    names = ("Lambda", "Mu", "Den")
+    if a.param == "vp_vs_den":      # the FWI module holds the unknowns on the device; m are its three fields
+        from sepfwi.modules import FWI
+        names = FWI.NAMES
+        opt = dict(nz=nz, nx=nx, nz_orig=nz, nx_orig=nx, nPml=nPml, nPad=nPad, para_fname=para_fname)
+        fwi = FWI(*[torch.tensor(t, dtype=torch.float32, device=dev, requires_grad=True) for t in (vp0, vs0, rho0)], Stf, opt, Mask=Mask)
+        m = [p.detach().clone() for p in fwi.parameters()]
+        W = [torch.ones_like(t) for t in m]      # the module applies the Mask itself (P and P^T carry it)
+
+        def at(mm):      # the module at the fields mm -> its padded (Lambda, Mu, Den)
+            with torch.no_grad():
+                for p, t in zip(fwi.parameters(), mm):
+                    p.copy_(t)
+                return [t.contiguous() for t in fwi.lame_padded()]
+
+        def gradient(mm):
+            at(mm)
+            fwi.zero_grad()
+            loss = fwi(ids, ngpu=1)
+            loss.backward()
+            H = fwi_ops.forward(*at(mm), Stf, 0, ids, para_fname, pseudo_hessian=1)[1:4]
+            return float(loss.detach()), [p.grad.detach().clone() for p in fwi.parameters()], list(fwi.diag(*[t.to(dev) for t in H]))
+        misfit = lambda mm: float(fwi_ops.forward(*at(mm), Stf, 0, ids, para_fname)[0])
+        product = lambda mm, v: fwi.gauss_newton(tuple(v), ids, exact=a.exact_adjoint)      # (the module sits at mm: gradient() left it there)
+    else:
+        m = lame(vp0, vs0, rho0)
+        W = [Mask, Mask, Mask]
+
+        def gradient(mm):
+            out = fwi_ops.backward(*mm, Stf, 1, ids, para_fname, pseudo_hessian=1)
+            return float(out[0]), [Mask * t for t in out[1:4]], [Mask * t for t in out[5:8]]
+        misfit = lambda mm: float(fwi_ops.forward(*mm, Stf, 0, ids, para_fname)[0])
+        product = lambda mm, v: [Mask * t for t in fwi_ops.gauss_newton(*mm, *[Mask * x for x in v], Stf, 1, ids, para_fname, exact=a.exact_adjoint)]
     f0_ = None
     for k in range(a.outer):
-        out = fwi_ops.backward(*m, Stf, 1, ids, para_fname, pseudo_hessian=1)
-        f, g, D = float(out[0]), [Mask * t for t in out[1:4]], [Mask * t for t in out[5:8]]
+        f, g, D = gradient(m)
         if f0_ is None:
             f0_ = f
             print("iterate 0: misfit %.6e" % f, flush=True)
-        hv = lambda v: [Mask * t for t in fwi_ops.gauss_newton(*m, *[Mask * x for x in v], Stf, 1, ids, para_fname, exact=a.exact_adjoint)]
+        hv = lambda v: product(m, v)
         # The pseudo-Hessian leaves out the receiver side, and its three blocks are not on one scale (it is a preconditioner, not a
         # Hessian): calibrate each block on the Gauss-Newton curvature along its own preconditioned gradient z_k = -g_k / D_k,
         # D_k <- D_k (z_k^T H z_k) / (z_k^T D_k z_k) -- three products per outer iteration
         dot = lambda x, y: float(sum((p.double() * q.double()).sum() for p, q in zip(x, y)))
         for j in range(3):
             z = [torch.zeros_like(t) for t in g]
-            z[j] = -(g[j] / D[j].clamp_min(1e-12 * float(D[j].max()))) * Mask
+            z[j] = -(g[j] / D[j].clamp_min(1e-12 * float(D[j].max()))) * W[j]
             s_j = dot(z, hv(z)) / dot([z[j]], [D[j] * z[j]])
             D[j] = D[j] * max(s_j, 0.0)
-            print("  outer %d: pseudo-Hessian block %s calibrated by %.3e" % (k + 1, ("Lambda", "Mu", "Den")[j], s_j), flush=True)
+            print("  outer %d: pseudo-Hessian block %s calibrated by %.3e" % (k + 1, names[j], s_j), flush=True)
         lam = a.damping
         p, hist = gauss_newton_cg(hv, g, damping=lam, diag=D, maxiter=a.inner, rtol=a.rtol,
                                   callback=lambda i, r: print("  outer %d cg %d: relative residual %.4e" % (k + 1, i, r), flush=True))
@@ -105,10 +142,13 @@ def main():
         m = [(mi + step * pi).contiguous() for mi, pi in zip(m, p)]
         print("iterate %d: misfit %.6e   (step %.3g, %d cg iterations)" % (k + 1, f_new, step, len(hist) - 1), flush=True)
         f = f_new
-    true, start = lame(vp, vs, rho), lame(vp0, vs0, rho0)
-    boxes = [(slice(nPml + 42, nPml + 58), slice(nPml + c, nPml + c + 16)) for c in (42, 92, 142)]    # the Vp, Vs and density boxes
     print("done: misfit %.4e -> %.4e" % (f0_, f))
-    for name, unit, mi, ti, si in zip(("Lambda", "Mu", "Den"), ("MPa", "MPa", "kg/m^3"), m, true, start):
+    if a.param == "vp_vs_den":
+        true, start, units, off = [torch.tensor(t, device=dev) for t in (vp, vs, rho)], [torch.tensor(t, device=dev) for t in (vp0, vs0, rho0)], ("m/s", "m/s", "kg/m^3"), 0
+    else:
+        true, start, units, off = lame(vp, vs, rho), lame(vp0, vs0, rho0), ("MPa", "MPa", "kg/m^3"), nPml
+    boxes = [(slice(off + 42, off + 58), slice(off + c, off + c + 16)) for c in (42, 92, 142)]    # the Vp, Vs and density boxes
+    for name, unit, mi, ti, si in zip(names, units, m, true, start):
         print("  %-6s update, extreme value inside the Vp / Vs / density box: %s %s   (true model: %s)" % (
             name, " / ".join("%+.1f" % float((mi - si)[b].flatten()[(mi - si)[b].abs().argmax()]) for b in boxes), unit,
             " / ".join("%+.1f" % float((ti - si)[b].flatten()[(ti - si)[b].abs().argmax()]) for b in boxes)))

@@ -335,6 +335,30 @@ int sepfwi_param_backward(int kind, int nz, int nx, int nPml, int nPad, const fl
                           void *hip_stream);
 
 /*
+ * The tangent of the same chain, and the diagonal of a Hessian pulled back through it.  With E the replicate padding,
+ * p_m = Mask E p + (1 - Mask) p_ref and map_kind the per-cell map of sepfwi_param_forward,
+ *     P = d(Lambda, Mu, Den) / d(A, B, C) = Dmap_kind(p_m) diag(Mask) E,
+ * a linear operator from three (nz, nx) arrays to three padded ones.  sepfwi_param_backward is its exact transpose P^T (the same
+ * float32 partials up to rounding; <P v, w> = <v, P^T w>), so a Hessian H_m in (Lambda, Mu, Den) becomes H_p = P^T H_m P in the
+ * user's parameters (Gauss-Newton: the second-order term of the map is left out).
+ *   sepfwi_param_jvp   (dLambda, dMu, dDen) = P (dA, dB, dC): forward-mode differentiation of the float32 operation list of the
+ *                      forward map, one launch over the padded grid.  dA, dB, dC: (nz, nx); each may be NULL, a field that is not
+ *                      inverted, read as 0 -- bit for bit the result with an array of zeros.  No special cases: where the
+ *                      forward map divides by zero the tangent is IEEE inf / nan.  0 wherever Mask is 0.
+ *   sepfwi_param_diag  (hA, hB, hC) = diag(P^T diag(hLambda, hMu, hDen) P):
+ *                      hA[s] = sum over the padded cells o that replicate s of Mask(o)^2 sum_k (d m_k / d A at o)^2 h_k(o),
+ *                      e.g. the diagonal pseudo-Hessian of sepfwi_get_pseudo_hessian in the user's parameters.  One launch over the
+ *                      physical grid and one over its rim (fixed summation order, no atomics), as sepfwi_param_backward.
+ * Arrays, sizes, kinds, stream and errors as above (a bad kind or size: SEPFWI_EINVAL before any device is touched).
+ */
+int sepfwi_param_jvp(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                     const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *dA,
+                     const float *dB, const float *dC, float *dLambda, float *dMu, float *dDen, void *hip_stream);
+int sepfwi_param_diag(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *hLambda,
+                      const float *hMu, const float *hDen, float *hA, float *hB, float *hC, void *hip_stream);
+
+/*
  * Test hook: wavefield `which` (0..4: vz, vx, szz, sxx, sxz; 5..9: their adjoint twins; 10..14: the scattered fields of the last
  * sepfwi_born call) of forward lane `lane` as the last sepfwi_cufd* / sepfwi_born call on (para_fname, gpu_id) left it, dense (nz - nPad, nx) row-major float32, host or device pointer.
  * After a gradient call the forward fields are the reverse-time RECONSTRUCTION run back to time step 0, i.e. they must

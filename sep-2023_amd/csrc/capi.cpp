@@ -268,9 +268,10 @@ struct DeviceRestore {
 };
 
 // every pointer of the fused parameterisation maps must be device memory of ONE device (the maps run where the tensors live)
-static int common_device(std::initializer_list<const void *> ptrs) {
+static int common_device(std::initializer_list<const void *> ptrs, bool skip_null = false) {
     int dev = -1;
     for (const void *p : ptrs) {
+        if (!p && skip_null) continue;  // an optional array (sepfwi_param_jvp's tangents)
         const int d = ptr_device(p);
         if (d < 0) throw std::invalid_argument("param maps: every array must be device memory (the host chain stays in torch)");
         if (dev >= 0 && d != dev) throw std::invalid_argument("param maps: arrays live on different devices");
@@ -307,6 +308,35 @@ int sepfwi_param_backward(int kind, int nz, int nx, int nPml, int nPad, const fl
         if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
         launch_param_bwd((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, gLambda, gMu, gDen, gA,
                          gB, gC);
+        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
+    });
+}
+
+int sepfwi_param_jvp(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C, const float *A_ref,
+                     const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB, const float *dC,
+                     float *dLambda, float *dMu, float *dDen, void *hip_stream) {
+    return guarded([&] {
+        check_param_dims(kind, nz, nx, nPml, nPad);
+        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, dLambda, dMu, dDen});
+        if (common_device({A, dA, dB, dC}, true) != dev) throw std::invalid_argument("param maps: arrays live on different devices");
+        DeviceRestore restore;
+        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
+        launch_param_jvp((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, dA, dB, dC, dLambda, dMu,
+                         dDen);
+        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
+    });
+}
+
+int sepfwi_param_diag(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C, const float *A_ref,
+                      const float *B_ref, const float *C_ref, const float *Mask, const float *hLambda, const float *hMu,
+                      const float *hDen, float *hA, float *hB, float *hC, void *hip_stream) {
+    return guarded([&] {
+        check_param_dims(kind, nz, nx, nPml, nPad);
+        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, hA, hB, hC});
+        DeviceRestore restore;
+        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
+        launch_param_diag((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, hA,
+                          hB, hC);
         if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
     });
 }

@@ -14,6 +14,10 @@
 // Same float32 operation order as the torch expressions (the library is built with -ffp-contract=off), divisions are
 // IEEE divisions, so the forward map equals the CPU torch result bit for bit; the backward sums the padding strips in a
 // fixed order (torch's replication_pad backward adds in another one: equal to rounding).
+//
+// The linearised chain (no counterpart in the reference): its tangent P = Dmap_kind(p_m) diag(Mask) E in one launch over the padded
+// grid (k_param_jvp; the backward launch above is P^T), and diag(P^T diag(h) P) in the backward's launch structure (k_param_diag,
+// k_param_diag_rim), both from map_jvp, forward-mode differentiation of the same float32 operation lists.
 #include <hip/hip_runtime.h>
 
 #include "param_maps.hpp"
@@ -303,6 +307,142 @@ __device__ __forceinline__ Triple map_bwd(int kind, float a, float b, float c, f
     return o;
 }
 
+// ---- tangents: forward-mode differentiation of exactly the float32 operation lists above, in their order (what torch.func.jvp
+// does with the torch expressions).  Quotient rule (dn - q dd) / d with q the quotient the forward pass formed, reciprocal rule
+// -dd (r r), square-root rule dA / (2 r).  No special cases: where the forward map divides by zero the tangent is IEEE inf / nan.
+__device__ __forceinline__ Triple vrh_jvp(float a, float b, float c, float da, float db, float dc) {
+    VrhMid q;
+    (void)vrh_fwd(a, b, c, q);
+    const float domp = -da, domc = -db, doms = -dc;
+    const float dks_v = RK_KC * db + RK_KQ * domc;
+    const float dkf_v = RK_KW * dc + RK_KH * doms;
+    const float dkv = (domp * q.ks_v + q.omp * dks_v) + (da * q.kf_v + a * dkf_v);
+    const float dr1 = db / RK_KC + domc / RK_KQ;
+    const float dr2 = dc / RK_KW + doms / RK_KH;
+    const float dkr1 = (domp * q.r1 + q.omp * dr1) + (da * q.r2 + a * dr2);
+    const float dkr = -dkr1 * (q.kr * q.kr);
+    const float dk = 0.5f * (dkv + dkr);
+    const float dms = RK_MUC * db + RK_MUQ * domc;
+    const float dmu0 = 0.5f * ((domp * q.ms + q.omp * dms) + 0.0f);
+    const float drho_f = RK_RHOW * dc + RK_RHOH * doms;
+    const float drho_s = RK_RHOC * db + RK_RHOQ * domc;
+    Triple o;
+    o.c = (drho_f * a + q.rho_f * da) + (drho_s * q.omp + q.rho_s * domp);
+    o.a = (dk - RK_23 * dmu0) / 1e6f;
+    o.b = dmu0 / 1e6f;
+    return o;
+}
+
+__device__ __forceinline__ Triple gas_jvp(float a, float b, float c, float da, float db, float dc) {
+    GasMid q;
+    (void)gas_fwd(a, b, c, q);
+    const float doms = -dc, domc = -db, domp = -da;
+    const float drho_f = RK_RHOW * dc + RK_RHOH * doms;
+    const float dk_f = RK_KW * dc + RK_KH * doms;
+    const float dk_s = RK_KC * db + RK_KQ * domc;
+    const float dmu_s = RK_MUC * db + RK_MUQ * domc;
+    const float drho_s = RK_RHOC * db + RK_RHOQ * domc;
+    const float dd1 = RK_CS * da;
+    const float dq1 = (domp - q.q1 * dd1) / q.d1;
+    const float dk_d = dk_s * q.q1 + q.k_s * dq1;
+    const float dd2 = RK_CS15 * da;
+    const float dq2 = (domp - q.q2 * dd2) / q.d2;
+    const float dmu_d = dmu_s * q.q2 + q.mu_s * dq2;
+    const float de1 = (domp - q.e1 * da) / a;
+    const float de2 = (dk_f - q.e2 * dk_s) / q.k_s;
+    const float de3 = dk_s - (dk_s * a + q.k_s * da);
+    const float de4 = (dk_d - q.e4 * de3) / q.e3;
+    const float de5 = -de4;
+    const float de12 = de1 * q.e2 + q.e1 * de2;
+    const float dDelta = de12 * q.e5 + q.e12 * de5;
+    const float ddenom = da * q.dd + a * dDelta;
+    const float du3 = (dk_d - q.u3 * dk_s) / q.k_s;
+    const float du5 = -(da * q.u3 + q.u2 * du3);
+    const float dnum = (da * q.k_d + a * dk_d) + (du5 * q.k_f + q.u5 * dk_f);
+    const float dk_u = (dnum - q.k_u * ddenom) / q.denom;
+    const float drho = (drho_f * a + q.rho_f * da) + (drho_s * q.omp + q.rho_s * domp);
+    const float dnA = dk_u + 0.75f * dmu_d;
+    const float dA = (dnA - q.A * drho) / q.rho;
+    const float dvp = dA / (2.0f * q.vp);
+    const float dBq = (dmu_d - q.Bq * drho) / q.rho;
+    const float dvs = dBq / (2.0f * q.vs);
+    const float dvp2 = (2.0f * q.vp) * dvp;
+    const float dvs2 = (2.0f * q.vs) * dvs;
+    const float dw = dvp2 - dvs2 * 2.0f;
+    Triple o;
+    o.a = (drho * q.w + q.rho * dw) / 1e6f;
+    o.b = (drho * q.vs2 + q.rho * dvs2) / 1e6f;
+    o.c = drho;
+    return o;
+}
+
+// (dA_m, dB_m, dC_m) at a padded cell -> (dLambda, dMu, dDen) there: the Jacobian of map_fwd at (a, b, c) applied to the tangent
+__device__ __forceinline__ Triple map_jvp(int kind, float a, float b, float c, float da, float db, float dc) {
+    Triple o;
+    switch (kind) {
+        case PARAM_VP_VS_DEN: {
+            const float t2 = b * b, dt2 = (2.0f * b) * db;
+            const float t4 = a * a - 2.0f * t2, dt4 = (2.0f * a) * da - 2.0f * dt2;
+            o.a = (dt4 * c + t4 * dc) / 1e6f;
+            o.b = (dt2 * c + t2 * dc) / 1e6f;
+            o.c = dc;
+            break;
+        }
+        case PARAM_LAM_MU_DEN:
+            o.a = da;
+            o.b = db;
+            o.c = dc;
+            break;
+        case PARAM_IP_IS_DEN: {
+            const float t2 = b * b, dt2 = (2.0f * b) * db;
+            const float t4 = a * a - 2.0f * t2, dt4 = (2.0f * a) * da - 2.0f * dt2;
+            o.a = (dt4 - (t4 / c) * dc) / c;
+            o.b = (dt2 - (t2 / c) * dc) / c;
+            o.c = dc;
+            break;
+        }
+        case PARAM_VP_VS_IP: {
+            const float t2 = b * b, dt2 = (2.0f * b) * db;
+            const float u3 = 2.0f * c / a, du3 = (2.0f * dc - u3 * da) / a;
+            const float r = c / a, dr = (dc - r * da) / a;
+            o.a = (dc * a + c * da) - (du3 * t2 + u3 * dt2);
+            o.b = dr * t2 + r * dt2;
+            o.c = dr;
+            break;
+        }
+        case PARAM_VP_VS_IS: {
+            const float t1 = a * a, dt1 = (2.0f * a) * da;
+            const float r = c / b, dr = (dc - r * db) / b;
+            const float w1 = 2.0f * c;
+            o.a = (dr * t1 + r * dt1) - ((2.0f * dc) * b + w1 * db);
+            o.b = dc * b + c * db;
+            o.c = dr;
+            break;
+        }
+        case PARAM_ROCK_VRH:
+            o = vrh_jvp(a, b, c, da, db, dc);
+            break;
+        default:  // PARAM_ROCK_GASSMANN
+            o = gas_jvp(a, b, c, da, db, dc);
+            break;
+    }
+    return o;
+}
+
+// One padded cell's term of diag(P^T diag(h) P): Mask^2 times the column sums of squares of the map's Jacobian, weighted by h.
+// The nine partials are three map_jvp calls on unit tangents.
+__device__ __forceinline__ Triple map_diag(int kind, float m, float a, float b, float c, float hl, float hm, float hd) {
+    const Triple ja = map_jvp(kind, a, b, c, 1.0f, 0.0f, 0.0f);
+    const Triple jb = map_jvp(kind, a, b, c, 0.0f, 1.0f, 0.0f);
+    const Triple jc = map_jvp(kind, a, b, c, 0.0f, 0.0f, 1.0f);
+    const float mm = m * m;
+    Triple o;
+    o.a = mm * ((ja.a * ja.a) * hl + (ja.b * ja.b) * hm + (ja.c * ja.c) * hd);
+    o.b = mm * ((jb.a * jb.a) * hl + (jb.b * jb.b) * hm + (jb.c * jb.c) * hd);
+    o.c = mm * ((jc.a * jc.a) * hl + (jc.b * jc.b) * hm + (jc.c * jc.c) * hd);
+    return o;
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 }  // namespace
@@ -387,6 +527,88 @@ __global__ void k_param_bwd_rim(int kind, int nz, int nx, int nPml, int nzp, int
     }
 }
 
+// The tangent of the whole chain, P = Dmap(p_m) diag(Mask) E: one thread per PADDED cell, index math of k_param_fwd.  A NULL dA / dB /
+// dC is a field that is not inverted: read as 0.0f through the same arithmetic, so the result equals that of an array of zeros.
+__global__ void k_param_jvp(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
+                            const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
+                            const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
+                            const float *__restrict__ dA, const float *__restrict__ dB, const float *__restrict__ dC,
+                            float *__restrict__ dLam, float *__restrict__ dMu, float *__restrict__ dDen) {
+    const int X = blockIdx.x * blockDim.x + threadIdx.x, Z = blockIdx.y * blockDim.y + threadIdx.y;
+    if (X >= nxp || Z >= nzp) return;
+    const size_t o = (size_t)Z * nxp + X;
+    const size_t s = (size_t)clampi(Z - nPml, 0, nz - 1) * nx + clampi(X - nPml, 0, nx - 1);  // replicate padding
+    const float m = Mask[o], w = 1.0f - m;
+    const float da = dA ? dA[s] : 0.0f, db = dB ? dB[s] : 0.0f, dc = dC ? dC[s] : 0.0f;
+    const Triple r = map_jvp(kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], m * da, m * db, m * dc);
+    dLam[o] = r.a;
+    dMu[o] = r.b;
+    dDen[o] = r.c;
+}
+
+// diag(P^T diag(h) P), launch structure of k_param_bwd / k_param_bwd_rim: one thread per PHYSICAL cell for the padded cell that is
+// the cell itself ...
+__global__ void k_param_diag(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
+                             const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
+                             const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
+                             const float *__restrict__ hLam, const float *__restrict__ hMu, const float *__restrict__ hDen,
+                             float *__restrict__ hA, float *__restrict__ hB, float *__restrict__ hC) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= nx || z >= nz) return;
+    const size_t s = (size_t)z * nx + x, o = (size_t)(z + nPml) * nxp + (x + nPml);
+    const float m = Mask[o], w = 1.0f - m;
+    const Triple d = map_diag(kind, m, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], hLam[o], hMu[o], hDen[o]);
+    hA[s] = d.a;
+    hB[s] = d.b;
+    hC[s] = d.c;
+}
+
+// ... and one WAVE per rim cell for the padded cells that replicate it: lanes stride row-major, a shuffle tree, lane 0 adds.
+__global__ void k_param_diag_rim(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
+                                 const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
+                                 const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
+                                 const float *__restrict__ hLam, const float *__restrict__ hMu, const float *__restrict__ hDen,
+                                 float *__restrict__ hA, float *__restrict__ hB, float *__restrict__ hC) {
+    const int lane = threadIdx.x & 63;
+    int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // rim cell, numbered as in k_param_bwd_rim
+    int z, x;
+    if (r < nx) { z = 0; x = r; }
+    else if (r < 2 * nx) { z = nz - 1; x = r - nx; }
+    else if (r < 2 * nx + (nz - 2)) { z = r - 2 * nx + 1; x = 0; }
+    else if (r < 2 * nx + 2 * (nz - 2)) { z = r - 2 * nx - (nz - 2) + 1; x = nx - 1; }
+    else return;
+    if (nz == 1 && r >= nx) return;
+    if (nx == 1 && r >= 2 * nx && r >= 2 * nx + (nz - 2)) return;
+    const size_t s = (size_t)z * nx + x;
+    const int Z0 = (z == 0) ? 0 : z + nPml, Z1 = (z == nz - 1) ? nzp - 1 : z + nPml;
+    const int X0 = (x == 0) ? 0 : x + nPml, X1 = (x == nx - 1) ? nxp - 1 : x + nPml;
+    const int w_ = X1 - X0 + 1, cnt = (Z1 - Z0 + 1) * w_;
+    const float a0 = A[s], b0 = B[s], c0 = C[s];
+    float ha = 0.0f, hb = 0.0f, hc = 0.0f;
+    for (int k = lane; k < cnt; k += 64) {
+        const int Z = Z0 + k / w_, X = X0 + k % w_;
+        if (Z == z + nPml && X == x + nPml) continue;  // the cell itself
+        const size_t o = (size_t)Z * nxp + X;
+        const float m = Mask[o];
+        if (m == 0.0f) continue;
+        const float w = 1.0f - m;
+        const Triple d = map_diag(kind, m, m * a0 + w * A_ref[o], m * b0 + w * B_ref[o], m * c0 + w * C_ref[o], hLam[o], hMu[o], hDen[o]);
+        ha += d.a;
+        hb += d.b;
+        hc += d.c;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        ha += __shfl_down(ha, off, 64);
+        hb += __shfl_down(hb, off, 64);
+        hc += __shfl_down(hc, off, 64);
+    }
+    if (lane == 0) {
+        hA[s] += ha;
+        hB[s] += hb;
+        hC[s] += hc;
+    }
+}
+
 void launch_param_fwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, float *Lam, float *Mu,
                       float *Den) {
@@ -404,6 +626,25 @@ void launch_param_bwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nP
     const int rim = 2 * nx + 2 * (nz > 2 ? nz - 2 : 0);
     hipLaunchKernelGGL(k_param_bwd_rim, dim3((rim + 3) / 4), dim3(256), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C, A_ref, B_ref,
                        C_ref, Mask, gLam, gMu, gDen, gA, gB, gC);
+}
+
+void launch_param_jvp(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB,
+                      const float *dC, float *dLam, float *dMu, float *dDen) {
+    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
+    hipLaunchKernelGGL(k_param_jvp, dim3((nxp + 63) / 64, (nzp + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
+                       A_ref, B_ref, C_ref, Mask, dA, dB, dC, dLam, dMu, dDen);
+}
+
+void launch_param_diag(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *hLam,
+                       const float *hMu, const float *hDen, float *hA, float *hB, float *hC) {
+    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
+    hipLaunchKernelGGL(k_param_diag, dim3((nx + 63) / 64, (nz + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
+                       A_ref, B_ref, C_ref, Mask, hLam, hMu, hDen, hA, hB, hC);
+    const int rim = 2 * nx + 2 * (nz > 2 ? nz - 2 : 0);
+    hipLaunchKernelGGL(k_param_diag_rim, dim3((rim + 3) / 4), dim3(256), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C, A_ref, B_ref,
+                       C_ref, Mask, hLam, hMu, hDen, hA, hB, hC);
 }
 
 }  // namespace sepfwi

@@ -22,5 +22,13 @@ void launch_param_fwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nP
 void launch_param_bwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *gLam,
                       const float *gMu, const float *gDen, float *gA, float *gB, float *gC);
+// the tangent P = Dmap(p_m) diag(Mask) E of the chain (launch_param_bwd is its transpose); dA, dB, dC may each be NULL (= 0)
+void launch_param_jvp(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB,
+                      const float *dC, float *dLam, float *dMu, float *dDen);
+// diag(P^T diag(h) P): h on the padded grid -> the (nz, nx) grid, rim sum and Mask^2 included
+void launch_param_diag(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
+                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *hLam,
+                       const float *hMu, const float *hDen, float *hA, float *hB, float *hC);
 
 }  // namespace sepfwi

@@ -99,6 +99,8 @@ def lib():
     L.sepfwi_get_option.argtypes = [C.c_char_p]
     L.sepfwi_param_forward.argtypes = [C.c_int] * 5 + [fp] * 10 + [C.c_void_p]
     L.sepfwi_param_backward.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
+    L.sepfwi_param_jvp.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
+    L.sepfwi_param_diag.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
     L.sepfwi_debug_field.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, fp]
     L.sepfwi_debug_live_bytes.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.sepfwi_loop_status.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int]
@@ -115,7 +117,7 @@ def lib():
     for f in ("sepfwi_cufd", "sepfwi_cufd_stream", "sepfwi_cpml_profiles", "sepfwi_stf_taper", "sepfwi_shot_split",
               "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes", "sepfwi_set_observed",
               "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact", "sepfwi_born_src",
-              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_version", "sepfwi_device_count"):
+              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_version", "sepfwi_device_count"):
         getattr(L, f).restype = C.c_int
     L.sepfwi_release_all.restype = None
     L.sepfwi_invalidate_observed.restype = None
@@ -127,7 +129,7 @@ EXPORTS = ["sepfwi_last_error", "sepfwi_version", "sepfwi_device_count", "sepfwi
            "sepfwi_release_all", "sepfwi_invalidate_observed", "sepfwi_cpml_profiles", "sepfwi_stf_taper",
            "sepfwi_shot_split", "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes",
            "sepfwi_set_observed", "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact",
-           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward"]
+           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag"]
 
 
 class SepFwiError(RuntimeError):

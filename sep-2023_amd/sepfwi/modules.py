@@ -113,18 +113,118 @@ class _MaskedTriple(nn.Module):
                 and all(tuple(t.shape) == padded_shape and t.dtype == torch.float32 and t.device == self.Mask.device for t in refs)
                 and self.Mask.dtype == torch.float32 and tuple(self.Mask.shape) == padded_shape)
 
-    def lame_padded(self):
-        """-> Lambda [MPa], Mu [MPa], Den on the padded grid, differentiable w.r.t. the module's parameters."""
+    def lame_padded(self, cur=None):
+        """-> Lambda [MPa], Mu [MPa], Den on the padded grid, differentiable w.r.t. the module's parameters (cur: other tensors in
+        the places of the three fields)."""
+        cur = [getattr(self, n) for n in self.NAMES] if cur is None else cur
         if self._fusable():
-            cur = [getattr(self, n) for n in self.NAMES]
             refs = [getattr(self, n + "_ref").contiguous() for n in self.NAMES]
             return _FusedParamMap.apply(cur[0], cur[1], cur[2], refs[0], refs[1], refs[2], self.Mask.contiguous(),
                                         int(self.KIND), int(self.nPml), int(self.nPad))
-        return self.lame(*self._masked())
+        return self._chain(*cur)
 
     def forward(self, Shot_ids, ngpu=1):
         Lambda, Mu, Den = self.lame_padded()
         return FWIFunction.apply(Lambda, Mu, Den, self.Stf, ngpu, Shot_ids, self.para_fname)
+
+    # -- the linearised chain in the module's own parameters (an extension without a counterpart in the reference) ------------
+    # P = d(Lambda, Mu, Den) / d(A, B, C) = Dlame(p_m) diag(Mask) E at the module's current fields, E the (resize and) replicate
+    # padding, p_m = Mask E p + (1 - Mask) p_ref (include/sepfwi.h, sepfwi_param_jvp).
+
+    def _chain(self, a, b, c):
+        pad = ft.padding(a, b, c, self.nz_orig, self.nx_orig, self.nz, self.nx, self.nPml, self.nPad)
+        return self.lame(*[self.Mask * p + (1.0 - self.Mask) * getattr(self, n + "_ref") for n, p in zip(self.NAMES, pad)])
+
+    def _fields(self):
+        return [getattr(self, n).detach() for n in self.NAMES]
+
+    def _native_args(self, cur):
+        p = lambda t: C.c_void_p(t.data_ptr())
+        keep = [t.contiguous() for t in cur] + [getattr(self, n + "_ref").contiguous() for n in self.NAMES] + [self.Mask.contiguous()]
+        st = torch.cuda.current_stream(self.Mask.device).cuda_stream
+        return keep, [int(self.KIND), self.nz_orig, self.nx_orig, int(self.nPml), int(self.nPad)] + [p(t) for t in keep], C.c_void_p(st) if st else None
+
+    def _like(self, t, ref, what):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(ref.shape):
+            raise ValueError("%s must be a tensor of shape %s (or None)" % (what, tuple(ref.shape)))
+        return t.detach().to(device=ref.device, dtype=ref.dtype).contiguous()
+
+    def tangent(self, dA, dB, dC):
+        """P v: the first-order change (dLambda, dMu, dDen) on the padded grid for a perturbation v = (dA, dB, dC) of the three fields
+        (each in its field's shape; None: a field that is not perturbed, e.g. one that is not inverted).  On HIP tensors one
+        launch (sepfwi_param_jvp), otherwise torch.func.jvp through the module's own padding, blend and Lame map.  `pullback` is the
+        transpose."""
+        cur = self._fields()
+        v = [self._like(t, f, "d" + n) for t, f, n in zip((dA, dB, dC), cur, self.NAMES)]
+        if self._fusable():
+            keep, args, st = self._native_args(cur)
+            outs = [torch.empty_like(keep[-1]) for _ in range(3)]      # the padded grid, contiguous
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            _native.check(_native.lib().sepfwi_param_jvp(*args, *[ptr(t) for t in v], *[ptr(t) for t in outs], st))
+            return tuple(outs)
+        v = [torch.zeros_like(f) if t is None else t for t, f in zip(v, cur)]
+        return tuple(torch.func.jvp(self._chain, tuple(cur), tuple(v))[1])
+
+    def pullback(self, gLambda, gMu, gDen):
+        """P^T w: (gLambda, gMu, gDen) on the padded grid (entries may be None) -> (gA, gB, gC) in the shapes of the three fields,
+        whether or not a field is a parameter -- the chain rule of `lame_padded` (on HIP tensors the fused sepfwi_param_backward)."""
+        cur = [t.clone().requires_grad_(True) for t in self._fields()]
+        outs = self.lame_padded(cur)
+        pairs = [(o, g.detach().to(device=o.device, dtype=o.dtype)) for o, g in zip(outs, (gLambda, gMu, gDen)) if g is not None]
+        if not pairs:
+            return tuple(torch.zeros_like(t) for t in cur)
+        gs = torch.autograd.grad([o for o, _ in pairs], cur, [g for _, g in pairs], allow_unused=True)
+        return tuple(torch.zeros_like(t) if g is None else g for g, t in zip(gs, cur))
+
+    def diag(self, hLambda, hMu, hDen):
+        """diag(P^T diag(h) P): a diagonal (pseudo-)Hessian of (Lambda, Mu, Den) on the padded grid -> that of the module's three
+        fields, hA[s] = sum over the padded cells o that replicate s of Mask(o)^2 sum_k (d m_k / d A at o)^2 h_k(o) -- a Jacobi
+        preconditioner for `gauss_newton` (obj_wrapper.gauss_newton_cg(diag=)).  Unlike utils.pseudo_hessian_vp_vs_den, which is cell
+        by cell for (Vp, Vs, Den) only, this applies the sum over the replicated rim and Mask^2, for every parameterisation.  On HIP
+        tensors sepfwi_param_diag, otherwise the same sum in torch (identity resize only)."""
+        cur = self._fields()
+        h = [self._like(t, self.Mask, "h" + n) for t, n in zip((hLambda, hMu, hDen), ("Lambda", "Mu", "Den"))]
+        if any(t is None for t in h):
+            raise ValueError("diag needs all of hLambda, hMu, hDen")
+        if self._fusable():
+            keep, args, st = self._native_args(cur)
+            outs = [torch.empty_like(t) for t in keep[:3]]
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            _native.check(_native.lib().sepfwi_param_diag(*args, *[ptr(t) for t in h], *[ptr(t) for t in outs], st))
+            return tuple(outs)
+        if (self.nz, self.nx) != (self.nz_orig, self.nx_orig):
+            raise NotImplementedError("diag: the padding's entries are 0 / 1 only without the bilinear resize")
+        leaf = [t.clone().requires_grad_(True) for t in cur]
+        pad = ft.padding(*leaf, self.nz_orig, self.nx_orig, self.nz, self.nx, self.nPml, self.nPad)
+        pm = tuple((self.Mask * p + (1.0 - self.Mask) * getattr(self, n + "_ref")).detach() for n, p in zip(self.NAMES, pad))
+        one, zero = torch.ones_like(pm[0]), torch.zeros_like(pm[0])
+        cells = []
+        for k in range(3):   # column k of the map's Jacobian at every padded cell
+            col = torch.func.jvp(self.lame, pm, tuple(one if j == k else zero for j in range(3)))[1]
+            cells.append(self.Mask * self.Mask * sum((c * c) * hk for c, hk in zip(col, h)))
+        return tuple(g.detach() for g in torch.autograd.grad(pad, leaf, cells))    # E^T: E has entries 0 / 1, so E^2 = E
+
+    def _model(self):
+        with torch.no_grad():
+            return [t.detach().contiguous() for t in self.lame_padded()]
+
+    def born(self, v, Shot_ids, components=("ett",)):
+        """Born modelling in the module's own parameters, J P v: fwi_ops.born at the module's current model for the perturbation
+        `tangent(*v)`; v = (dA, dB, dC), entries may be None.  -> one dict per shot, as fwi_ops.born.  One GPU only."""
+        return fwi_ops.born(*self._model(), *self.tangent(*v), self.Stf, 1, Shot_ids, self.para_fname, components)
+
+    def gauss_newton(self, v, Shot_ids, exact=False):
+        """The Gauss-Newton Hessian-vector product in the module's own parameters, H_p v = P^T H_m P v: `pullback` of
+        fwi_ops.gauss_newton for `tangent(*v)` at the module's current model.  v = (dA, dB, dC) in the shapes of the three fields
+        (None: a field that is not inverted) -> three tensors in those shapes.  The second-order term of the parameter map is left
+        out (Gauss-Newton, not Newton).  One GPU only, as the ops.
+        exact=True: H_m = P_Omega J^T W J P_Omega with the exact discrete adjoint; the restriction P_Omega sits inside H_m, so
+        H_p = (J P_Omega P)^T W (J P_Omega P) is symmetric and non-negative for ANY Mask, v^T H_p v = |W^1/2 J P_Omega P v|^2 to
+        float32 rounding.  exact=False: the reference's backward pass in the place of J^T (sepfwi_born's product)."""
+        hv = fwi_ops.gauss_newton(*self._model(), *self.tangent(*v), self.Stf, 1, Shot_ids, self.para_fname, exact=exact)
+        return self.pullback(*hv)
 
 
 class FWI(_MaskedTriple):

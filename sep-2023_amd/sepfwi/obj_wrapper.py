@@ -10,9 +10,11 @@ from scipy import optimize
 
 
 class PyTorchObjective(object):
-    def __init__(self, obj, loss):
+    def __init__(self, obj, loss, shot_ids=None, exact=True):
         self.obj = obj      # nn.Module holding the parameters (and .Bounds)
         self.loss = loss    # callable -> scalar tensor
+        self.shot_ids = shot_ids   # for hessp: the shots of obj.gauss_newton (None: no hessp)
+        self.exact = exact         # ... and its adjoint (True: symmetric and non-negative, what trust-ncg / Newton-CG assume)
         params = OrderedDict(obj.named_parameters())
         self.param_shapes = OrderedDict((n, tuple(p.shape)) for n, p in params.items())
         self.x0 = np.concatenate([p.data.cpu().numpy().ravel() for p in params.values()]).astype(np.float64)
@@ -39,11 +41,14 @@ class PyTorchObjective(object):
             return True
         return np.abs(np.array(x) - np.array(self.cached_x)).max() > 1e-8
 
-    def cache(self, x):
+    def load(self, x):
         state = self.unpack_parameters(x)
         for name, buf in self.obj.named_buffers():
             state[name] = buf
         self.obj.load_state_dict(state)
+
+    def cache(self, x):
+        self.load(x)
         self.cached_x = x
         self.obj.zero_grad()
         val = self.loss()
@@ -60,6 +65,25 @@ class PyTorchObjective(object):
         if self.is_new(x):
             self.cache(x)
         return self.jac
+
+    def hessp(self, x, p):
+        """The Gauss-Newton Hessian at x times p, flat float64 in and out -- what `optimize.minimize(fun, x0, jac=, hessp=,
+        method="trust-ncg")` (or "Newton-CG") takes; an extension without a counterpart in the reference.  p is scattered over the
+        module's parameters in named_parameters() order (a field of the module that is not a parameter gets None), the product is
+        obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient."""
+        if self.shot_ids is None:
+            raise ValueError("hessp needs the shots of the Gauss-Newton product: PyTorchObjective(obj, loss, shot_ids=...)")
+        if not hasattr(self.obj, "gauss_newton"):
+            raise ValueError("hessp needs a module with a gauss_newton(v, Shot_ids, exact=) method")
+        if self.is_new(x):
+            self.load(x)
+            self.__dict__.pop("cached_x", None)      # the module has left the cached point: the next fun / jac evaluates again
+        params = OrderedDict(self.obj.named_parameters())
+        fields = tuple(getattr(self.obj, "NAMES", tuple(params)))
+        chunks = self.unpack_parameters(np.asarray(p, dtype=np.float64))
+        v = tuple(chunks[n].to(device=params[n].device, dtype=params[n].dtype) if n in params else None for n in fields)
+        hv = self.obj.gauss_newton(v, self.shot_ids, exact=self.exact)
+        return np.concatenate([hv[fields.index(n)].detach().cpu().numpy().ravel() for n in params]).astype(np.float64)
 
 
 _SETULB_SIGNATURE = "setulb(m,x,l,u,nbd,f,g,factr,pgtol,wa,iwa,task,lsave,isave,dsave,maxls,ln_task)"
