@@ -172,6 +172,18 @@ def inputs_discriminate(O, pb, jv, what):
     return c1
 
 
+def discrimination(O, pb, gathers):
+    """inputs_discriminate for several gathers at once, without the assertion: gathers {name: per-shot list}
+    -> ({name: (|C d| / |d|, |C C d| / |C d|)}, whether every ratio differs from 1 by more than 10 %)"""
+    out = {}
+    for name, d in gathers.items():
+        c1 = C_all(O, pb, d)
+        c2 = C_all(O, pb, c1)
+        n0, n1, n2 = norm(d), norm(c1), norm(c2)
+        out[name] = (n1 / n0, n2 / n1) if n0 > 0 and n1 > 0 else (1.0, 1.0)
+    return out, all(abs(r - 1.0) > 0.10 for pair in out.values() for r in pair)
+
+
 def oracle_gathers(lib, pb, model):
     """the oracle's raw axial-strain gathers of a model, per shot (nrec, nSteps) float32, and all four components for cufd's obs"""
     plain = {k: val for k, val in pb["para"].items() if k not in COND_KEYS}

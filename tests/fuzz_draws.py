@@ -4,7 +4,8 @@ files see; tests/test_gauge_reference.py, tests/test_born_fuzz_reference.py and 
 the first 16 seeds' draws
 (draw_problem; draw_gauge, draw_born and draw_exact change its draw for tests/test_gpu_gauge_fuzz.py, test_gpu_born_fuzz.py and
 test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw; draw_pseudo_hessian adds to it, and changes nothing, for
-tests/test_gpu_pseudo_hessian_fuzz.py)."""
+tests/test_gpu_pseudo_hessian_fuzz.py; draw_conditioned puts draw_born's draw under live conditioning keys for
+tests/test_gpu_conditioned_gn_fuzz.py, its digest is in tests/test_conditioned_fuzz_reference.py)."""
 import json
 import os
 
@@ -358,8 +359,81 @@ def perturbations(d, e):
     return v, X.on_omega(pb, dm)
 
 
+# ---- conditioned Gauss-Newton (if_win / filter) ------------------------------------------------------------------------------------
+COND_SEED0 = 98035      # offset of the generator (how it was chosen: tests/test_conditioned_fuzz_reference.py)
+COND_MODES = ("filter", "window", "both", "narrow")      # the names of cond_gn_ref
+COND_CORNERS = (0.1, 0.5, 0.6, 1.2)      # x f0.  Not cond_gn_ref.CORNERS: on these draws that band leaves |C C d| within 7 % of |C d|
+COND_MAX = (4, 128)                      # shots and channels a draw_problem survey can hold: the window draws have this shape for every seed
+
+
+def conditioned_raw(seed):
+    """What draw_conditioned draws for a seed before it looks at the problem or at a gather; every quantity for every seed."""
+    rg = np.random.default_rng(COND_SEED0 + seed)
+    raw = dict(mode=COND_MODES[int(rg.integers(0, len(COND_MODES)))], u1=rg.uniform(size=COND_MAX), u2=rg.uniform(size=COND_MAX),
+               weights=rg.uniform(0.5, 2.0, COND_MAX), want_empty=int(rg.integers(0, 4)) == 0, empty_u=[float(u) for u in rg.uniform(size=2)])
+    raw["v_seeds"] = [int(s) for s in rg.integers(0, 2 ** 31, size=2)]
+    return raw
+
+
+def energy_times(trace, dt, T):
+    """(t10, t90): the times at which the cumulative energy of a trace reaches 10 % and 90 %; (0, T) for a dead trace"""
+    e = np.cumsum(np.asarray(trace, np.float64) ** 2)
+    if not e[-1] > 0:
+        return 0.0, T
+    return float(np.searchsorted(e, 0.1 * e[-1]) * dt), float(np.searchsorted(e, 0.9 * e[-1]) * dt)
+
+
+def draw_conditioned(d, b, seed, syn):
+    """The draw (d: draw_problem, b: draw_born) under live conditioning keys, as the docstring of tests/test_gpu_conditioned_gn_fuzz.py
+    says.  syn: per shot the REFERENCE's (nrec, nSteps) axial-strain gather at lame_init (plain oracle build) -- the windows are placed on
+    its arrivals, from the reference side alone.  No joint weights: misfit_w_* leave d's parameter file and b["weights"] becomes None
+    (config.cpp refuses them together with conditioning keys); everything else of draw_born stays, and d's two files remain the same
+    problem WITHOUT the keys.  The conditioned pair is written next to them with cond_gn_ref.write_files.
+    -> dict(mode, pb (a shallow copy of d["pb"] on the conditioned pair, with "survey" and "data_dir"), empty ((shot, channel) of the
+    empty window, or None), v_seeds)."""
+    import cond_gn_ref as G
+    pb, sv = d["pb"], d["sv"]
+    raw = conditioned_raw(seed)
+    mode = raw["mode"]
+    plain = {k: v for k, v in pb["para"].items() if k not in COND_KEYS and not k.startswith("misfit_w_")}
+    json.dump(plain, open(pb["para_fname"], "w"))
+    pb["para"] = plain
+    b["weights"] = None
+    ids = [int(i) for i in pb["Shot_ids"].tolist()]
+    dt, f0 = float(plain["dt"]), float(plain["f0"])
+    T = int(plain["nSteps"]) * dt
+    empty = None
+    if raw["want_empty"]:
+        k = int(raw["empty_u"][0] * len(ids))
+        empty = (k, int(raw["empty_u"][1] * int(sv["shot%d" % ids[k]]["nrec"])))
+    csv = dict(sv)
+    for k, sid in enumerate(ids):
+        sh = dict(sv["shot%d" % sid])
+        n = int(sh["nrec"])
+        assert np.shape(syn[k]) == (n, int(plain["nSteps"])) and n <= COND_MAX[1] and k < COND_MAX[0], (seed, k, np.shape(syn[k]))
+        t = [energy_times(syn[k][r], dt, T) for r in range(n)]
+        sh["win_start"] = [float(t10 + raw["u1"][k, r] * 0.5 * (t90 - t10)) for r, (t10, t90) in enumerate(t)]
+        sh["win_end"] = [float(t90 + raw["u2"][k, r] * 0.5 * (T - t90)) for r, (t10, t90) in enumerate(t)]
+        sh["weights"] = [float(w) for w in raw["weights"][k, :n]]
+        sh["src_weight"] = 0.3 + 0.05 * k      # below 1: with 3.0 the window's gain and the filter's loss cancel in mode "both"
+        if empty is not None and empty[0] == k:
+            sh["win_end"][empty[1]] = sh["win_start"][empty[1]]      # "Window error 1": the trace passes untouched
+        csv["shot%d" % sid] = sh
+    para = dict(plain)
+    if mode in ("filter", "both"):
+        para["filter"] = [c * f0 for c in COND_CORNERS]
+    if mode == "narrow":
+        para["filter"] = G.narrow(f0)
+    if mode in ("window", "both"):
+        para["if_win"] = True
+    cpb = dict(pb)
+    cpb["para_fname"], cpb["para"] = G.write_files(pb, "cond", para, csv)
+    cpb["survey"], cpb["survey_fname"], cpb["data_dir"] = csv, cpb["para"]["survey_fname"], cpb["para"]["data_dir_name"]
+    return dict(mode=mode, pb=cpb, empty=empty, v_seeds=raw["v_seeds"])
+
+
 # ---- the diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------
-PH_SEED0 = 97255      # (of the offsets 97000 ... 97399 the one whose default 16 seeds hold the most of the 17 option sets: 13, with batch = 0 and batch = 1 on multi-shot draws)
+PH_SEED0 = 97255     # (of the offsets 97000 ... 97399 the one whose default 16 seeds hold the most of the 17 option sets: 13, with batch = 0 and batch = 1 on multi-shot draws)
 PH_EVERY = (1, 2, 3, 5)
 PH_OPTION_SETS = OPTION_SETS + [o for o in BORN_OPTION_SETS if o not in OPTION_SETS]      # the union, every structure once
 

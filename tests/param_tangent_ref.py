@@ -1,4 +1,5 @@
-"""What the tests of the parameter chain's tangent share (tests/test_param_tangent_host.py, tests/test_gpu_param_tangent.py): seeded inputs
+"""What the tests of the parameter chain's tangent share (tests/test_param_tangent_host.py, tests/test_gpu_param_tangent.py, and on random
+grids tests/test_param_chain_fuzz_reference.py, tests/test_gpu_param_chain_fuzz.py): seeded inputs
 for the seven modules on a small grid, and the float64 references -- torch.func.jvp of the modules' own expression, its dense Jacobian.
 Nothing of the code under test is restated: the references differentiate `lame(blend(padding(.)))` of a float64 copy of the module.
 
@@ -123,6 +124,170 @@ def inputs(cls_name, dims, seed=SEED):
     w = [rng.standard_normal(padded_shape(dims)).astype(np.float32) for _ in range(3)]
     h = [rng.uniform(0.0, 1.0, padded_shape(dims)).astype(np.float32) for _ in range(3)]
     return f, mask, v, w, h
+
+
+# ---- random grids (tests/test_param_chain_fuzz_reference.py, tests/test_gpu_param_chain_fuzz.py) -------------------------------------
+# What the four fixed grids of tests/test_gpu_param_tangent.py leave out of k_param_bwd_rim / k_param_diag_rim: a rim cell with more
+# replicas than the 64 lanes of its wave (the corner rectangle has (nPml + 1)^2 cells), one-row, one-column and two-row grids with
+# padding, a strip lengthened by nPad, and padded widths on both sides of the 64-wide block.
+FUZZ_SEED0 = 31002      # offset of the generators below: of 31000 ... 31007 the one at which every default seed x class has a target
+#                         (settled_inputs; the others leave one to three rock-physics draws without one), searched on the CPU alone
+DEFAULT_SEEDS = range(16)
+WIDTHS = (63, 64, 65, 127, 128, 129)
+GRID_KINDS = ("one row", "one column", "two rows", "nPad without nPml", "three passes", "long strip") + tuple("width %d" % w for w in WIDTHS)
+MASK_KINDS = ("random", "ones", "interior", "fractional padding")
+
+
+def draw_grid(seed):
+    """-> (nz, nx, nPml, nPad).  The kind of grid goes round GRID_KINDS with the seed, so that any 12 consecutive seeds hold every
+    one; everything else is drawn.  The six tiny kinds have nz, nx in {1, 2, 3}, nPml 0 ... 12 and nPad 0 ... 8 -- except "long strip",
+    whose strip of nPml + nPad + 1 > 64 cells below a bottom-row cell that is no corner needs nPad 62 ... 72 (its lanes make two
+    passes over ONE column: k / w_ with w_ = 1).  The wide kinds have the padded width named, nz 3 ... 9 and a padded height that
+    is no multiple of the 4 rows of a block."""
+    rng = np.random.default_rng(FUZZ_SEED0 + seed)
+    small = [int(a) for a in rng.integers(1, 4, 2)]
+    nPml, nPad = int(rng.integers(0, 13)), int(rng.integers(0, 9))
+    extra = int(rng.integers(0, 9))
+    tall = int(rng.integers(3, 10))
+    kind = GRID_KINDS[seed % len(GRID_KINDS)]
+    nz, nx = small
+    if kind == "one row":
+        nz, nx = 1, max(nx, 2)
+    elif kind == "one column":
+        nz, nx = 3, 1
+    elif kind == "two rows":
+        nz = 2
+    elif kind == "nPad without nPml":
+        nPml, nPad = 0, max(nPad, 1)
+    elif kind == "three passes":
+        nPml, nPad = 11 + nPml % 2, max(nPad, 1)      # (nPml + 1)^2 = 144 or 169 > 128; the bottom strip lengthened by nPad
+        nz, nx = max(nz, 2), max(nx, 2)
+    elif kind == "long strip":
+        nz, nx, nPml = max(nz, 2), 3, nPml % 3      # a shallow layer: the corner rectangles stay at a few passes
+        nPad = 64 - nPml + extra                    # nPml + nPad + 1 >= 65
+    else:
+        width = int(kind.split()[1])
+        nz, nx = tall, width - 2 * nPml
+        while (nz + 2 * nPml + nPad) % 4 == 0:
+            nPad += 1
+    return nz, nx, nPml, nPad
+
+
+def fractional_padding_mask(rng, dims):
+    """1 on the physical cells, uniform in [0.1, 0.9] on the padding: the rim sums then carry the blend with the reference model, which
+    a unit mask switches off"""
+    nz, nx, nPml, _ = dims
+    m = rng.uniform(0.1, 0.9, padded_shape(dims)).astype(np.float32)
+    m[nPml:nPml + nz, nPml:nPml + nx] = 1.0
+    return m
+
+
+def fuzz_inputs(cls_name, seed, attempt=0):
+    """-> dims, mask kind, fields f (float64), Mask, a tangent v, weights w and a non-negative diagonal h (float32).  The grid, the
+    kind of mask and the signs belong to the seed; the values to the seed, the class and the attempt (settled_inputs).  v is 1 % noise
+    with ONE sign per field: per-cell signs let the three terms of an output cancel at a cell, and on a one-cell grid everywhere
+    (module docstring).  w has one sign per array too: a rim cell's sum runs over up to 200 replicas, and with per-cell signs its
+    float32 rounding is measured against a sum that has cancelled to a tenth of its terms."""
+    dims = draw_grid(seed)
+    rs = np.random.default_rng(FUZZ_SEED0 + 500000 + seed)
+    mask_kind = MASK_KINDS[int(rs.integers(0, len(MASK_KINDS)))]
+    signs, wsigns = rs.choice([-1.0, 1.0], 3), rs.choice([-1.0, 1.0], 3)
+    rng = np.random.default_rng([FUZZ_SEED0, seed, CLASSES.index(cls_name), attempt])
+    f = fields(cls_name, rng, dims[0], dims[1])
+    masks = dict(zip(MASK_KINDS, (random_mask(rng, dims), np.ones(padded_shape(dims), np.float32), interior_mask(dims),
+                                  fractional_padding_mask(rng, dims))))
+    v = [(s * np.abs(a)).astype(np.float32) for s, a in zip(signs, noise_v(rng, f))]
+    w = [(s * np.abs(rng.standard_normal(padded_shape(dims)))).astype(np.float32) for s in wsigns]
+    h = [rng.uniform(0.0, 1.0, padded_shape(dims)).astype(np.float32) for _ in range(3)]
+    return dims, mask_kind, f, masks[mask_kind], v, w, h
+
+
+def cell_terms64(mod64, h):
+    """What every padded cell adds to diag(P^T diag(h) P), per field.  Every padded cell depends on ONE physical cell, so the tangent
+    of the all-ones direction in field k holds at each padded cell the single non-zero entry of that field's Jacobian column there
+    (Mask included).  -> three float64 arrays on the padded grid"""
+    shp = tuple(getattr(mod64, mod64.NAMES[0]).shape)
+    out = []
+    for k in range(3):
+        t = tangent64(mod64, [np.ones(shp) if j == k else np.zeros(shp) for j in range(3)])
+        out.append(sum(np.asarray(hk, np.float64) * a * a for hk, a in zip(h, t)))
+    return out
+
+
+def diag_ref64(mod64, h):
+    """diag(P^T diag(h) P) for a grid of any size, no index arithmetic restated: E^T of cell_terms64, E^T the float64 autograd
+    transpose of utils.padding.  Three jvps and one autograd call.  -> three (nz, nx) arrays"""
+    leaf = [torch.zeros_like(getattr(mod64, n).detach()).requires_grad_(True) for n in mod64.NAMES]
+    pad = ft.padding(*leaf, mod64.nz_orig, mod64.nx_orig, mod64.nz, mod64.nx, mod64.nPml, mod64.nPad)
+    return [g.numpy() for g in torch.autograd.grad(pad, leaf, [torch.as_tensor(c) for c in cell_terms64(mod64, h)])]
+
+
+def pullback64(mod64, w):
+    """the float64 autograd gradient of <chain64(f), w> -> three (nz, nx) arrays"""
+    cur = [getattr(mod64, n).detach().clone().requires_grad_(True) for n in mod64.NAMES]
+    outs = chain64(mod64)(*cur)
+    return [g.numpy() for g in torch.autograd.grad(outs, cur, [torch.as_tensor(np.asarray(a, np.float64)) for a in w])]
+
+
+def rim_sum_restated(cells, dims, passes=None, one_row_twice=False):
+    """A host restatement of the rim kernels' sum, kept ONLY to show that the comparison can fail: E^T of three padded arrays with, per
+    physical cell, the padded cells that replicate it walked row-major as the lanes of a wave walk them.  passes=1 keeps the first 64
+    of them ("only the first pass of the lane loop"); one_row_twice adds the rim of a one-row grid a second time (its top and its
+    bottom row are the same cells).  With neither it is E^T."""
+    nz, nx, nPml, nPad = dims
+    nzp, nxp = padded_shape(dims)
+    out = [np.zeros((nz, nx)) for _ in cells]
+    for z in range(nz):
+        for x in range(nx):
+            Z = range(0 if z == 0 else z + nPml, nzp if z == nz - 1 else z + nPml + 1)
+            X = range(0 if x == 0 else x + nPml, nxp if x == nx - 1 else x + nPml + 1)
+            cover = [(a, b) for a in Z for b in X]
+            rim = [(a, b) for k, (a, b) in enumerate(cover) if (a, b) != (z + nPml, x + nPml) and (passes is None or k < 64 * passes)]
+            for o, c in zip(out, cells):
+                o[z, x] = c[z + nPml, x + nPml] + (2.0 if one_row_twice and nz == 1 else 1.0) * sum(c[a, b] for a, b in rim)
+    return out
+
+
+def deviations(got, ref):
+    """max |got - ref| / max |ref| per array"""
+    return [float(np.abs(np.asarray(g, np.float64) - np.asarray(r, np.float64)).max() / np.abs(r).max()) for g, r in zip(got, ref)]
+
+
+def float32_path(cls_name, seed, attempt=0):
+    """The float32 torch path on the CPU against the float64 references of a draw: a second rounding of the same operation lists.
+    -> {"tangent" | "pullback" | "diag": deviations per array}"""
+    dims, _, f, mask, v, w, h = fuzz_inputs(cls_name, seed, attempt)
+    m32, m64 = make_module(cls_name, dims, f, mask), make_module(cls_name, dims, f, mask, dtype=torch.float64)
+    T = lambda arrs: [torch.tensor(a) for a in arrs]
+    return dict(tangent=deviations([t.numpy() for t in m32.tangent(*T(v))], tangent64(m64, v)),
+                pullback=deviations([t.numpy() for t in m32.pullback(*T(w))], pullback64(m64, w)),
+                diag=deviations([t.numpy() for t in m32.diag(*T(h))], diag_ref64(m64, h)))
+
+
+ATTEMPTS = 8
+
+
+def target_share(cls_name):
+    """The share of tol_of that the second rounding may use for a draw to have a target: a third -- except for the two rock-physics
+    maps, whose dLambda = dk - 2/3 dmu loses a factor of about 3.5 to cancellation for ANY input, so that every float32 evaluation of
+    it sits at 3e-7 ... 6e-7 of the maximum (module docstring, profiles/r19_param_tangent.txt): a third of 1e-6 is out of float32's
+    reach there, and the share is two thirds.  The bound that the kernels are held to is tol_of for every class."""
+    return 2.0 / 3.0 if "Rock" in cls_name else 1.0 / 3.0
+
+
+def has_target(cls_name, seed, attempt=0):
+    """A draw has a target when that second rounding lies within target_share of the bound."""
+    return max(max(d) for d in float32_path(cls_name, seed, attempt).values()) <= target_share(cls_name) * tol_of(cls_name)
+
+
+def settled_inputs(cls_name, seed):
+    """-> (fuzz_inputs of the first attempt that has a target, or None when none of ATTEMPTS has; the attempt).  Only the values are
+    drawn again, never the grid, the mask's kind or the signs; what decides is the torch path on the CPU alone.  A draw without a
+    target is reported (xfail), never passed."""
+    for attempt in range(ATTEMPTS):
+        if has_target(cls_name, seed, attempt):
+            return fuzz_inputs(cls_name, seed, attempt), attempt
+    return None, ATTEMPTS
 
 
 def close(got, ref, tol, what):
