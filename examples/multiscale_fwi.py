@@ -8,12 +8,20 @@ and the last one uses the unfiltered data.
 
     python examples/multiscale_fwi.py --niter 4 [--bands 3]
     python examples/multiscale_fwi.py --gauss-newton --niter 2 [--inner 3]
+    python examples/multiscale_fwi.py --envelope [--gauss-newton]
 
 --gauss-newton (off by default; without it every printed line is what it was): every stage runs --niter truncated Gauss-Newton steps in
 the Lame parameters instead of L-BFGS-B -- the band's own parameter file serves the conditioned misfit, its exact gradient
 (fwi_ops.backward(exact_adjoint=True)) and the Gauss-Newton product J^T C^T Z C J v of the windowed / band-passed data
 (fwi_ops.gauss_newton(exact=True)); the diagonal pseudo-Hessian, calibrated block by block on the Gauss-Newton curvature, is damping and
 Jacobi preconditioner of the inner conjugate gradients, as in examples/gauss_newton_fwi.py.
+
+--envelope (off by default; without it every printed line is what it was): a first stage on the envelope misfit (parameter key
+"if_envelope_misfit": the squared instantaneous amplitudes of the unfiltered gathers are compared instead of the gathers) before the band
+stages -- the stage for data whose low band is noise, where the first low-pass stage has nothing to work with.  The misfit is printed
+after every iteration of that stage.  With --gauss-newton the stage runs as truncated Gauss-Newton steps on the envelope misfit's own
+Gauss-Newton product J^T C^T D^T Z D C J v.  Whether the stage helps depends on the starting model: on this example's 2 % anomalies the
+waveform misfit does not cycle-skip, and the stage is a demonstration of the plumbing, not of a rescue.
 """
 import argparse
 import os
@@ -31,6 +39,11 @@ from sepfwi.obj_wrapper import PyTorchObjective, minimize_lbfgsb  # noqa: E402
 
 FILTER_TABLE = [[0.0, 0.0, 2.0, 2.5], [0.0, 0.0, 2.0, 3.5], [0.0, 0.0, 2.0, 4.5], [0.0, 0.0, 2.0, 5.5], [0.0, 0.0, 2.0, 6.5],
                 [0.0, 0.0, 2.0, 7.5]]    # Main-001-...py:46-51
+ENVELOPE = "envelope"                    # in the place of a band: the stage on the envelope misfit (--envelope)
+
+
+def stage_name(band):
+    return "envelope misfit" if band == ENVELOPE else ("low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies")
 
 
 def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping=0.05, rtol=0.1, say=None):
@@ -73,10 +86,10 @@ def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping
     return m, f_start, f, taken
 
 
-def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3):
+def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False):
     """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage.
     gauss_newton: every stage is `niter` truncated Gauss-Newton steps (at most `inner` conjugate-gradient iterations each) on the stage's
-    own parameter file instead of L-BFGS-B (gauss_newton_stage)."""
+    own parameter file instead of L-BFGS-B (gauss_newton_stage).  envelope: a first stage on the envelope misfit, band = ENVELOPE in the log."""
     dev = torch.device(device)
     nx, nz, dx, dz, dt, nt, f0, nPml = 201, 101, 20.0, 20.0, 0.002, 1501, 10.0, 32
     vp = np.ones((nz, nx), np.float32) * 4000.0
@@ -101,7 +114,10 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
 
     def para_for(tag, band):
         fn = os.path.join(work, "para_%s.json" % tag)
-        ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band)
+        if band == ENVELOPE:
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_envelope_misfit=True)
+        else:
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band)
         return fn
 
     pad = lambda m: torch.tensor(ft.padding_numpy_array(m, nPml, nPad), dtype=torch.float32, device=dev)
@@ -109,6 +125,8 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
 
     log = []
     bands = FILTER_TABLE[len(FILTER_TABLE) - n_bands:] + [None]      # the widest n_bands rows: a 10 Hz Ricker has little below 4 Hz
+    if envelope:
+        bands = [ENVELOPE] + bands
     if gauss_newton:
         lame = lambda c: [((pad(c[0]) ** 2 - 2.0 * pad(c[1]) ** 2) * pad(c[2]) / 1e6).contiguous(), (pad(c[1]) ** 2 * pad(c[2]) / 1e6).contiguous(), pad(c[2])]
         m, mask = lame(cur), torch.tensor(Mask, device=dev)
@@ -117,7 +135,7 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
             log.append((band, f_start, f_end))
             if verbose:
                 print("stage %d, %s: conditioned misfit %.4e -> %.4e in %d Gauss-Newton steps" %
-                      (k, "low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies", f_start, f_end, taken), flush=True)
+                      (k, stage_name(band), f_start, f_end, taken), flush=True)
         inner_ = (slice(nPml, nPml + nz), slice(nPml, nPml + nx))
         lam, mu, den = [t[inner_].double().cpu().numpy() for t in m]
         cur = [np.sqrt((lam + 2.0 * mu) * 1e6 / den).astype(np.float32), np.sqrt(mu * 1e6 / den).astype(np.float32), den.astype(np.float32)]
@@ -129,13 +147,15 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
         obj = PyTorchObjective(fwi, lambda: fwi(Shot_ids, ngpu=1))
         fun, jac = obj.fun, obj.jac
         f_start = fun(obj.x0)
-        res = minimize_lbfgsb(fun, obj.x0, jac, bounds=obj.bounds, maxiter=niter, maxcor=5, ftol=1e-12, gtol=1e-16, maxfun=1500, maxls=6)
+        history = []      # the envelope stage prints its misfit after every iteration (the value of the iterate: no further evaluation)
+        each = (lambda x: (history.append(fun(x)), print("  iteration %d: envelope misfit %.4e" % (len(history), history[-1]), flush=True))) if (band == ENVELOPE and verbose) else None
+        res = minimize_lbfgsb(fun, obj.x0, jac, bounds=obj.bounds, callback=each, maxiter=niter, maxcor=5, ftol=1e-12, gtol=1e-16, maxfun=1500, maxls=6)
         n = nz * nx
         cur = [res.x[i * n:(i + 1) * n].reshape(nz, nx).astype(np.float32) for i in range(3)]
         log.append((band, float(f_start), float(res.fun)))
         if verbose:
             print("stage %d, %s: misfit %.4e -> %.4e in %d iterations (%d evaluations)" %
-                  (k, "low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies", f_start, res.fun, res.nit, res.nfev), flush=True)
+                  (k, stage_name(band), f_start, res.fun, res.nit, res.nfev), flush=True)
     if verbose:
         print("recovered Vp anomaly peak %.1f m/s (true 80), Vs %.1f (true %.1f), density %.1f kg/m^3 (true 40)" %
               ((cur[0] - 4000.0)[42:58, 42:58].max(), (cur[1] - 4000.0 / 1.732)[42:58, 92:108].min(), -80.0 / 1.732,
@@ -150,5 +170,6 @@ if __name__ == "__main__":
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--gauss-newton", action="store_true", help="truncated Gauss-Newton steps on every band's conditioned misfit instead of L-BFGS-B (--niter: steps per band)")
     ap.add_argument("--inner", type=int, default=3, help="with --gauss-newton: conjugate-gradient iterations per step (cap)")
+    ap.add_argument("--envelope", action="store_true", help="a first stage on the envelope misfit (parameter key if_envelope_misfit) before the band stages; prints the misfit per iteration")
     a = ap.parse_args()
-    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner)
+    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope)

@@ -84,6 +84,19 @@ int sepfwi_device_count(void);
  *                weight come from Shot_{vx,vz,ett}{id}.bin, sepfwi_set_observed_component or calc_id 3; a component with weight 0
  *                is never read.  misfit_w_vx / misfit_w_vz > 0 with "obs_pack_fname", and any weights other than (1, 0, 0) with a
  *                live conditioning key, are refused (SEPFWI_EINVAL).  Absent or (1, 0, 0): bit for bit the axial-strain misfit.
+ *                "if_envelope_misfit": true (an extension that no reference run pins) -- the envelope misfit, for data whose low
+ *                frequencies are missing and whose waveform misfit cycle-skips.  With o = C obs, s = C syn (C as under
+ *                sepfwi_condition below), H the discrete Hilbert transform (zero-pad to 2 nSteps, real FFT, bin k times -i for
+ *                0 < k < nSteps and times 0 for k = 0 and k = nSteps, inverse FFT, crop: H^T = -H exactly) and the SQUARED envelope
+ *                e(x) = x^2 + (H x)^2:
+ *                  misfit = 0.5 sum_shots |rho|^2,  rho = Z (e(o) - e(s)),  Z the zeroing of time sample 0;
+ *                  adjoint source = -d misfit / d syn = C^T D^T rho,  D^T rho = 2 [ s rho - H((H s) rho) ].
+ *                A polynomial in the data: no division, no floor, every derivative exact.  ARITHMETIC: e, rho and the adjoint
+ *                source are float32 and scale with the second and third power of the data; nothing rescales them -- the survey's
+ *                "weights" / "src_weight" (with if_win) are the user's handle on the amplitudes.  A live conditioning key: it
+ *                composes with if_win and filter; with "conditioning": "reference" it is parsed and ignored like the other four.
+ *                Refused (SEPFWI_EINVAL): together with if_cross_misfit, with if_src_update, or with weights other than (1, 0, 0).
+ *                Absent or false: every launch, allocation and bit as before.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.
@@ -166,6 +179,11 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
  *                       the data, and the same sentence holds for the conditioned misfit: hv = J^T C^T Z C J v, with C = B Wn (per-channel
  *                       windows with weights, or the end taper; then the zero-phase band-pass: sepfwi_condition below) and Z the zeroing of
  *                       time sample 0 that the conditioned residual applies.  d_* stay the raw gathers.
+ *                       Under if_envelope_misfit the misfit is a non-linear least-squares problem in the squared envelope, and hv is its
+ *                       Gauss-Newton product hv = J^T C^T D^T Z D C J v with D = 2 [diag(s) + diag(H s) H] the derivative of the squared
+ *                       envelope at s = C of the BACKGROUND gather (one more sampler launch per time step records it, only under the key):
+ *                       symmetric, non-negative, the full Hessian where the residual vanishes; the second-order term of the envelope map is
+ *                       left out.  d_* stay the raw gathers, bit for bit those of the file without the key.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, perturbation, stf or para_fname; a bad shot list; the product
  * (hv_* set) under if_cross_misfit (a misfit that is not quadratic in the data) or if_src_update (a matching filter that depends on the
  * synthetics) -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
@@ -202,6 +220,9 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
  *   the gradient mode returns the exact gradient on Omega of the conditioned misfit 1/2 |Z (C obs - C syn)|^2 and that value in *misfit,
  *   as a misfit call on the same file reports it;
  *   the w mode is untouched: g = J^T w with w in raw data space -- a caller composes C and C^T through sepfwi_condition.
+ * Envelope misfit (if_envelope_misfit; D, H, e as under sepfwi_cufd and sepfwi_born): the product is g = P J^T C^T D^T Z D C J P v
+ *   (v^T g = |Z D C J P v|^2); the gradient mode returns the exact gradient on Omega of 1/2 |Z (e(C obs) - e(C syn))|^2 and that value in
+ *   *misfit; the w mode is untouched and stays in raw data space (sepfwi_data_misfit / sepfwi_data_gn give the operators to compose).
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
  * shot list; if_cross_misfit or if_src_update in any mode; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
  * gradient of the source time function is returned by sepfwi_adjoint_exact_src (below), not here.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
@@ -247,6 +268,25 @@ int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float 
    (if_cross_misfit and if_src_update select a misfit, not C).  Creates the session as sepfwi_set_observed does; touches no observed
    data, misfit or statistics; synchronous. */
 int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream);
+
+/*
+ * The misfit of the parameter file as operators in data space, without any wave propagation: for users of the w mode of
+ * sepfwi_adjoint_exact, who compose their own passes.  All gathers are RAW axial-strain gathers laid out like sepfwi_born's d_ett
+ * ([nrec_i][nSteps] shot after shot in the order of shot_ids), host or device; inputs are never changed.  Both run the code that a gradient
+ * call or a product of the session runs between its two transpositions.  They create the session as sepfwi_condition does, touch no
+ * observed data, misfit or statistics, and are synchronous.
+ *   sepfwi_data_misfit   *misfit = the file's misfit of (obs, syn), halved as sepfwi_cufd reports it; adj (may be NULL) = the raw-space
+ *       adjoint source a = -d misfit / d syn, what the backward pass injects:  C^T Z (C obs - C syn) for the L2 misfit (C = 1 without a
+ *       conditioning key),  the adjoint source of the normalised cross-correlation under if_cross_misfit,  C^T D^T Z (e(C obs) - e(C syn))
+ *       under if_envelope_misfit.  SEPFWI_EINVAL under if_src_update and under weights other than (1, 0, 0).
+ *   sepfwi_data_gn       out = the Gauss-Newton operator of the misfit at syn applied to d:  C^T Z C d for the L2 misfit (syn is not
+ *       read),  C^T D^T Z D C d under if_envelope_misfit, D at C syn.  Symmetric and non-negative.  SEPFWI_EINVAL under if_cross_misfit,
+ *       if_src_update and under weights other than (1, 0, 0).
+ */
+int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int gpu_id, int group_size, const int *shot_ids,
+                       const char *para_fname, void *hip_stream);
+int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids, const char *para_fname,
+                   void *hip_stream);
 
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);

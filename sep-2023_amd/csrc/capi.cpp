@@ -196,6 +196,27 @@ int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, con
     });
 }
 
+int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int gpu_id, int group_size, const int *shot_ids,
+                       const char *para_fname, void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        if (!misfit) throw std::invalid_argument("data_misfit: misfit must not be NULL");
+        if (group_size > 0 && (!obs || !syn)) throw std::invalid_argument("data_misfit: obs and syn must not be NULL");
+        get_session(para_fname, gpu_id)->data_misfit(misfit, adj, obs, syn, group_size, shot_ids, (hipStream_t)hip_stream);
+    });
+}
+
+int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids, const char *para_fname,
+                   void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        if (group_size > 0 && (!out || !syn || !d)) throw std::invalid_argument("data_gn: out, syn and d must not be NULL");
+        get_session(para_fname, gpu_id)->data_gn(out, syn, d, group_size, shot_ids, (hipStream_t)hip_stream);
+    });
+}
+
 void sepfwi_invalidate_observed(void) {
     try { invalidate_observed_all(); } catch (...) {}
 }

@@ -133,11 +133,12 @@ __global__ void k_l2_residual(int nt, int nrec, const float *__restrict__ obs, c
 }
 
 // the same residual for observed data syn - d (the Gauss-Newton product, d = C J v): r = -d, first sample zeroed.  No misfit.
-__global__ void k_scattered_residual(int nt, int nrec, const float *__restrict__ d, float *__restrict__ res) {
+// (sign = -1; sepfwi_data_gn hands out +Z d: sign = 1.  A product with -1 is the negation, bit for bit.)
+__global__ void k_scattered_residual(int nt, int nrec, const float *__restrict__ d, float *__restrict__ res, float sign) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
     if (it >= nt || r >= nrec) return;
     const size_t i = (size_t)r * nt + it;
-    res[i] = it == 0 ? 0.0f : -d[i];
+    res[i] = it == 0 ? 0.0f : sign * d[i];
 }
 
 // cuda_spectrum_update (utilities.cu:905-977), first half: one block per frequency bin sums conj(C_r) O_r and |C_r|^2 over the
@@ -185,6 +186,73 @@ __global__ void k_apply_coef(int nf, int nrec, hipfftComplex *__restrict__ spec,
     v.y = y;
 }
 
+// ---- envelope misfit (parameter key if_envelope_misfit; no counterpart in the reference) ------------------------------------------
+// Spectrum multiplier of the discrete Hilbert transform on the nf = nt + 1 bins of a trace zero-padded to 2 nt: bin k times -i for
+// 0 < k < nt, times 0 for k = 0 and the Nyquist bin k = nt.  With pad and crop around it the transform is exactly antisymmetric.
+__global__ void k_hilbert_mult(int nf, int nrec, hipfftComplex *__restrict__ spec) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (k >= nf || r >= nrec) return;
+    hipfftComplex &c = spec[(size_t)r * nf + k];
+    const bool keep = k > 0 && k < nf - 1;
+    const float x = c.x, y = c.y;
+    c.x = keep ? y : 0.0f;  // (x + i y) (-i) = y - i x
+    c.y = keep ? -x : 0.0f;
+}
+
+// One block per trace: rho = Z (e(o) - e(s)) with e(x) = x^2 + (H x)^2 and Z the zeroing of sample 0; the trace's sum rho^2 in double
+// (the reduction of k_l2_residual) into sum[r] -- no atomics, so that the order of the additions is fixed (k_env_sum adds the traces);
+// a = s rho and b = (H s) rho, the two halves of D^T rho = 2 [a - H b].  float32 throughout: rho is of the data's second power, a and b
+// of its third, and nothing rescales them.
+__global__ void k_env_residual(int nt, const float *__restrict__ o, const float *__restrict__ ho, const float *__restrict__ s,
+                               const float *__restrict__ hs, float *__restrict__ a, float *__restrict__ b, double *__restrict__ sum) {
+    const int r = blockIdx.x;
+    double acc = 0.0;
+    for (int it = threadIdx.x; it < nt; it += blockDim.x) {
+        const size_t i = (size_t)r * nt + it;
+        const float sv = s[i], hv = hs[i];
+        const float rho = it == 0 ? 0.0f : (o[i] * o[i] + ho[i] * ho[i]) - (sv * sv + hv * hv);
+        a[i] = sv * rho;
+        b[i] = hv * rho;
+        acc += (double)rho * (double)rho;
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) sum[r] = part[0] + part[1] + part[2] + part[3];
+}
+
+// *acc += sum_r sum[r], one block, a fixed order (the call's stream serialises the shots: no atomic is needed)
+__global__ void k_env_sum(int nrec, const double *__restrict__ sum, double *__restrict__ acc) {
+    double s = 0.0;
+    for (int r = threadIdx.x; r < nrec; r += blockDim.x) s += sum[r];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    __shared__ double part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *acc += part[0] + part[1] + part[2] + part[3];
+}
+
+// The linearised twin at the background s for a data perturbation d: rho' = Z 2 (s d + (H s)(H d)) = Z D d, then a = s rho', b = (H s) rho'
+__global__ void k_env_linear(int nt, int nrec, const float *__restrict__ s, const float *__restrict__ hs, const float *__restrict__ d,
+                             const float *__restrict__ hd, float *__restrict__ a, float *__restrict__ b) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (it >= nt || r >= nrec) return;
+    const size_t i = (size_t)r * nt + it;
+    const float sv = s[i], hv = hs[i];
+    const float rho = it == 0 ? 0.0f : 2.0f * (sv * d[i] + hv * hd[i]);
+    a[i] = sv * rho;
+    b[i] = hv * rho;
+}
+
+// a <- sign 2 (a - hb): D^T rho from its two halves (hb = H b), in place
+__global__ void k_env_combine(int nt, int nrec, float *__restrict__ a, const float *__restrict__ hb, float sign) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (it >= nt || r >= nrec) return;
+    const size_t i = (size_t)r * nt + it;
+    a[i] = sign * (2.0f * (a[i] - hb[i]));
+}
+
 // hipFFT is only needed by a parameter file with a band-pass or a source-signature update, so libsepfwi.so does not link it:
 // the five entry points are resolved with dlopen when the first plan is made, and a ROCm image without hipFFT still loads and
 // runs the propagator (a parameter file that asks for a filter then fails with a message that names the library).
@@ -200,7 +268,7 @@ const FftApi &fft() {
         void *h = nullptr;
         for (const char *name : {"libhipfft.so.0", "libhipfft.so", "/opt/rocm/lib/libhipfft.so.0"})
             if ((h = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
-        if (!h) throw std::runtime_error("data conditioning (filter / if_src_update) needs hipFFT, and libhipfft.so could not be opened");
+        if (!h) throw std::runtime_error("data conditioning (filter / if_src_update / if_envelope_misfit) needs hipFFT, and libhipfft.so could not be opened");
         FftApi a{};
         auto sym = [&](const char *n) {
             void *p = dlsym(h, n);
@@ -336,9 +404,9 @@ void Conditioner::l2_residual(hipStream_t st, const float *obs, const float *syn
     hipLaunchKernelGGL(k_l2_residual, dim3(nrec), dim3(256), 0, st, nt_, nrec, obs, syn, res, acc);
 }
 
-void Conditioner::scattered_residual(hipStream_t st, const float *d, float *res, int nrec) {
+void Conditioner::scattered_residual(hipStream_t st, const float *d, float *res, int nrec, float sign) {
     if (nrec <= 0) return;
-    hipLaunchKernelGGL(k_scattered_residual, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, d, res);
+    hipLaunchKernelGGL(k_scattered_residual, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, d, res, sign);
 }
 
 void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights,
@@ -352,6 +420,55 @@ void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *
     hipLaunchKernelGGL(k_cross_misfit, dim3(1), dim3(256), 0, st, nrec, n_os, n_oo, n_ss, weights, src_weight, acc);
     hipLaunchKernelGGL(k_cross_adjoint, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, n_oo, n_ss, n_os, obs, syn, res, weights,
                        src_weight);
+}
+
+void Conditioner::ensure_envelope_buffers() {
+    if (env_.get()) return;
+    env_ = DevBuf<float>(&bytes_, 3 * (size_t)nt_ * cap_);
+    env_sum_ = DevBuf<double>(&bytes_, (size_t)cap_);
+}
+
+// H of the header: pad, R2C, the multiplier, C2R, crop with 1 / (2 nt) -- the padding, plans and buffers of bandpass
+void Conditioner::hilbert(hipStream_t st, const float *in, float *out, int nrec) {
+    if (nrec <= 0) return;
+    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    const int npad = 2 * nt_, nf = nt_ + 1;
+    Plans &pl = plans_for(nrec, st);
+    hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
+    hipLaunchKernelGGL(k_embed, dim3((npad + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, in, pad_.get());
+    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
+    hipLaunchKernelGGL(k_hilbert_mult, dim3((nf + 255) / 256, nrec), dim3(256), 0, st, nf, nrec, (hipfftComplex *)spec_.get());
+    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
+    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, out, pad_.get(), 1.0f / (float)npad);
+}
+
+void Conditioner::envelope_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc) {
+    if (nrec <= 0) return;
+    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    ensure_envelope_buffers();
+    const size_t g = (size_t)nt_ * cap_;
+    float *ho = env_.get(), *hs = ho + g, *b = ho + 2 * g;
+    const dim3 grid((nt_ + 255) / 256, nrec), blk(256);
+    hilbert(st, obs, ho, nrec);
+    hilbert(st, syn, hs, nrec);
+    hipLaunchKernelGGL(k_env_residual, dim3(nrec), blk, 0, st, nt_, obs, (const float *)ho, syn, (const float *)hs, res, b, env_sum_.get());
+    hipLaunchKernelGGL(k_env_sum, dim3(1), blk, 0, st, nrec, (const double *)env_sum_.get(), acc);
+    hilbert(st, b, b, nrec);
+    hipLaunchKernelGGL(k_env_combine, grid, blk, 0, st, nt_, nrec, res, (const float *)b, 1.0f);
+}
+
+void Conditioner::envelope_scattered(hipStream_t st, const float *syn, const float *d, float *res, int nrec, float sign) {
+    if (nrec <= 0) return;
+    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    ensure_envelope_buffers();
+    const size_t g = (size_t)nt_ * cap_;
+    float *hd = env_.get(), *hs = hd + g, *b = hd + 2 * g;
+    const dim3 grid((nt_ + 255) / 256, nrec), blk(256);
+    hilbert(st, d, hd, nrec);
+    hilbert(st, syn, hs, nrec);
+    hipLaunchKernelGGL(k_env_linear, grid, blk, 0, st, nt_, nrec, syn, (const float *)hs, d, (const float *)hd, res, b);
+    hilbert(st, b, b, nrec);
+    hipLaunchKernelGGL(k_env_combine, grid, blk, 0, st, nt_, nrec, res, (const float *)b, sign);
 }
 
 }  // namespace sepfwi

@@ -1,5 +1,5 @@
 // conditioning.hpp -- data-conditioning chain of the misfit (conditioning.hip): windows, band-pass (hipFFT), normalised
-// cross-correlation misfit.  All gathers are [rec][nt] float32 device arrays.
+// cross-correlation misfit, envelope misfit.  All gathers are [rec][nt] float32 device arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +25,21 @@ class Conditioner {
     // gpuMinus + cuda_cal_objective (utilities.cu:154-205): res = obs - syn (first sample zeroed), *acc += sum res^2
     void l2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc);
     // what l2_residual leaves in res for observed data syn - d: res = -d (first sample zeroed); no misfit is accumulated
-    void scattered_residual(hipStream_t st, const float *d, float *res, int nrec);
+    // (sign = 1: +Z d, what sepfwi_data_gn hands out)
+    void scattered_residual(hipStream_t st, const float *d, float *res, int nrec, float sign = -1.0f);
+    // ---- envelope misfit (parameter key if_envelope_misfit) ----
+    // The discrete Hilbert transform H of every trace: zero-pad to 2 nt, R2C, bin k times -i for 0 < k < nt and times 0 for k = 0 and
+    // k = nt, C2R, 1 / (2 nt), crop -- the padding, plans and buffers of bandpass.  H^T = -H exactly.  in == out is allowed.
+    void hilbert(hipStream_t st, const float *in, float *out, int nrec);
+    // Squared envelope e(x) = x^2 + (H x)^2, pointwise.  rho = Z (e(obs) - e(syn)), Z the zeroing of sample 0; *acc += sum rho^2 (double,
+    // a fixed order of additions: no atomics); res = D^T rho = 2 [syn rho - H((H syn) rho)], which is -d(1/2 |rho|^2)/d syn -- the sign of
+    // l2_residual.  ARITHMETIC: e, rho and res are float32 and scale with the second and third power of the data; nothing rescales
+    // them.  Data whose squares or cubes leave the float32 range must be scaled by the survey's weights / src_weight (if_win).
+    // obs, syn and res must be three different gathers.
+    void envelope_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc);
+    // The linearised twin at the background syn: res = sign D^T Z D d with D = 2 [diag(syn) + diag(H syn) H].  sign = -1: what
+    // envelope_residual leaves for observed data whose envelope is e(syn) - D d (the Gauss-Newton product); no misfit.
+    void envelope_scattered(hipStream_t st, const float *syn, const float *d, float *res, int nrec, float sign = -1.0f);
     // cuda_find_normfact x3 + cuda_normal_misfit + cuda_normal_adjoint_source (utilities.cu:1010-1111):
     // *acc += -2 sum_r <obs,syn>_r / (|obs|_r |syn|_r) w_r ; res = the adjoint source.  weights may be null (all ones).
     void cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight,
@@ -42,6 +56,9 @@ class Conditioner {
     // once; the session calls it up-front when the parameter file sets if_src_update, so that no shot pays an allocation inside
     // its time loop
     void ensure_source_buffers(hipStream_t st);
+    // three [cap][nt] scratch gathers (H obs or H d, H syn, (H syn) rho) and the per-trace sums of the envelope misfit, allocated on
+    // first use: a session whose file does not set the key never holds them
+    void ensure_envelope_buffers();
     long long device_bytes() const { return bytes_; }  // what the buffers below hold
 
   private:
@@ -54,6 +71,8 @@ class Conditioner {
     DevBuf<float> pad_, norm_, pad2_;
     DevBuf<float2> spec_;          // hipfftComplex [cap][nt + 1]
     DevBuf<float2> spec2_, coef_;  // second padded gather / spectrum and the nt + 1 matching-filter coefficients (source update)
+    DevBuf<float> env_;            // envelope misfit: 3 x [cap][nt]
+    DevBuf<double> env_sum_;       // ... and sum rho^2 per trace
     std::map<int, Plans> plans_;  // by number of traces
 };
 

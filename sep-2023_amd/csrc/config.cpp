@@ -42,6 +42,7 @@ Params parse_params(const std::string &text) {
     if (j.has("if_win")) p.if_win = j.at("if_win").as_bool("if_win");
     if (j.has("if_src_update")) p.if_src_update = j.at("if_src_update").as_bool("if_src_update");
     if (j.has("if_cross_misfit")) p.if_cross_misfit = j.at("if_cross_misfit").as_bool("if_cross_misfit");
+    if (j.has("if_envelope_misfit")) p.if_envelope_misfit = j.at("if_envelope_misfit").as_bool("if_envelope_misfit");
     p.has_filter = j.has("filter");
     if (p.has_filter) {
         const JsonValue &f = j.at("filter");
@@ -55,7 +56,7 @@ Params parse_params(const std::string &text) {
         const std::string c = j.at("conditioning").as_string("conditioning");
         if (c == "reference") {
             p.conditioning_reference = true;
-            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = false;
+            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = false;
         } else if (c != "live") {
             throw std::runtime_error("parameter JSON: conditioning must be \"live\" or \"reference\"");
         }
@@ -99,9 +100,14 @@ Params parse_params(const std::string &text) {
         if (!p.obs_pack_fname.empty())
             throw std::invalid_argument(std::string("parameter file: ") + key + " > 0 together with obs_pack_fname is not supported (the packed file holds axial strain only)");
     }
-    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update)) {
+    // the envelope misfit is neither a correlation of the traces nor linear in them: the trace norms of the cross-correlation misfit and the
+    // matching filter of the source update have no meaning on envelopes
+    if (p.if_envelope_misfit && (p.if_cross_misfit || p.if_src_update))
+        throw std::invalid_argument(std::string("parameter file: if_envelope_misfit together with ") + (p.if_cross_misfit ? "if_cross_misfit" : "if_src_update") +
+                                    " is not supported");
+    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit)) {
         const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
-        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : "if_src_update"));
+        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : "if_envelope_misfit")));
         throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
                                     " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
     }

@@ -20,7 +20,11 @@ struct Params {
     int obs_cache_mb = 0;
     // data-conditioning keys (dormant in the reference's driver, libCUFD.cu:353-457; live here, csrc/conditioning.hip)
     bool if_win = false, if_src_update = false, if_cross_misfit = false, has_filter = false;
-    // optional key "conditioning": "live" (default) -- the four keys above switch their stage on; "reference" -- they are parsed
+    // optional key "if_envelope_misfit" (no counterpart in the reference; conditioning.hip): the misfit compares the squared envelopes
+    // e(x) = x^2 + (H x)^2 of the conditioned gathers instead of the gathers.  A live conditioning key like the four above; refused
+    // together with if_cross_misfit or if_src_update.
+    bool if_envelope_misfit = false;
+    // optional key "conditioning": "live" (default) -- the five keys above switch their stage on; "reference" -- they are parsed
     // and validated like the reference does and then IGNORED like its driver does (every call site commented out,
     // libCUFD.cu:353-457): results are those of a file without them.  if_win_key keeps what the file said, because the survey
     // file must carry win_start / win_end whenever if_win is set, used or not (Src_Rec.cu:144-174).

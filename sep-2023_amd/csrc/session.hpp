@@ -69,6 +69,10 @@ class Session {
     // The conditioning operator of the parameter file (sepfwi_condition): C, or C^T, in place on gathers laid out like born()'s d_ett,
     // host or device; the identity when no conditioning key is live
     void condition(float *data, bool transpose, int group_size, const int *shot_ids, hipStream_t ext_stream);
+    // The misfit of the parameter file in data space (sepfwi_data_misfit, sepfwi_data_gn; session_data.cpp): raw gathers laid out like
+    // born()'s d_ett, host or device.  Neither the observed store nor the misfit, misfit parts or statistics of the last call are touched.
+    void data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int group_size, const int *shot_ids, hipStream_t ext_stream);
+    void data_gn(float *out, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
@@ -178,12 +182,17 @@ class Session {
     void forward_init(const ShotCtx &x);
     void forward_step(const Call &c, const ShotCtx &x, int it, bool inl);
     void record_column(const ShotCtx &x, int column);
+    void record_background(const ShotCtx &x, int column);  // session_born.cpp (if_envelope_misfit)
     const GaugeDev &gauge_taps(const ShotCtx &x);  // a gauge shot's taps on the device, built on first use (das_gauge.hpp)
     void residual(const ShotCtx &x);
     GeoResShot geo_res_shot(const ShotCtx &x) const;  // joint misfit: what the residual kernel needs of one shot (geophone.hpp)
     void residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int nb);
     void residual_conditioned(const Call &c, const ShotCtx &x);
     void adjoint_source_conditioned(const Call &c, const ShotCtx &x);  // -C^T Z C (J v) from the shot's scattered gather (if_win / filter)
+    // what the two run between their transpositions, on the scratch gathers (session_run.cpp); the data-space entry points run them too
+    void misfit_chain(hipStream_t st, const float *d_obs, int shot_id, int nrec, double *acc);
+    void gn_chain(hipStream_t st, int shot_id, int nrec, float sign);
+    void ensure_data_scratch();  // xpose3_ / data_acc_
     // what a forward pass leaves behind, by kind of call
     void after_forward(Call &c, const ShotCtx &x);
     void export_gathers(const Call &c, const ShotCtx &x);
@@ -278,6 +287,11 @@ class Session {
     // Born modelling (born.hpp), allocated on the first Born call: [5 scattered fields | their 8 C-PML memories | 5 perturbed-media
     // arrays] and the staging of a perturbation that does not live on this device
     DevBuf<float> born_stage_, born_;
+    // envelope misfit (parameter key if_envelope_misfit): the time-major BACKGROUND axial-strain gather of the shot a Born call is
+    // running, allocated by the first product under the key; a third [rec][it] scratch gather and a sum of their own for that product
+    // and the data-space entry points, allocated on first use
+    DevBuf<float> born_bg_, xpose3_;
+    DevBuf<double> data_acc_;
     DevBuf<float> ph_out_, ph_set_[kPhMaxSets];
     DevBuf<float> inj_val_{&device_bytes_};
     // gauge channels (parameter key das_gauge_length): per shot its taps (device copies, built on first use); the batched schedule's

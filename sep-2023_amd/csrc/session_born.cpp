@@ -10,7 +10,9 @@
 //                       residual kernel would put w_c (obs_c - syn_c), and Session::backward runs as in a gradient call: persistent loop
 //                       or two-launch step, injection plans, the background's saved boundary frames.  Under a parameter file with if_win
 //                       / filter (C = band-pass . window) the buffer gets -C^T Z C dsyn instead (Session::adjoint_source_conditioned):
-//                       the product is J^T C^T Z C J v; the gathers handed out stay the raw ones
+//                       the product is J^T C^T Z C J v; the gathers handed out stay the raw ones.  Under if_envelope_misfit the product is
+//                       J^T C^T D^T Z D C J v, D the derivative of the squared envelope at C of the BACKGROUND gather: one more sampler
+//                       launch per step records that gather (record_background), only under the key
 // and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
 // state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
 // exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
@@ -32,6 +34,18 @@
 #include "session.hpp"
 
 namespace sepfwi {
+
+// Axial-strain column `column` of the shot's BACKGROUND state into born_bg_ (time-major like the lane's own gathers): record_column
+// with the one component and the one target.
+void Session::record_background(const ShotCtx &x, int column) {
+    float *col = born_bg_.get() + (size_t)column * x.nrec;
+    if (x.gauge)
+        launch_record_gauge(x.st, x.fld, x.nrec, x.rec, x.gauge->start.get(), x.gauge->cell.get(), x.gauge->field.get(), x.gauge->w.get(), nullptr, nullptr, nullptr,
+                            col, 8);
+    else
+        launch_record(x.st, g_, x.fld, x.nrec, x.rec, nullptr, nullptr, nullptr, col, 8, x.sens);
+    cs_.launches++;
+}
 
 void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float *hv_Mu, float *hv_Den, const float *Lambda, const float *Mu,
                    const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int group_size, const int *shot_ids,
@@ -86,6 +100,10 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     // which scattered gathers the call needs: the requested ones, and for the product the components with a weight
     int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
     if (want_hv) comps |= active_comps();
+    // envelope misfit: the product linearises the envelope at the BACKGROUND gather, which the samplers record into a buffer of its own
+    const bool bg = want_hv && par_.if_envelope_misfit;
+    if (bg && !born_bg_) born_bg_ = dev<float>(data_len_);
+    if (bg) ensure_data_scratch();
     float *out[4] = {nullptr, d_vx, d_vz, d_ett};
     size_t out_off = 0;
     const BornArgs args{state_, dstate, media_, dmedia, pc_.a_z, n};
@@ -99,6 +117,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         HIP_OK(hipEventRecord(ev_[0], st));
         forward_init(x);  // background state, column 0 of the gathers
         HIP_OK(hipMemsetAsync(dstate, 0, kStateArrays * n * sizeof(float), st));
+        if (bg && x.nrec > 0) HIP_OK(hipMemsetAsync(born_bg_.get(), 0, (size_t)x.nrec * sizeof(float), st));  // column 0, as forward_init
         for (int it = 0; it <= nSteps - 2; it++) {
             float *frame_t = want_hv ? x.frame + (size_t)it * 5 * (size_t)g_.frame_len : nullptr;
             const float amp = c.src_scale * x.stf_s[it] * par_.dt;
@@ -107,6 +126,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
             launch_born_velocity(st, g_, c.opt, args);
             cs_.launches += 2;
             if (x.nrec > 0 && comps) record_column(xd, it + 1);
+            if (bg && x.nrec > 0) record_background(x, it + 1);
         }
         HIP_OK(hipEventRecord(ev_[1], st));
         cs_.fwd_steps += (long long)(nSteps - 1);

@@ -70,7 +70,9 @@ class PyTorchObjective(object):
         """The Gauss-Newton Hessian at x times p, flat float64 in and out -- what `optimize.minimize(fun, x0, jac=, hessp=,
         method="trust-ncg")` (or "Newton-CG") takes; an extension without a counterpart in the reference.  p is scattered over the
         module's parameters in named_parameters() order (a field of the module that is not a parameter gets None), the product is
-        obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient."""
+        obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient.
+        Under a parameter file with if_envelope_misfit the product is the envelope misfit's own Gauss-Newton Hessian (include/sepfwi.h,
+        sepfwi_born): nothing changes here."""
         if self.shot_ids is None:
             raise ValueError("hessp needs the shots of the Gauss-Newton product: PyTorchObjective(obj, loss, shot_ids=...)")
         if not hasattr(self.obj, "gauss_newton"):
@@ -195,7 +197,9 @@ def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2
     """Matrix-free (preconditioned) conjugate gradients for the Gauss-Newton step:  (H + damping D) p = -g.
 
     hessvec   callable: a tuple of tensors v -> the tuple H v (fwi_ops.gauss_newton at a fixed model; an extension without a
-              counterpart in the reference)
+              counterpart in the reference).  The parameter file decides which misfit's product that is: J^T W J, J^T C^T Z C J under
+              if_win / filter, J^T C^T D^T Z D C J under if_envelope_misfit -- symmetric and non-negative with exact=True in every case,
+              which is all this solver needs
     grad      the gradient g, a tuple of tensors shaped like v
     diag      optional tuple of non-negative tensors, e.g. the diagonal pseudo-Hessian: D in the damping term AND the Jacobi
               preconditioner M = D (zero entries -- outside the illuminated region -- are floored at 1e-12 max D); None: D = M = I

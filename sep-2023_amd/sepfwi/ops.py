@@ -235,7 +235,8 @@ class _FwiOps:
         the misfit on Omega (0 outside) and gStf ZEROS unless `source_gradient=True`: then gStf is the exact d misfit / d Stf
         (sepfwi_adjoint_exact_src), in Stf's shape with zero rows for shots not in Shot_ids.  One GPU, not together with
         pseudo_hessian.  Windowed / band-passed data (if_win, filter) are served: misfit and gradients are those of the conditioned
-        misfit 1/2 |Z (C obs - C syn)|^2; if_cross_misfit and if_src_update are refused (SepFwiError).
+        misfit 1/2 |Z (C obs - C syn)|^2, under if_envelope_misfit of the envelope misfit 1/2 |Z (e(C obs) - e(C syn))|^2;
+        if_cross_misfit and if_src_update are refused (SepFwiError).
         Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
         shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
         and ranks like the gradients; under torch.distributed through ONE more all-reduce, of the fused [hL | hM | hD] buffer).
@@ -375,8 +376,10 @@ class _FwiOps:
         """The Gauss-Newton Hessian-vector product J^T W J v, summed over Shot_ids -> (hvLambda, hvMu, hvDen), each (nz_pad, nx_pad):
         the gradient `backward` would return at the model if the observed data were syn - J v (W: the misfit weights of the parameter
         file).  Under a parameter file whose live conditioning keys are among if_win and filter the same holds for the conditioned
-        misfit: the product is J^T C^T Z C J v (C: `condition`; Z: time sample 0 zeroed).  Refused (SepFwiError, SEPFWI_EINVAL) under
-        if_cross_misfit or if_src_update.  One GPU only, as born.
+        misfit: the product is J^T C^T Z C J v (C: `condition`; Z: time sample 0 zeroed).  Under if_envelope_misfit it is the
+        Gauss-Newton product of the envelope misfit, J^T C^T D^T Z D C J v with D the derivative of the squared envelope at C of the
+        background gather (`data_gn` is its data-space part).  Refused (SepFwiError, SEPFWI_EINVAL) under if_cross_misfit or
+        if_src_update.  One GPU only, as born.
         exact=True (include/sepfwi.h, sepfwi_adjoint_exact): J^T is the exact transpose of J instead of the reference's backward pass,
         and the product is P J^T W J P v with P the restriction to Omega (the physical interior without its first row and column; v is
         read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding (windowed / band-passed data:
@@ -489,6 +492,53 @@ class _FwiOps:
             torch.cuda.synchronize(out.device)
         _native.check(_native.lib().sepfwi_condition(_ptr(out), int(bool(transpose)), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
                                                      str(para_fname).encode(), stream))
+        return out
+
+    # -- the misfit of a parameter file in data space (sepfwi_data_misfit, sepfwi_data_gn) ----------------
+    def _data_args(self, tensors, names, Shot_ids, para_fname, gpu_id):
+        """float32 contiguous gathers of one size on one device, checked against the survey -> (tensors, ids, dev, stream)"""
+        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
+        dev = self.device_override if self.device_override is not None else int(gpu_id)
+        ts = [_f32c(t, n) for t, n in zip(tensors, names)]
+        if any(t.numel() != ts[0].numel() or t.device != ts[0].device for t in ts):
+            raise ValueError("%s must hold the same number of elements on one device" % " and ".join(names))
+        dims = _para_dims(para_fname)
+        if dims is not None:
+            want = int(sum(_nrec_per_shot(para_fname, ids))) * dims[2]
+            if ts[0].numel() != want:
+                raise ValueError("%s must hold (nrec_i, nSteps = %d) float32 per shot of Shot_ids, %d elements in all, got %d"
+                                 % (names[0], dims[2], want, ts[0].numel()))
+        stream = None
+        if ts[0].is_cuda and ts[0].device.index == dev:
+            cs = torch.cuda.current_stream(ts[0].device).cuda_stream
+            stream = C.c_void_p(cs) if cs else None
+        elif ts[0].is_cuda:
+            torch.cuda.synchronize(ts[0].device)
+        return ts, ids, dev, stream
+
+    def data_misfit(self, obs, syn, Shot_ids, para_fname, gpu_id=0):
+        """The parameter file's misfit of RAW axial-strain gathers, with no wave propagation (include/sepfwi.h, sepfwi_data_misfit):
+        obs, syn are float32 tensors holding the gathers [nrec_i][nSteps] shot after shot in the order of Shot_ids (any shape with that
+        many elements, CPU or HIP).  -> (misfit, adj): the misfit as `forward` reports it (a Python float) and the raw-space adjoint source
+        a = -d misfit / d syn in syn's shape and device -- C^T Z (C obs - C syn) under an L2 file, the cross-correlation's under
+        if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under if_envelope_misfit.  if_src_update is refused.  With `born_adjoint` a caller
+        composes a gradient pass: g = -J^T a."""
+        (obs, syn), ids, dev, stream = self._data_args((obs, syn), ("obs", "syn"), Shot_ids, para_fname, gpu_id)
+        adj = torch.empty_like(syn)
+        mis = C.c_float(0.0)
+        _native.check(_native.lib().sepfwi_data_misfit(C.cast(C.byref(mis), C.c_void_p), _ptr(adj), _ptr(obs), _ptr(syn), dev, int(ids.size),
+                                                       C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
+        return float(mis.value), adj
+
+    def data_gn(self, syn, d, Shot_ids, para_fname, gpu_id=0):
+        """The Gauss-Newton operator of the parameter file's misfit in data space, at syn, applied to d (sepfwi_data_gn): C^T Z C d under
+        an L2 file, C^T D^T Z D C d under if_envelope_misfit (D the derivative of the squared envelope at C syn).  Layout as data_misfit;
+        -> a new tensor like d.  Symmetric and non-negative; refused under if_cross_misfit and if_src_update.  `born`, this and
+        `born_adjoint` compose the product J^T (.) J v."""
+        (syn, d), ids, dev, stream = self._data_args((syn, d), ("syn", "d"), Shot_ids, para_fname, gpu_id)
+        out = torch.empty_like(d)
+        _native.check(_native.lib().sepfwi_data_gn(_ptr(out), _ptr(syn), _ptr(d), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
+                                                   str(para_fname).encode(), stream))
         return out
 
     # -- extras --------------------------------------------------------------------------------

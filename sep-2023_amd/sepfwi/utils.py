@@ -35,7 +35,8 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
-            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None):
+            das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None,
+            if_envelope_misfit=False):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
@@ -44,7 +45,10 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
     das_gauge_length (extension) [m]: every channel records the mean axial strain over this gauge along the fibre, a whole multiple
     of the grid spacing along it (csrc/das_gauge.hpp); written only when given.
     misfit_weights (extension): dict with keys among "ett" / "vx" / "vz" -- the weights of the axial-strain, vx and vz residuals in
-    misfit and adjoint source (csrc/geophone.hpp; defaults ett 1, vx 0, vz 0).  Only the keys given are written."""
+    misfit and adjoint source (csrc/geophone.hpp; defaults ett 1, vx 0, vz 0).  Only the keys given are written.
+    if_envelope_misfit (extension): the misfit compares the squared envelopes of the conditioned gathers instead of the gathers
+    (include/sepfwi.h, sepfwi_cufd); refused by the library together with if_cross_misfit, if_src_update or misfit_weights.  Written
+    only when set."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
     if if_win:
@@ -58,6 +62,8 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
     os.makedirs(data_dir_name, exist_ok=True)
     if if_cross_misfit:
         para["if_cross_misfit"] = True
+    if if_envelope_misfit:
+        para["if_envelope_misfit"] = True
     if das_fiber != "horizontal":
         if das_fiber != "vertical":
             raise ValueError("das_fiber must be 'horizontal' or 'vertical'")
