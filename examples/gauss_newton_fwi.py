@@ -10,11 +10,16 @@ Gauss-Newton curvature -- as damping matrix and preconditioner, and takes a back
     python examples/gauss_newton_fwi.py --device cuda
     python examples/gauss_newton_fwi.py --device cuda --outer 2 --inner 3 --nsteps 600 --shot-stride 3
     python examples/gauss_newton_fwi.py --device cuda --param vp_vs_den --exact-adjoint
+    python examples/gauss_newton_fwi.py --device cuda --param vp_vs_den --exact-adjoint --tikhonov 1e3 --tv 10
 
 With --param vp_vs_den the gradient is module(ids).backward(), D is module.diag(pseudo-Hessian) and the product is module.gauss_newton
 (P^T J^T J P v with P the tangent of the parameter chain); calibration, CG and backtracking are the same.
 
-Prints the CG residual of every inner iteration and the misfit of every outer one."""
+With --tikhonov BETA, --tv GAMMA or --prior ALPHA (--param vp_vs_den; all 0 by default, the run without them) the objective gains the model
+term R of sepfwi.regularize.Regularizer on the three fields -- first-order Tikhonov, smoothed total variation, damping towards the starting
+model: the gradient carries its gradient, the CG operator its exact Hessian-vector product, the backtracking its value.
+
+Prints the CG residual of every inner iteration and the misfit of every outer one (with a model term: the data misfit and R separately)."""
 import argparse
 import os
 import sys
@@ -44,7 +49,13 @@ def main():
                     help="the CG operator uses the exact discrete adjoint (fwi_ops.gauss_newton(exact=True)): symmetric and non-negative on Omega")
     ap.add_argument("--param", default="lame", choices=["lame", "vp_vs_den"],
                     help="the unknowns: (Lambda, Mu, Den) on the padded grid, or the FWI module's (Vp, Vs, Den) on the physical grid")
+    ap.add_argument("--tikhonov", type=float, default=0.0, metavar="BETA", help="weight of the first-order Tikhonov term of the three fields (--param vp_vs_den)")
+    ap.add_argument("--tv", type=float, default=0.0, metavar="GAMMA", help="weight of the smoothed total-variation term (--param vp_vs_den)")
+    ap.add_argument("--prior", type=float, default=0.0, metavar="ALPHA", help="weight of the damping towards the starting model (--param vp_vs_den)")
     a = ap.parse_args()
+    regularised = a.tikhonov > 0 or a.tv > 0 or a.prior > 0
+    if regularised and a.param != "vp_vs_den":
+        ap.error("--tikhonov / --tv / --prior act on the fields of a module: use --param vp_vs_den")
     dev = torch.device(a.device)
 
     # ---- model and survey: Main-001-...py:20-73
@@ -85,6 +96,11 @@ def main():
         fwi = FWI(*[torch.tensor(t, dtype=torch.float32, device=dev, requires_grad=True) for t in (vp0, vs0, rho0)], Stf, opt, Mask=Mask)
         m = [p.detach().clone() for p in fwi.parameters()]
         W = [torch.ones_like(t) for t in m]      # the module applies the Mask itself (P and P^T carry it)
+        reg = None
+        if regularised:      # R at the module's fields, prior = the starting model, scale = its mean, the grid of the parameter file
+            from sepfwi.regularize import Regularizer
+            reg = Regularizer(fwi, alpha=a.prior, beta=a.tikhonov, gamma=a.tv)
+        parts = {}           # the last evaluation's data misfit and R
 
         def at(mm):      # the module at the fields mm -> its padded (Lambda, Mu, Den)
             with torch.no_grad():
@@ -98,12 +114,28 @@ def main():
             loss = fwi(ids, ngpu=1)
             loss.backward()
             H = fwi_ops.forward(*at(mm), Stf, 0, ids, para_fname, pseudo_hessian=1)[1:4]
-            return float(loss.detach()), [p.grad.detach().clone() for p in fwi.parameters()], list(fwi.diag(*[t.to(dev) for t in H]))
-        misfit = lambda mm: float(fwi_ops.forward(*at(mm), Stf, 0, ids, para_fname)[0])
-        product = lambda mm, v: fwi.gauss_newton(tuple(v), ids, exact=a.exact_adjoint)      # (the module sits at mm: gradient() left it there)
+            f, g = float(loss.detach()), [p.grad.detach().clone() for p in fwi.parameters()]
+            D = list(fwi.diag(*[t.to(dev) for t in H]))
+            if reg is not None:
+                r, rg = reg.value_and_grad()
+                parts.update(data=f, reg=float(r))
+                f, g = f + float(r), [x + y for x, y in zip(g, rg)]
+            return f, g, D
+
+        def misfit(mm):
+            f = float(fwi_ops.forward(*at(mm), Stf, 0, ids, para_fname)[0])
+            if reg is not None:
+                parts.update(data=f, reg=float(reg.value_and_grad()[0]))
+                f += parts["reg"]
+            return f
+
+        def product(mm, v):      # (the module sits at mm: gradient() left it there)
+            hv = fwi.gauss_newton(tuple(v), ids, exact=a.exact_adjoint)
+            return hv if reg is None else [x + y for x, y in zip(hv, reg.hvp(tuple(v)))]
     else:
         m = lame(vp0, vs0, rho0)
         W = [Mask, Mask, Mask]
+        parts = {}
 
         def gradient(mm):
             out = fwi_ops.backward(*mm, Stf, 1, ids, para_fname, pseudo_hessian=1)
@@ -115,8 +147,8 @@ def main():
         f, g, D = gradient(m)
         if f0_ is None:
             f0_ = f
-            print("iterate 0: misfit %.6e" % f, flush=True)
-        hv = lambda v: product(m, v)
+            print("iterate 0: misfit %.6e%s" % (f, "   (data %.6e, regulariser %.6e)" % (parts["data"], parts["reg"]) if parts else ""), flush=True)
+        hv = (lambda v: product(m, v)) if not regularised else (lambda v: fwi.gauss_newton(tuple(v), ids, exact=a.exact_adjoint))      # D is calibrated on the data term
         # The pseudo-Hessian leaves out the receiver side, and its three blocks are not on one scale (it is a preconditioner, not a
         # Hessian): calibrate each block on the Gauss-Newton curvature along its own preconditioned gradient z_k = -g_k / D_k,
         # D_k <- D_k (z_k^T H z_k) / (z_k^T D_k z_k) -- three products per outer iteration
@@ -127,6 +159,13 @@ def main():
             s_j = dot(z, hv(z)) / dot([z[j]], [D[j] * z[j]])
             D[j] = D[j] * max(s_j, 0.0)
             print("  outer %d: pseudo-Hessian block %s calibrated by %.3e" % (k + 1, names[j], s_j), flush=True)
+        if a.param == "vp_vs_den" and reg is not None:
+            # the model term's Hessian does not vanish where the illumination does: without its diagonal in D the Jacobi-preconditioned
+            # system is arbitrarily ill-conditioned there.  Its Gershgorin bound per field (W = 1, phi >= eps) is a constant.
+            for j, n in enumerate(names):
+                s_n = reg.scale[n]
+                D[j] = D[j] + (reg.alpha[n] / s_n ** 2 + (reg.beta[n] + reg.gamma[n] / reg.eps) * (2.0 / (s_n * reg.dx) ** 2 + 2.0 / (s_n * reg.dz) ** 2))
+        hv = lambda v: product(m, v)
         lam = a.damping
         p, hist = gauss_newton_cg(hv, g, damping=lam, diag=D, maxiter=a.inner, rtol=a.rtol,
                                   callback=lambda i, r: print("  outer %d cg %d: relative residual %.4e" % (k + 1, i, r), flush=True))
@@ -140,7 +179,8 @@ def main():
             print("iterate %d: no decrease along the Gauss-Newton step, stopping" % (k + 1))
             break
         m = [(mi + step * pi).contiguous() for mi, pi in zip(m, p)]
-        print("iterate %d: misfit %.6e   (step %.3g, %d cg iterations)" % (k + 1, f_new, step, len(hist) - 1), flush=True)
+        print("iterate %d: misfit %.6e   (step %.3g, %d cg iterations)%s" % (
+            k + 1, f_new, step, len(hist) - 1, "   (data %.6e, regulariser %.6e)" % (parts["data"], parts["reg"]) if parts else ""), flush=True)
         f = f_new
     print("done: misfit %.4e -> %.4e" % (f0_, f))
     if a.param == "vp_vs_den":

@@ -399,6 +399,37 @@ int sepfwi_param_diag(int kind, int nz, int nx, int nPml, int nPad, const float 
                       const float *hMu, const float *hDen, float *hA, float *hB, float *hC, void *hip_stream);
 
 /*
+ * Model regularisation (an extension without a counterpart in the reference, which has data terms only): damping towards a prior,
+ * first-order Tikhonov and Charbonnier-smoothed isotropic total variation of up to three (nz, nx) fields, its gradient and its EXACT
+ * Hessian-vector product (symmetric and non-negative: R is convex; not the lagged-diffusivity approximation).  For every field k
+ * with p[k] != NULL (a NULL field is skipped), with s = scale[k] and W the cell weights (NULL: 1):
+ *     q  = (p - p0) / s
+ *     gx(i,j) = (p(i,j+1) - p(i,j)) / (s dx)    0 in the last column         gz(i,j) = (p(i+1,j) - p(i,j)) / (s dz)    0 in the last row
+ *     n2 = gx^2 + gz^2,   phi = sqrt(n2 + eps^2)
+ *     R  = sum over the cells of  W [ alpha q^2 / 2  +  beta n2 / 2  +  gamma (phi - eps) ]         (a constant field costs exactly 0)
+ * and the total is the sum over the fields.  Gradient, in gather form, with c = W (beta + gamma / phi), fx = c gx, fz = c gz:
+ *     g(i,j)  = W alpha (p - p0) / s^2 - fx(i,j) / (s dx) - fz(i,j) / (s dz) + fx(i,j-1) / (s dx) + fz(i-1,j) / (s dz)
+ * Product, with qx, qz the same differences of v and d = gx qx + gz qz:  tx = W (beta qx + gamma (qx / phi - gx d / phi^3)), tz likewise,
+ *     Hv(i,j) = W alpha v / s^2 - tx(i,j) / (s dx) - tz(i,j) / (s dz) + tx(i,j-1) / (s dx) + tz(i-1,j) / (s dz)
+ * (a predecessor that does not exist contributes nothing).  One launch over the three fields, one thread per cell, no atomics;
+ * float32 with a fixed operation list (csrc/regularizer.hip); the cell energies are summed in double, block partials first and
+ * then one block in a fixed order, so the same input gives the same bits.  With gamma[k] == 0 nothing of field k depends on eps.
+ *   p, p0, v, g, hv     triples of (nz, nx) float32 row-major arrays, W one such array: host or device memory (of one device), in any
+ *                       mix; host arrays are staged and the call then synchronises the stream, device arrays are only enqueued.
+ *                       p0[k] may be NULL when alpha[k] == 0.
+ *   value               the total R as a double, host or device pointer; value, g or entries of g may be NULL (not computed).
+ *   v[k] == NULL        (product) field k is not perturbed: hv[k], when given, is zeros.  There is no coupling between fields.
+ * SEPFWI_EINVAL before any device is touched: nz or nx < 1; a negative or non-finite alpha / beta / gamma of a given field;
+ * scale, dx or dz <= 0; eps <= 0 while some gamma > 0; alpha[k] > 0 without p0[k]; v[k] for a field without p[k]; all fields NULL.
+ */
+int sepfwi_regularizer(int nz, int nx, float dx, float dz, const float *const p[3], const float *const p0[3], const float *W,
+                       const float alpha[3], const float beta[3], const float gamma[3], const float scale[3], float eps,
+                       double *value, float *const g[3], void *hip_stream);
+int sepfwi_regularizer_hvp(int nz, int nx, float dx, float dz, const float *const p[3], const float *const p0[3], const float *W,
+                           const float alpha[3], const float beta[3], const float gamma[3], const float scale[3], float eps,
+                           const float *const v[3], float *const hv[3], void *hip_stream);
+
+/*
  * Test hook: wavefield `which` (0..4: vz, vx, szz, sxx, sxz; 5..9: their adjoint twins; 10..14: the scattered fields of the last
  * sepfwi_born call) of forward lane `lane` as the last sepfwi_cufd* / sepfwi_born call on (para_fname, gpu_id) left it, dense (nz - nPad, nx) row-major float32, host or device pointer.
  * After a gradient call the forward fields are the reverse-time RECONSTRUCTION run back to time step 0, i.e. they must

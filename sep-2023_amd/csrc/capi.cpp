@@ -8,6 +8,7 @@
 
 #include "kernels.hpp"
 #include "param_maps.hpp"
+#include "regularizer.hpp"
 #include "session.hpp"
 
 using namespace sepfwi;
@@ -82,6 +83,7 @@ int sepfwi_cufd(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_D
 
 void sepfwi_release_all(void) {
     try { release_all_sessions(); } catch (...) {}
+    release_regularizer_workspaces();
 }
 
 int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const float *ett, int nrec, int nSteps) {
@@ -359,6 +361,25 @@ int sepfwi_param_diag(int kind, int nz, int nx, int nPml, int nPad, const float 
         launch_param_diag((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, hA,
                           hB, hC);
         if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
+    });
+}
+
+int sepfwi_regularizer(int nz, int nx, float dx, float dz, const float *const p[3], const float *const p0[3], const float *W,
+                       const float alpha[3], const float beta[3], const float gamma[3], const float scale[3], float eps, double *value,
+                       float *const g[3], void *hip_stream) {
+    return guarded([&] {
+        const RegModel m{nz, nx, dx, dz, p, p0, W, alpha, beta, gamma, scale, eps};
+        run_regularizer(m, nullptr, value, g, (hipStream_t)hip_stream);
+    });
+}
+
+int sepfwi_regularizer_hvp(int nz, int nx, float dx, float dz, const float *const p[3], const float *const p0[3], const float *W,
+                           const float alpha[3], const float beta[3], const float gamma[3], const float scale[3], float eps,
+                           const float *const v[3], float *const hv[3], void *hip_stream) {
+    return guarded([&] {
+        if (!v || !hv) throw std::invalid_argument("regularizer: the product needs v and hv");
+        const RegModel m{nz, nx, dx, dz, p, p0, W, alpha, beta, gamma, scale, eps};
+        run_regularizer(m, v, nullptr, hv, (hipStream_t)hip_stream);
     });
 }
 

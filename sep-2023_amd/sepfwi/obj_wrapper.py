@@ -10,11 +10,12 @@ from scipy import optimize
 
 
 class PyTorchObjective(object):
-    def __init__(self, obj, loss, shot_ids=None, exact=True):
+    def __init__(self, obj, loss, shot_ids=None, exact=True, regularizer=None):
         self.obj = obj      # nn.Module holding the parameters (and .Bounds)
         self.loss = loss    # callable -> scalar tensor
         self.shot_ids = shot_ids   # for hessp: the shots of obj.gauss_newton (None: no hessp)
         self.exact = exact         # ... and its adjoint (True: symmetric and non-negative, what trust-ncg / Newton-CG assume)
+        self.regularizer = regularizer   # for hessp: a sepfwi.regularize.Regularizer whose term `loss` adds (None: no model term)
         params = OrderedDict(obj.named_parameters())
         self.param_shapes = OrderedDict((n, tuple(p.shape)) for n, p in params.items())
         self.x0 = np.concatenate([p.data.cpu().numpy().ravel() for p in params.values()]).astype(np.float64)
@@ -72,7 +73,8 @@ class PyTorchObjective(object):
         module's parameters in named_parameters() order (a field of the module that is not a parameter gets None), the product is
         obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient.
         Under a parameter file with if_envelope_misfit the product is the envelope misfit's own Gauss-Newton Hessian (include/sepfwi.h,
-        sepfwi_born): nothing changes here."""
+        sepfwi_born): nothing changes here.  With `regularizer=` its exact Hessian-vector product regularizer.hvp(v) is added, field by
+        field, to the Gauss-Newton product: the Hessian of the model term that `loss` carries as `+ regularizer()`."""
         if self.shot_ids is None:
             raise ValueError("hessp needs the shots of the Gauss-Newton product: PyTorchObjective(obj, loss, shot_ids=...)")
         if not hasattr(self.obj, "gauss_newton"):
@@ -85,6 +87,8 @@ class PyTorchObjective(object):
         chunks = self.unpack_parameters(np.asarray(p, dtype=np.float64))
         v = tuple(chunks[n].to(device=params[n].device, dtype=params[n].dtype) if n in params else None for n in fields)
         hv = self.obj.gauss_newton(v, self.shot_ids, exact=self.exact)
+        if self.regularizer is not None:
+            hv = tuple(h if r is None else h + r.to(h.dtype) for h, r in zip(hv, self.regularizer.hvp(v)))
         return np.concatenate([hv[fields.index(n)].detach().cpu().numpy().ravel() for n in params]).astype(np.float64)
 
 
@@ -199,7 +203,7 @@ def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2
     hessvec   callable: a tuple of tensors v -> the tuple H v (fwi_ops.gauss_newton at a fixed model; an extension without a
               counterpart in the reference).  The parameter file decides which misfit's product that is: J^T W J, J^T C^T Z C J under
               if_win / filter, J^T C^T D^T Z D C J under if_envelope_misfit -- symmetric and non-negative with exact=True in every case,
-              which is all this solver needs
+              which is all this solver needs.  A model term composes as `lambda v: add(H(v), reg.hvp(v))` (sepfwi.regularize)
     grad      the gradient g, a tuple of tensors shaped like v
     diag      optional tuple of non-negative tensors, e.g. the diagonal pseudo-Hessian: D in the damping term AND the Jacobi
               preconditioner M = D (zero entries -- outside the illuminated region -- are floored at 1e-12 max D); None: D = M = I

@@ -1,0 +1,316 @@
+"""The model regulariser on the GPU (-m gpu): k_reg_value_grad, k_reg_sum and k_reg_hvp of csrc/regularizer.hip through
+sepfwi_regularizer / sepfwi_regularizer_hvp, sepfwi.regularize.Regularizer on HIP tensors, PyTorchObjective(regularizer=) and
+gauss_newton_cg over the composed operator.
+
+Reference: the definition in float64 torch (tests/regularizer_ref.py), inputs born float32.  Bounds:
+  value     VALUE_ROUNDINGS 2^-24 relative.  Every cell's energy is a sum of non-negative float32 terms and the cells are summed in double,
+            so the relative error of the total is that of the worst term's path through the operation list of csrc/regularizer.hip, in
+            roundings (a square doubles what its argument carries, a square root halves it, a sum of non-negative terms keeps the
+            larger): gx = (p1 - p) rx with rx rounded once: 3; gx^2: 7; n2 = gx^2 + gz^2: 8; n2 + e2: 9; sqrt: 5.5; + eps: 6.5;
+            n2 / (.): 15.5; gamma x: 16.5; + the Tikhonov term (9): 17.5; + the damping term ((a2/2) (d d): 5): 18.5; W x: 19.5 -> 20.
+  gradient, product   each array's largest deviation as a share of the reference array's largest entry within 4 x the same figure of
+            the float32 torch path on the CPU for the same case (tests/test_regularizer_reference.py prints it).
+Every comparison prints its figure before it asserts (profiles/r22_model_regularisation.txt holds those measured on the MI355X).
+
+Every test fails on the parent: the entry points and sepfwi.regularize are missing."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import problems as P
+import regularizer_ref as R
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+VALUE_ROUNDINGS = 20
+U = 2.0 ** -24
+
+
+def _ids(x):
+    return "x".join(map(str, x)) if isinstance(x, tuple) else str(x)
+
+
+def _lib(hip_ops):
+    from sepfwi import _native
+    return _native.lib()
+
+
+def _dot(a, b):
+    return float(sum((np.asarray(x, np.float64) * np.asarray(y, np.float64)).sum() for x, y in zip(a, b) if x is not None))
+
+
+def _same(a, b):
+    return all((x is None and y is None) or np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+@pytest.mark.parametrize("grid", R.GRIDS, ids=_ids)
+def test_kernels_against_the_float64_definition(hip_ops, grid, name):
+    L = _lib(hip_ops)
+    c = R.case(grid, name)
+    val, g, hv = R.reference(c)
+    fval, fg, fhv = R.fallback(c, torch.float32)
+    rc, dval, dg = R.c_value_grad(L, c, on_device=True)
+    assert rc == 0, L.sepfwi_last_error()
+    rc, dhv = R.c_hvp(L, c, on_device=True)
+    assert rc == 0, L.sepfwi_last_error()
+    dv = abs(dval - val) / val if val else abs(dval)
+    print("regulariser %s %s: value %.10e, off by %.2e of it (bound %.2e)" % (_ids(grid), name, dval, dv, VALUE_ROUNDINGS * U))
+    assert dv <= VALUE_ROUNDINGS * U
+    for k in range(3):
+        if c["p"][k] is None:
+            assert dg[k] is None and dhv[k] is None
+            continue
+        for what, got, ref, fb in (("gradient", dg[k], g[k], fg[k]), ("product", dhv[k], hv[k], fhv[k])):
+            dev, yard = R.share(got, ref), R.share(fb, ref)
+            print("regulariser %s %s field %d %s: %.2e of the largest entry (float32 torch path %.2e, bound 4 x)" % (_ids(grid), name, k, what, dev, yard))
+            assert got.dtype == np.float32 and dev <= 4.0 * yard
+    # host pointers give the bits of device pointers; a second call, and a device double for the value, the same value bits
+    rc, hval, hg = R.c_value_grad(L, c, on_device=False)
+    assert rc == 0 and hval == dval and _same(hg, dg)
+    rc, hhv = R.c_hvp(L, c, on_device=False)
+    assert rc == 0 and _same(hhv, dhv)
+    rc, dval2, dg2 = R.c_value_grad(L, c, on_device=True, device_value=True)
+    assert rc == 0 and dval2 == dval and _same(dg2, dg)
+
+
+def test_value_or_gradient_alone_and_mixed_pointers(hip_ops):
+    """value or g may be NULL; single arrays may live on the host while the others are HIP tensors"""
+    import ctypes as C
+    L = _lib(hip_ops)
+    c = R.case((33, 129), "full")
+    rc, val, g = R.c_value_grad(L, c, on_device=True)
+    keep, args = R._model_args(c, True)
+    only = C.c_double(-1.0)
+    assert L.sepfwi_regularizer(*args, C.cast(C.byref(only), C.c_void_p), None, None) == 0 and only.value == val
+    out = R._empty(c["p"], True)
+    assert L.sepfwi_regularizer(*args, None, R._triple(out), None) == 0 and _same(R._host(out), g)
+    mixed = [out[0], np.empty_like(g[1]), None]                  # g[1] to the host, g[2] not wanted
+    args[4] = R._triple([keep["p"][0], c["p"][1], keep["p"][2]])                     # p[1] from the host
+    assert L.sepfwi_regularizer(*args, None, R._triple(mixed), None) == 0, L.sepfwi_last_error()
+    assert _same(R._host(mixed[:2]), g[:2])
+
+
+def test_identities_that_need_no_tolerance(hip_ops):
+    L = _lib(hip_ops)
+    grid = (33, 129)
+    c = R.case(grid, "full")
+    # a constant field with alpha = 0: value and gradient exactly 0
+    flat = dict(c, p=[np.full(grid, np.float32(b)) for b in R.BASE], alpha=R.F32(0, 0, 0), beta=R.F32(0.4, 0.9, 0.3), gamma=R.F32(0.2, 0.6, 1.1))
+    rc, val, g = R.c_value_grad(L, flat, on_device=True)
+    assert rc == 0 and val == 0.0 and all(not a.any() for a in g)
+    # a cell whose own weight and both predecessors' weights are 0: g and Hv exactly 0 there
+    W = c["W"]
+    dead = W == 0
+    dead[:, 1:] &= W[:, :-1] == 0
+    dead[1:, :] &= W[:-1, :] == 0
+    assert dead.sum() >= 10
+    rc, val, g = R.c_value_grad(L, c, on_device=True)
+    rc2, hv = R.c_hvp(L, c, on_device=True)
+    assert rc == 0 and rc2 == 0
+    for k in range(3):
+        assert not g[k][dead].any() and not hv[k][dead].any() and g[k][~dead].any() and hv[k][~dead].any()
+    # Hv with v = 0 is exactly 0
+    rc, hv0 = R.c_hvp(L, dict(c, v=[np.zeros(grid, np.float32)] * 3), on_device=True)
+    assert rc == 0 and all(not a.any() for a in hv0)
+    # gamma = 0: nothing depends on eps, bit for bit (eps <= 0 included: it is not even checked then)
+    outs = []
+    for eps in (R.EPS, R.EPS_LARGE, np.float32(0.0)):
+        q = R.case(grid, "beta_only")
+        q.update(alpha=c["alpha"], eps=eps)
+        rc, val, g = R.c_value_grad(L, q, on_device=True)
+        rc2, hv = R.c_hvp(L, q, on_device=True)
+        assert rc == 0 and rc2 == 0
+        outs.append((val, g, hv))
+    assert all(o[0] == outs[0][0] and _same(o[1], outs[0][1]) and _same(o[2], outs[0][2]) for o in outs[1:])
+
+
+@pytest.mark.parametrize("name", ["full", "eps_small", "no_weight"])
+@pytest.mark.parametrize("grid", [(5, 63), (130, 257)], ids=_ids)
+def test_product_is_symmetric_and_non_negative(hip_ops, grid, name):
+    """<u, Hv> = <v, Hu> and v^T H v >= 0, formed in float64 from the float32 outputs, to the product's own bound: each H x within
+    4 x the float32 torch path's share of its largest entry, so an inner product with y within that times |y|_1 max |H x|."""
+    L = _lib(hip_ops)
+    c = R.case(grid, name)
+    cu = dict(c, v=R.fields(grid, seed=1)[2])
+    u, v = cu["v"], c["v"]
+    tol = lambda q: [4.0 * R.share(fb, ref) * np.abs(ref).max() for fb, ref in zip(R.fallback(q, torch.float32)[2], R.reference(q)[2])]
+    tv, tu = tol(c), tol(cu)
+    (rc, hv), (rc2, hu) = R.c_hvp(L, c, on_device=True), R.c_hvp(L, cu, on_device=True)
+    assert rc == 0 and rc2 == 0
+    l1 = lambda a: float(np.abs(a.astype(np.float64)).sum())
+    uhv, vhu, vhv, uhu = _dot(u, hv), _dot(v, hu), _dot(v, hv), _dot(u, hu)
+    bound = sum(l1(a) * t for a, t in zip(u, tv)) + sum(l1(a) * t for a, t in zip(v, tu))
+    print("regulariser %s %s: <u, Hv> %.10e, <v, Hu> %.10e, difference %.2e (bound %.2e); v^T H v %.6e, u^T H u %.6e" % (
+        _ids(grid), name, uhv, vhu, abs(uhv - vhu), bound, vhv, uhu))
+    assert abs(uhv - vhu) <= bound
+    assert vhv >= -sum(l1(a) * t for a, t in zip(v, tv)) and uhu >= -sum(l1(a) * t for a, t in zip(u, tu))
+    assert vhv > 0 and uhu > 0      # (far from the bound: both are sums of squares)
+
+
+@pytest.mark.parametrize("grid", [(5, 63), (130, 257)], ids=_ids)
+def test_without_total_variation_the_functional_is_quadratic(hip_ops, grid):
+    """gamma = 0: R(p + v) - R(p) - <g, v> - v^T H v / 2 = 0, within the value's bound times R(p + v).  p + v is rounded to float32
+    first and v taken as the difference, which float32 holds exactly."""
+    L = _lib(hip_ops)
+    c = R.case(grid, "full")
+    c.update(gamma=R.F32(0, 0, 0), beta=R.F32(0.4, 0.9, 0.5))
+    pv = [(a + b).astype(np.float32) for a, b in zip(c["p"], c["v"])]
+    v = [a - b for a, b in zip(pv, c["p"])]
+    assert all(np.array_equal(a.astype(np.float64) - b.astype(np.float64), d.astype(np.float64)) for a, b, d in zip(pv, c["p"], v))
+    c["v"] = v
+    rc, r0, g = R.c_value_grad(L, c, on_device=True)
+    rc1, r1, _ = R.c_value_grad(L, dict(c, p=pv), on_device=True)
+    rc2, hv = R.c_hvp(L, c, on_device=True)
+    assert rc == 0 and rc1 == 0 and rc2 == 0
+    rest = r1 - r0 - _dot(g, v) - 0.5 * _dot(v, hv)
+    print("regulariser %s quadratic: R(p + v) %.10e, R(p) %.10e, <g, v> %.10e, v^T H v / 2 %.10e, remainder %.2e (bound %.2e)" % (
+        _ids(grid), r1, r0, _dot(g, v), 0.5 * _dot(v, hv), abs(rest), VALUE_ROUNDINGS * U * r1))
+    assert abs(rest) <= VALUE_ROUNDINGS * U * r1
+
+
+# ---- module level: FWI in Vp / Vs / Den on HIP tensors --------------------------------------------------------------------------------
+_CHILD = r"""
+import sys, types
+stub = types.ModuleType("sepfwi.regularize")
+stub.Regularizer = None
+sys.modules["sepfwi.regularize"] = stub          # the package's import of it finds this: the real module is never loaded
+sys.path[:0] = [%r, %r]
+import numpy as np, torch
+import problems as P
+from sepfwi import modules as M
+pb = P.make_problem(%r)
+f = [torch.tensor(pb["init"][k], device="cuda", requires_grad=True) for k in ("vp", "vs", "rho")]
+fwi = M.FWI(f[0], f[1], f[2], pb["Stf"], pb["opt"])
+f = [getattr(fwi, n) for n in fwi.NAMES]
+fwi(pb["Shot_ids"], ngpu=1).backward()
+assert not hasattr(sys.modules["sepfwi.regularize"], "_RegFunction")
+np.save(%r, np.stack([t.grad.cpu().numpy() for t in f]))
+"""
+
+
+@pytest.fixture(scope="module")
+def prob(hip_ops, tmp_path_factory):
+    from sepfwi import modules as M
+    from sepfwi.regularize import Regularizer
+    work = str(tmp_path_factory.mktemp("regularizer"))
+    pb = P.make_problem(work)                                     # 44 x 60, 240 steps, 2 shots
+    hip_ops.obscalc(*pb["lame_true"], pb["Stf"], 1, pb["Shot_ids"], pb["para_fname"])
+    f = [torch.tensor(pb["init"][k], device="cuda", requires_grad=True) for k in ("vp", "vs", "rho")]
+    fwi = M.FWI(f[0], f[1], f[2], pb["Stf"], pb["opt"])
+    f = [getattr(fwi, n) for n in fwi.NAMES]                      # the module's parameters: the leaves that collect .grad
+    W = torch.ones(44, 60)
+    W[:4] = 0.0
+    prior = [torch.tensor(pb["true"][k]) for k in ("vp", "vs", "rho")]
+    reg = Regularizer(fwi, alpha={"Vp": 2.0, "Den": 5.0}, beta=30.0, gamma={"Vs": 1.0, "Den": 3.0}, eps=1e-3, prior=prior, weight=W)
+
+    def data_grad():
+        fwi.zero_grad()
+        loss = fwi(pb["Shot_ids"], ngpu=1)
+        loss.backward()
+        return float(loss.detach()), [t.grad.detach().clone() for t in f]
+    return dict(pb=pb, fwi=fwi, reg=reg, f=f, work=work, data_grad=data_grad)
+
+
+def test_regularizer_of_a_module_runs_the_kernels(hip_ops, prob):
+    """The Regularizer on HIP float32 tensors is the fused path: value, gradient and product against the float64 definition at the
+    module's fields, with the bounds of the kernel tests (the float32 torch path on the CPU is the yardstick)."""
+    reg, f = prob["reg"], prob["f"]
+    assert (reg.dx, reg.dz) == (10.0, 10.0) and reg._fusable([t.detach() for t in f])
+    val, g = reg.value_and_grad()
+    assert val.dtype == torch.float64 and val.is_cuda and val.dim() == 0 and all(t.is_cuda and t.dtype == torch.float32 for t in g)
+    host = lambda ts: [t.detach().cpu().numpy() for t in ts]
+    v = [(0.01 * a * np.random.default_rng(5).standard_normal(a.shape)).astype(np.float32) for a in host(f)]
+    hv = reg.hvp(tuple(torch.tensor(a) for a in v))             # (CPU tensors: moved to the fields' device)
+    per = lambda d: R.F32(*[d[n] for n in reg.names])
+    c = dict(nz=44, nx=60, dx=np.float32(reg.dx), dz=np.float32(reg.dz), p=host(f), p0=host([reg.prior[n] for n in reg.names]), v=v,
+             W=reg.weight.cpu().numpy(), alpha=per(reg.alpha), beta=per(reg.beta), gamma=per(reg.gamma), scale=per(reg.scale), eps=np.float32(reg.eps))
+    rval, rg, rhv = R.reference(c)
+    fval, fg, fhv = R.fallback(c, torch.float32)
+    dv = abs(float(val) - rval) / rval
+    print("regulariser module: R %.8e, off by %.2e of it (bound %.2e)" % (float(val), dv, VALUE_ROUNDINGS * U))
+    assert rval > 0 and dv <= VALUE_ROUNDINGS * U
+    for what, got, ref, fb in [("gradient", x, y, z) for x, y, z in zip(host(g), rg, fg)] + [("product", x, y, z) for x, y, z in zip(host(hv), rhv, fhv)]:
+        dev, yard = R.share(got, ref), R.share(fb, ref)
+        print("regulariser module: %s %.2e of the largest entry (float32 torch path %.2e, bound 4 x)" % (what, dev, yard))
+        assert dev <= 4.0 * yard
+    part = reg.hvp((None, torch.tensor(v[1]), None))
+    assert part[0] is None and part[2] is None and torch.equal(part[1], hv[1])
+
+
+def test_gradient_of_misfit_plus_regularizer(hip_ops, prob):
+    """.grad of module(ids) + reg() is .grad of module(ids) plus reg.value_and_grad(), to one float32 addition -- bit for bit where two
+    data gradients agree bit for bit, otherwise within 3 x their run-to-run difference."""
+    pb, fwi, reg, f = prob["pb"], prob["fwi"], prob["reg"], prob["f"]
+    m0, g0 = prob["data_grad"]()
+    m1, g1 = prob["data_grad"]()
+    val, gr = reg.value_and_grad()
+    fwi.zero_grad()
+    loss = fwi(pb["Shot_ids"], ngpu=1) + reg()
+    loss.backward()
+    assert loss.shape == (1,) and abs(float(loss) - (m0 + float(val))) <= 4 * U * float(loss)
+    for t, a, b, r in zip(f, g0, g1, gr):
+        want, run = a + r, float((a - b).abs().max())
+        dev = float((t.grad - want).abs().max())
+        print("regulariser module: grad of misfit + R against the sum of the two: %.2e (data gradient run to run %.2e, largest %.2e, of R %.2e)" % (
+            dev, run, float(a.abs().max()), float(r.abs().max())))
+        assert float(r.abs().max()) > 0 and not torch.equal(t.grad, a)       # the term is in the sum
+        assert torch.equal(t.grad, want) if run == 0.0 else dev <= 3.0 * run + U * float(want.abs().max())
+
+
+def test_hessp_with_regularizer_is_the_sum(hip_ops, prob):
+    from sepfwi.obj_wrapper import PyTorchObjective
+    pb, fwi, reg = prob["pb"], prob["fwi"], prob["reg"]
+    loss = lambda: fwi(pb["Shot_ids"], ngpu=1) + reg()
+    with_reg = PyTorchObjective(fwi, loss, shot_ids=pb["Shot_ids"], exact=True, regularizer=reg)
+    without = PyTorchObjective(fwi, loss, shot_ids=pb["Shot_ids"], exact=True)
+    rng = np.random.default_rng(11)
+    x = with_reg.x0
+    p = np.concatenate([0.01 * t.detach().cpu().numpy().ravel() for t in prob["f"]]) * rng.standard_normal(x.size)
+    a, a2, b = without.hessp(x, p), without.hessp(x, p), with_reg.hessp(x, p)
+    v = tuple(torch.tensor(p[k * 2640:(k + 1) * 2640].reshape(44, 60), dtype=torch.float32, device="cuda") for k in range(3))
+    r = np.concatenate([t.cpu().numpy().ravel() for t in reg.hvp(v)]).astype(np.float64)
+    run, dev = np.abs(a - a2).max(), np.abs(b - (a + r)).max()
+    print("regulariser module: hessp with the regulariser against the sum: %.2e (Gauss-Newton run to run %.2e, largest %.2e, of R %.2e)" % (
+        dev, run, np.abs(a).max(), np.abs(r).max()))
+    assert np.abs(r).max() > 0 and dev <= 3.0 * run + U * np.abs(a + r).max()
+
+
+def test_no_regularizer_leaves_the_gradient_bits(hip_ops, prob):
+    """regularizer=None and no reg() in the loss: the gradient of a process that never loaded sepfwi.regularize."""
+    out = os.path.join(prob["work"], "child_grad.npy")
+    code = _CHILD % (os.path.join(ROOT, "sep-2023_amd"), os.path.join(ROOT, "tests"), prob["work"], out)
+    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, stdin=subprocess.DEVNULL)
+    assert res.returncode == 0, res.stderr[-2000:]
+    child = np.load(out)
+    m0, g0 = prob["data_grad"]()
+    m1, g1 = prob["data_grad"]()
+    for k in range(3):
+        here, again = g0[k].cpu().numpy(), g1[k].cpu().numpy()
+        run = np.abs(here - again).max()
+        print("regulariser module: gradient %d against a process without sepfwi.regularize: %.2e (run to run %.2e)" % (k, np.abs(here - child[k]).max(), run))
+        assert np.array_equal(here, child[k]) if run == 0.0 else np.abs(here - child[k]).max() <= 3.0 * run
+
+
+def test_gauss_newton_cg_with_the_composed_operator(hip_ops, prob):
+    """gauss_newton_cg over v -> H_GN v + H_R v with the exact adjoint: every curvature d^T A d the solver meets is positive, so no
+    iteration stops on non-positive curvature, and the residual falls."""
+    from sepfwi.obj_wrapper import gauss_newton_cg
+    pb, fwi, reg = prob["pb"], prob["fwi"], prob["reg"]
+    fwi.zero_grad()
+    (fwi(pb["Shot_ids"], ngpu=1) + reg()).backward()
+    g = [t.grad.detach().clone() for t in prob["f"]]
+    curv = []
+
+    def hessvec(v):
+        hv = [a + b for a, b in zip(fwi.gauss_newton(v, pb["Shot_ids"], exact=True), reg.hvp(v))]
+        curv.append(float(sum((x.double() * y.double()).sum() for x, y in zip(v, hv))))
+        return hv
+    step, hist = gauss_newton_cg(hessvec, g, maxiter=4, rtol=1e-12)
+    print("regulariser module: cg curvatures %s, residuals %s" % (" ".join("%.3e" % x for x in curv), " ".join("%.3e" % x for x in hist)))
+    assert len(curv) == 4 and min(curv) > 0 and len(hist) == 5 and hist[-1] < 1.0
