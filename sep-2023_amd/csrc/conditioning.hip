@@ -199,18 +199,31 @@ __global__ void k_hilbert_mult(int nf, int nrec, hipfftComplex *__restrict__ spe
     c.y = keep ? -x : 0.0f;
 }
 
+// d = o - s: the data residual whose Hilbert transform k_env_residual needs
+__global__ void k_env_diff(int nt, int nrec, const float *__restrict__ o, const float *__restrict__ s, float *__restrict__ d) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (it >= nt || r >= nrec) return;
+    const size_t i = (size_t)r * nt + it;
+    d[i] = o[i] - s[i];
+}
+
 // One block per trace: rho = Z (e(o) - e(s)) with e(x) = x^2 + (H x)^2 and Z the zeroing of sample 0; the trace's sum rho^2 in double
 // (the reduction of k_l2_residual) into sum[r] -- no atomics, so that the order of the additions is fixed (k_env_sum adds the traces);
-// a = s rho and b = (H s) rho, the two halves of D^T rho = 2 [a - H b].  float32 throughout: rho is of the data's second power, a and b
-// of its third, and nothing rescales them.
-__global__ void k_env_residual(int nt, const float *__restrict__ o, const float *__restrict__ ho, const float *__restrict__ s,
+// a = s rho and b = (H s) rho, the two halves of D^T rho = 2 [a - H b].
+// rho is formed from the data residual, never as the difference of the two envelopes: with d = o - s and H linear,
+//     e(o) - e(s) = d (o + s) + (H d) (H d + 2 H s),
+// whose rounding error is a few eps of rho itself.  (e(o) - e(s) taken literally in float32 is off by eps |e(s)|, and where the data
+// nearly fit -- |rho| / |e(s)| is 1e-4 on a channel of seed 0 and 1.6e-7 on a shot of seed 10 of tests/test_gpu_envelope_fuzz.py -- that
+// was 5e-3 of the adjoint source, and all of it.)  float32 throughout: rho is of the data's second power, a and b of its third, and
+// nothing rescales them.
+__global__ void k_env_residual(int nt, const float *__restrict__ o, const float *__restrict__ hd, const float *__restrict__ s,
                                const float *__restrict__ hs, float *__restrict__ a, float *__restrict__ b, double *__restrict__ sum) {
     const int r = blockIdx.x;
     double acc = 0.0;
     for (int it = threadIdx.x; it < nt; it += blockDim.x) {
         const size_t i = (size_t)r * nt + it;
-        const float sv = s[i], hv = hs[i];
-        const float rho = it == 0 ? 0.0f : (o[i] * o[i] + ho[i] * ho[i]) - (sv * sv + hv * hv);
+        const float ov = o[i], sv = s[i], hv = hs[i], hdv = hd[i];
+        const float rho = it == 0 ? 0.0f : (ov - sv) * (ov + sv) + hdv * (hdv + 2.0f * hv);
         a[i] = sv * rho;
         b[i] = hv * rho;
         acc += (double)rho * (double)rho;
@@ -447,11 +460,12 @@ void Conditioner::envelope_residual(hipStream_t st, const float *obs, const floa
     if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
     ensure_envelope_buffers();
     const size_t g = (size_t)nt_ * cap_;
-    float *ho = env_.get(), *hs = ho + g, *b = ho + 2 * g;
+    float *hd = env_.get(), *hs = hd + g, *b = hd + 2 * g;
     const dim3 grid((nt_ + 255) / 256, nrec), blk(256);
-    hilbert(st, obs, ho, nrec);
+    hipLaunchKernelGGL(k_env_diff, grid, blk, 0, st, nt_, nrec, obs, syn, hd);
+    hilbert(st, hd, hd, nrec);  // H (obs - syn), in place (the transform reads its input into the padded buffer first)
     hilbert(st, syn, hs, nrec);
-    hipLaunchKernelGGL(k_env_residual, dim3(nrec), blk, 0, st, nt_, obs, (const float *)ho, syn, (const float *)hs, res, b, env_sum_.get());
+    hipLaunchKernelGGL(k_env_residual, dim3(nrec), blk, 0, st, nt_, obs, (const float *)hd, syn, (const float *)hs, res, b, env_sum_.get());
     hipLaunchKernelGGL(k_env_sum, dim3(1), blk, 0, st, nrec, (const double *)env_sum_.get(), acc);
     hilbert(st, b, b, nrec);
     hipLaunchKernelGGL(k_env_combine, grid, blk, 0, st, nt_, nrec, res, (const float *)b, 1.0f);

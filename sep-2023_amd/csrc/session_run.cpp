@@ -245,7 +245,7 @@ void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
     misfit_chain(st, x.d_obs, x.id, x.nrec, scal_);
     launch_transpose(st, xpose2_, x.res, x.nrec, nSteps);  // [rec][it] -> [it][rec]: the adjoint source
     cs_.launches += 8;
-    if (par_.if_envelope_misfit) cs_.launches += 17;  // three Hilbert transforms of five launches each, residual, sum, combination -- for the one of l2_residual
+    if (par_.if_envelope_misfit) cs_.launches += 18;  // the data residual, three Hilbert transforms of five launches each, residual, sum, combination -- for the one of l2_residual
 }
 
 // The middle of it, between the two transpositions: the raw [rec][it] synthetic gather in xpose_ and the shot's CONDITIONED observed gather

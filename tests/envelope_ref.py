@@ -16,6 +16,7 @@ conditioning keys stripped -- the hook the oracle's own chain uses; J is tests/b
 import numpy as np
 
 import cond_gn_ref as G
+from fuzz_common import groups
 
 KEY = "if_envelope_misfit"
 STRIP = G.COND_KEYS + (KEY,)
@@ -137,11 +138,27 @@ def plain_para(pb):
     return {k: v for k, v in pb["para"].items() if k not in STRIP}
 
 
-def gradient(O, pb, adj, model="lame_init"):
-    """the oracle's backward pass with the adjoint source a (per shot (nrec, nSteps)) injected: dict(gLambda, gMu, gDen, gStf)"""
+def gradient(O, pb, adj, model="lame_init", gauge=0):
+    """the oracle's backward pass with the adjoint source a (per shot (nrec, nSteps)) injected: dict(gLambda, gMu, gDen, gStf).  Shots
+    with different channel counts run one at a time (fuzz_common.groups) and are summed in shot order; gauge = G cells: the channels are
+    gauge channels, a is spread over their members (gauge_ref.inject)."""
     m = [t.numpy() for t in pb[model]]
-    a = np.ascontiguousarray(np.stack([np.asarray(x, np.float32) for x in adj]))
-    return O.cufd(*m, pb["Stf"].numpy(), 1, pb["Shot_ids"].numpy(), plain_para(pb), pb["survey"], adj_src=a)
+    stf, ids = pb["Stf"].numpy(), pb["Shot_ids"].numpy()
+    if gauge:
+        import gauge_ref
+        return gauge_ref.inject(O, m, stf, ids, plain_para(pb), pb["survey"], gauge, [np.asarray(x, np.float32) for x in adj])
+    out, pos = None, 0
+    for grp in groups(ids, pb["survey"]):
+        a = np.ascontiguousarray(np.stack([np.asarray(x, np.float32) for x in adj[pos:pos + len(grp)]]))
+        pos += len(grp)
+        r = O.cufd(*m, stf, 1, np.asarray(grp, np.int32), plain_para(pb), pb["survey"], adj_src=a)
+        if out is None:
+            out = r
+        else:
+            for k in ("gLambda", "gMu", "gDen"):
+                out[k] = out[k] + r[k]
+            out["gStf"] = np.concatenate([out["gStf"], r["gStf"]], axis=0)
+    return out
 
 
 # ---- the problem of the GPU tests -----------------------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ the first 16 seeds' draws
 (draw_problem; draw_gauge, draw_born and draw_exact change its draw for tests/test_gpu_gauge_fuzz.py, test_gpu_born_fuzz.py and
 test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw; draw_pseudo_hessian adds to it, and changes nothing, for
 tests/test_gpu_pseudo_hessian_fuzz.py; draw_conditioned puts draw_born's draw under live conditioning keys for
-tests/test_gpu_conditioned_gn_fuzz.py, its digest is in tests/test_conditioned_fuzz_reference.py)."""
+tests/test_gpu_conditioned_gn_fuzz.py, its digest is in tests/test_conditioned_fuzz_reference.py; draw_envelope writes that draw once
+more with if_envelope_misfit for tests/test_gpu_envelope_fuzz.py, its digest is in tests/test_envelope_fuzz_reference.py)."""
 import json
 import os
 
@@ -430,6 +431,39 @@ def draw_conditioned(d, b, seed, syn):
     cpb["para_fname"], cpb["para"] = G.write_files(pb, "cond", para, csv)
     cpb["survey"], cpb["survey_fname"], cpb["data_dir"] = csv, cpb["para"]["survey_fname"], cpb["para"]["data_dir_name"]
     return dict(mode=mode, pb=cpb, empty=empty, v_seeds=raw["v_seeds"])
+
+
+# ---- the envelope misfit (if_envelope_misfit) on the conditioned draw ----------------------------------------------------------------
+ENV_SEED0 = 99001      # offset of the generator (how it was chosen: tests/test_envelope_fuzz_reference.py)
+ENV_KEY = "if_envelope_misfit"
+
+
+def envelope_raw(seed):
+    """What draw_envelope draws for a seed, every quantity for every seed: whether the key stands alone (one draw in four) and the seed
+    of the white-noise gathers a test may want."""
+    rg = np.random.default_rng(ENV_SEED0 + seed)
+    return dict(alone=int(rg.integers(0, 4)) == 0, noise_seed=int(rg.integers(0, 2 ** 31)))
+
+
+def draw_envelope(d, c, seed):
+    """The conditioned draw (d: draw_problem, c: draw_conditioned) written a second time with if_envelope_misfit added: the pair
+    "env" next to the conditioned pair, same survey (windows, weights, src_weight), same keys plus the key -- or, in one draw of four,
+    the key ALONE: if_win and filter leave the file (nobody then reads the survey's windows) and C is the plain end taper.  The pair
+    "env_twin" is the same file without the key, for the bit-identity checks.  draw_conditioned's own pair stays what it is.
+    -> dict(mode (c's, or "alone"), alone, pb, twin (shallow copies of c["pb"] on the two pairs), noise_seed)."""
+    import cond_gn_ref as G
+    raw = envelope_raw(seed)
+    cpb = c["pb"]
+    para = {k: v for k, v in cpb["para"].items() if k not in ("survey_fname", "data_dir_name")}
+    if raw["alone"]:
+        para = {k: v for k, v in para.items() if k not in COND_KEYS}
+    out = {}
+    for name, extra in (("pb", {ENV_KEY: True}), ("twin", {})):
+        pb = dict(cpb)
+        pb["para_fname"], pb["para"] = G.write_files(d["pb"], "env" if name == "pb" else "env_twin", dict(para, **extra), cpb["survey"])
+        pb["survey_fname"], pb["data_dir"] = pb["para"]["survey_fname"], pb["para"]["data_dir_name"]
+        out[name] = pb
+    return dict(mode="alone" if raw["alone"] else c["mode"], alone=raw["alone"], noise_seed=raw["noise_seed"], **out)
 
 
 # ---- the diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

@@ -96,11 +96,6 @@ def reference(oracle, models, stf, ids, para, survey, G, obs_gauge, cond=None):
     counts are run one at a time and summed in shot order.
 
     -> dict(misfit, gLambda, gMu, gDen, gStf (group, nSteps), gauge (list per shot, float64), own (list per shot: pr, vx, vz))."""
-    vertical = para.get("das_fiber", "horizontal") == "vertical"
-    plain = {k: v for k, v in para.items() if k not in COND_KEYS + ("das_gauge_length",)}
-    msurvey = member_survey(survey, G, vertical)
-    _, w = members(G)
-    lam, mu, den = [np.asarray(m) for m in models]
     stf = np.asarray(stf)
     all_ids = [int(i) for i in np.asarray(ids).reshape(-1)]
     if cond is None:
@@ -123,11 +118,31 @@ def reference(oracle, models, stf, ids, para, survey, G, obs_gauge, cond=None):
             obj, a, _, _ = oracle.conditioned_residual(o.astype(np.float32), gauge[i].astype(np.float32), np.float32(para["dt"]), conds[i])
             total += obj
             a = a.astype(np.float64)
-        adj.append((w[None, :, None] * a[:, None, :]).reshape(a.shape[0] * w.size, a.shape[1]).astype(np.float32))
+        adj.append(a)
+    out = inject(oracle, models, stf, ids, para, survey, G, adj)
+    out.update(misfit=0.5 * total, gauge=gauge, own=own)
+    return out
+
+
+def inject(oracle, models, stf, ids, para, survey, G, adj):
+    """The oracle's backward pass of the gauge problem with a caller's CHANNEL-space adjoint source: adj per shot of ids (nrec, nSteps),
+    a_c = -d misfit / d gauge_c.  Member j of channel c is handed  w_j a_c  (formed in float64, float32 as the oracle takes it) through
+    oracle.cufd(adj_src=...) on the member survey, one call per group of fuzz_common.groups, summed in shot order.  models, para, survey
+    as `reference` takes them.  -> dict(gLambda, gMu, gDen, gStf (group, nSteps))."""
+    vertical = para.get("das_fiber", "horizontal") == "vertical"
+    plain = {k: v for k, v in para.items() if k not in COND_KEYS + ("das_gauge_length",)}
+    msurvey = member_survey(survey, G, vertical)
+    _, w = members(G)
+    lam, mu, den = [np.asarray(m) for m in models]
+    stf = np.asarray(stf)
+    spread = []
+    for a in adj:
+        a = np.asarray(a, np.float64)
+        spread.append((w[None, :, None] * a[:, None, :]).reshape(a.shape[0] * w.size, a.shape[1]).astype(np.float32))
     out = None
     pos = 0
     for grp in groups(ids, survey):
-        r = oracle.cufd(lam, mu, den, stf, 1, np.asarray(grp, np.int32), plain, msurvey, adj_src=np.stack(adj[pos:pos + len(grp)]))
+        r = oracle.cufd(lam, mu, den, stf, 1, np.asarray(grp, np.int32), plain, msurvey, adj_src=np.stack(spread[pos:pos + len(grp)]))
         pos += len(grp)
         if out is None:
             out = {k: r[k].copy() for k in ("gLambda", "gMu", "gDen", "gStf")}
@@ -135,5 +150,4 @@ def reference(oracle, models, stf, ids, para, survey, G, obs_gauge, cond=None):
             for k in ("gLambda", "gMu", "gDen"):
                 out[k] += r[k]
             out["gStf"] = np.concatenate([out["gStf"], r["gStf"]], axis=0)
-    out.update(misfit=0.5 * total, gauge=gauge, own=own)
     return out
