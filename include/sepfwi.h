@@ -278,7 +278,9 @@ int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, con
  *   sepfwi_data_misfit   *misfit = the file's misfit of (obs, syn), halved as sepfwi_cufd reports it; adj (may be NULL) = the raw-space
  *       adjoint source a = -d misfit / d syn, what the backward pass injects:  C^T Z (C obs - C syn) for the L2 misfit (C = 1 without a
  *       conditioning key),  the adjoint source of the normalised cross-correlation under if_cross_misfit,  C^T D^T Z (e(C obs) - e(C syn))
- *       under if_envelope_misfit.  SEPFWI_EINVAL under if_src_update and under weights other than (1, 0, 0).
+ *       under if_envelope_misfit.  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot, as
+ *       a gradient call computes it: the misfit is that of the updated synthetics, a is taken with the filter held fixed.  SEPFWI_EINVAL
+ *       under weights other than (1, 0, 0).
  *   sepfwi_data_gn       out = the Gauss-Newton operator of the misfit at syn applied to d:  C^T Z C d for the L2 misfit (syn is not
  *       read),  C^T D^T Z D C d under if_envelope_misfit, D at C syn.  Symmetric and non-negative.  SEPFWI_EINVAL under if_cross_misfit,
  *       if_src_update and under weights other than (1, 0, 0).

@@ -78,8 +78,11 @@ __global__ void k_bp_filter(int nf, int nrec, float df, float f0, float f1, floa
     c.y *= a * a;
 }
 
-// cuda_find_normfact (utilities.cu:1010-1040): out[r] = sum_t a b + DIVCONST; one block per trace, double partial sums
-__global__ void k_normfact(int nt, const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ out) {
+// cuda_find_normfact (utilities.cu:1010-1040): out[r] = sum_t a b + DIVCONST; one block per trace, double partial sums, and the norm is
+// KEPT in double: k_cross_adjoint subtracts (n_os / n_ss) syn from obs, and where the data nearly fit (obs close to a multiple of syn,
+// every late iteration of an inversion) that difference is a cancellation -- a norm rounded to float32 is off by 6e-8 of itself, and
+// 6e-8 |obs| is 1e-3 of a residual that is 1e-4 of the data (tests/test_gpu_cross_data.py: nearly fitting data).
+__global__ void k_normfact(int nt, const float *__restrict__ a, const float *__restrict__ b, double *__restrict__ out) {
     const int r = blockIdx.x;
     double s = 0.0;
     for (int it = threadIdx.x; it < nt; it += blockDim.x) s += (double)a[(size_t)r * nt + it] * (double)b[(size_t)r * nt + it];
@@ -87,15 +90,15 @@ __global__ void k_normfact(int nt, const float *__restrict__ a, const float *__r
     __shared__ double part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) out[r] = (float)(part[0] + part[1] + part[2] + part[3]) + 1e-9f;  // DIVCONST, utilities.h:24
+    if (threadIdx.x == 0) out[r] = part[0] + part[1] + part[2] + part[3] + (double)1e-9f;  // DIVCONST, utilities.h:24
 }
 
 // cuda_normal_misfit (utilities.cu:1056-1083): *acc += -2 sum_r cross / (sqrt(obs) sqrt(cal)) w_r  (the driver halves the total)
-__global__ void k_cross_misfit(int nrec, const float *__restrict__ n_os, const float *__restrict__ n_oo, const float *__restrict__ n_ss,
+__global__ void k_cross_misfit(int nrec, const double *__restrict__ n_os, const double *__restrict__ n_oo, const double *__restrict__ n_ss,
                                const float *__restrict__ weights, float src_weight, double *__restrict__ acc) {
     double s = 0.0;
     for (int r = threadIdx.x; r < nrec; r += blockDim.x)
-        s += (double)(n_os[r] / (sqrtf(n_oo[r]) * sqrtf(n_ss[r])) * (weights ? weights[r] * src_weight : 1.0f));
+        s += n_os[r] / (sqrt(n_oo[r]) * sqrt(n_ss[r])) * (double)(weights ? weights[r] * src_weight : 1.0f);
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     __shared__ double part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
@@ -103,15 +106,17 @@ __global__ void k_cross_misfit(int nrec, const float *__restrict__ n_os, const f
     if (threadIdx.x == 0) atomicAdd(acc, -2.0 * (part[0] + part[1] + part[2] + part[3]));
 }
 
-// cuda_normal_adjoint_source (utilities.cu:1086-1111)
-__global__ void k_cross_adjoint(int nt, int nrec, const float *__restrict__ n_oo, const float *__restrict__ n_ss,
-                                const float *__restrict__ n_os, const float *__restrict__ obs, const float *__restrict__ syn,
+// cuda_normal_adjoint_source (utilities.cu:1086-1111).  obs - (n_os / n_ss) syn is formed per element in double, from the double
+// norms, and rounded once: its error is then half a unit of the residual's last place, however nearly the data fit.
+__global__ void k_cross_adjoint(int nt, int nrec, const double *__restrict__ n_oo, const double *__restrict__ n_ss,
+                                const double *__restrict__ n_os, const float *__restrict__ obs, const float *__restrict__ syn,
                                 float *__restrict__ res, const float *__restrict__ weights, float src_weight) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
     if (it >= nt || r >= nrec) return;
     const size_t i = (size_t)r * nt + it;
-    const float w = weights ? weights[r] * src_weight : 1.0f;
-    res[i] = (obs[i] - n_os[r] / n_ss[r] * syn[i]) / (sqrtf(n_oo[r]) * sqrtf(n_ss[r])) * w;
+    const double w = (double)(weights ? weights[r] * src_weight : 1.0f);
+    const double ratio = n_os[r] / n_ss[r], scale = w / (sqrt(n_oo[r]) * sqrt(n_ss[r]));
+    res[i] = (float)(((double)obs[i] - ratio * (double)syn[i]) * scale);
 }
 
 // gpuMinus + cuda_cal_objective on [rec][it] (utilities.cu:154-205): r = obs - syn, first sample zeroed, *acc += sum r^2
@@ -308,7 +313,7 @@ Conditioner::Conditioner(int nt, int max_nrec) : nt_(nt), cap_(max_nrec) {
     const size_t npad = 2 * (size_t)nt, nf = (size_t)nt + 1;
     pad_ = DevBuf<float>(&bytes_, npad * cap_);
     spec_ = DevBuf<float2>(&bytes_, nf * cap_);
-    norm_ = DevBuf<float>(&bytes_, 3 * (size_t)cap_);
+    norm_ = DevBuf<double>(&bytes_, 3 * (size_t)cap_);
 }
 
 Conditioner::~Conditioner() {
@@ -426,7 +431,7 @@ void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *
                                  float src_weight, double *acc) {
     if (nrec <= 0) return;
     if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
-    float *n_oo = norm_.get(), *n_ss = n_oo + cap_, *n_os = n_oo + 2 * (size_t)cap_;
+    double *n_oo = norm_.get(), *n_ss = n_oo + cap_, *n_os = n_oo + 2 * (size_t)cap_;
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, obs, n_oo);
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, syn, syn, n_ss);
     hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, syn, n_os);

@@ -68,7 +68,8 @@ class Conditioner {
     Plans &plans_for(int nrec, hipStream_t st);
     int nt_, cap_;
     long long bytes_ = 0;
-    DevBuf<float> pad_, norm_, pad2_;
+    DevBuf<float> pad_, pad2_;
+    DevBuf<double> norm_;          // the three per-trace norms of the cross-correlation misfit, 3 x [cap]
     DevBuf<float2> spec_;          // hipfftComplex [cap][nt + 1]
     DevBuf<float2> spec2_, coef_;  // second padded gather / spectrum and the nt + 1 matching-filter coefficients (source update)
     DevBuf<float> env_;            // envelope misfit: 3 x [cap][nt]

@@ -136,7 +136,7 @@ void Session::upload_survey() {
             HIP_OK(hipMemcpy(sens_, sv.data(), sv.size() * sizeof(float), hipMemcpyHostToDevice));
         }
     }
-    if (cond_on_) {  // [start | end | weight] per channel; without if_win only the weights matter (cross-correlation misfit)
+    if (cond_on_) {  // [start | end | weight] per channel, read under if_win alone (the windows, and the trace weights of the cross-correlation misfit)
         const int ns = (int)survey_.shots.size();
         const size_t tot = (size_t)rec_off_[ns] + 1;
         std::vector<float> w(3 * tot, 0.0f);

@@ -5,7 +5,9 @@
 // gradient call or a Gauss-Newton product runs between its two transpositions (Session::misfit_chain, Session::gn_chain):
 //   data_misfit   the file's misfit of (obs, syn) and the raw-space adjoint source a = -d misfit / d syn: C^T Z (C obs - C syn) under an L2
 //                 file, the adjoint source of the normalised cross-correlation under if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under
-//                 if_envelope_misfit.  if_src_update is refused (its matching filter is a state of the shot's last gradient call).
+//                 if_envelope_misfit.  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
+//                 as a gradient call computes it; the misfit is that of the updated synthetics and a is taken with the filter held fixed
+//                 (nothing is carried from one shot or call to the next).
 //   data_gn       the Gauss-Newton operator of the misfit in data space at syn: C^T Z C d, or C^T D^T Z D C d under if_envelope_misfit.
 //                 Refused under if_cross_misfit and if_src_update (not a least-squares misfit of the data), as the products are.
 // A file without a live conditioning key has C = 1 and no conditioner: its misfit runs through the residual kernel of its gradient calls
@@ -29,7 +31,6 @@ void Session::ensure_data_scratch() {
 
 void Session::data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int group_size, const int *shot_ids, hipStream_t ext_stream) {
     std::lock_guard<std::mutex> lock(mu_);
-    if (par_.if_src_update) throw std::invalid_argument("data_misfit: not defined under if_src_update (the matching filter belongs to a shot's gradient call)");
     if (joint_) throw std::invalid_argument("data_misfit: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);
     HIP_OK(hipSetDevice(gpu_id_));

@@ -255,8 +255,8 @@ void Session::misfit_chain(hipStream_t st, const float *d_obs, int shot_id, int 
     const Shot &sh = survey_.shots[shot_id];
     condition_gather(st, xpose_, shot_id, nrec);
     if (par_.if_src_update) cond_->source_update(st, d_obs, xpose_, nrec, par_.dt);  // libCUFD.cu:383-390
-    if (par_.if_cross_misfit)
-        cond_->cross_residual(st, d_obs, xpose_, xpose2_, nrec, win_ + 2 * tot + off, sh.src_weight, acc);
+    if (par_.if_cross_misfit)  // the trace weights belong to if_win, as the window's do: without the key w_r = 1 (oracle.conditioned_residual)
+        cond_->cross_residual(st, d_obs, xpose_, xpose2_, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
     else if (par_.if_envelope_misfit)
         cond_->envelope_residual(st, d_obs, xpose_, xpose2_, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
     else

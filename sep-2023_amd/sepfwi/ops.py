@@ -521,8 +521,9 @@ class _FwiOps:
         obs, syn are float32 tensors holding the gathers [nrec_i][nSteps] shot after shot in the order of Shot_ids (any shape with that
         many elements, CPU or HIP).  -> (misfit, adj): the misfit as `forward` reports it (a Python float) and the raw-space adjoint source
         a = -d misfit / d syn in syn's shape and device -- C^T Z (C obs - C syn) under an L2 file, the cross-correlation's under
-        if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under if_envelope_misfit.  if_src_update is refused.  With `born_adjoint` a caller
-        composes a gradient pass: g = -J^T a."""
+        if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under if_envelope_misfit.  Under if_src_update the matching filter is computed
+        from the call's own (C obs, C syn), shot by shot; the misfit is that of the updated synthetics and a holds the filter fixed.
+        With `born_adjoint` a caller composes a gradient pass: g = -J^T a."""
         (obs, syn), ids, dev, stream = self._data_args((obs, syn), ("obs", "syn"), Shot_ids, para_fname, gpu_id)
         adj = torch.empty_like(syn)
         mis = C.c_float(0.0)

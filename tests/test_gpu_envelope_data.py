@@ -18,66 +18,21 @@ import pytest
 import torch
 
 import cond_gn_ref as G
+import data_entry_common as DC
 import envelope_ref as E
-import problems as P
+from data_entry_common import flat, rel, traces, unflat
 
 pytestmark = pytest.mark.gpu
 MISFIT_TOL, DATA_TOL, SYM_TOL = 1e-4, 1e-4, 1e-3
-NSTEPS = (2, 3, 63, 64, 65, 255, 256, 257, 600)
+NSTEPS = DC.NSTEPS
 LAYOUTS = {"one": (1,), "five": (5,), "ragged": (5, 3)}
-DT = 1.0e-3
 FILTER = [25.0, 60.0, 260.0, 400.0]      # the traces carry 25 ... 175 Hz: the lower ramp cuts into them; the one live bin of nSteps = 2 (250 Hz) passes
 KEYSETS = {"alone": {}, "filter": {"filter": FILTER}, "window": {"if_win": True}, "both": {"filter": FILTER, "if_win": True}}
 
 
 def problem(tmp, nt, layout, keys, name, misfit_key=E.KEY):
-    """a parameter / survey file pair: len(layout) shots with layout[i] channels, windows and weights in the survey, `keys` and the
-    misfit's key in the parameter file"""
-    nrec = LAYOUTS[layout]
-    pb = P.make_problem(str(tmp), nz=40, nx=48, nPml=10, nSteps=nt, nshots=len(nrec), dt=DT, rec_x=list(range(6, 6 + max(nrec))))
-    rng = np.random.default_rng(17)
-    sv, T = dict(pb["survey"]), nt * DT
-    for i, n in enumerate(nrec):
-        sh = dict(sv["shot%d" % i])
-        sh["z_rec"], sh["x_rec"], sh["nrec"] = sh["z_rec"][:n], sh["x_rec"][:n], n
-        sh["win_start"] = [float(v) for v in rng.uniform(0.05 * T, 0.3 * T, n)]
-        sh["win_end"] = [float(v) for v in rng.uniform(0.6 * T, 0.95 * T, n)]
-        sh["weights"] = [float(v) for v in rng.uniform(0.5, 2.0, n)]
-        if n > 1:
-            sh["weights"][1] = 0.0
-        if n >= 3:
-            sh["win_end"][n - 1] = sh["win_start"][n - 1]
-        sh["src_weight"] = 1.3 + 0.2 * i
-        sv["shot%d" % i] = sh
-    para = dict({k: v for k, v in pb["para"].items() if k not in E.STRIP}, **keys)
-    if misfit_key:
-        para[misfit_key] = True
-    pb = dict(pb)
-    pb["para_fname"], pb["para"] = G.write_files(pb, name, para, sv)
-    pb["survey"] = sv
-    return pb
-
-
-def traces(pb, seed):
-    nt = pb["nSteps"]
-    rng = np.random.default_rng(seed)
-    return [E.band_limited(rng, int(pb["survey"]["shot%d" % s]["nrec"]), nt) for s in G.shots_of(pb)]
-
-
-def flat(gathers):
-    return torch.from_numpy(np.concatenate([np.asarray(g, np.float32).reshape(-1) for g in gathers]))
-
-
-def unflat(t, like):
-    a, out, off = t.cpu().numpy(), [], 0
-    for g in like:
-        out.append(a[off:off + g.size].reshape(g.shape))
-        off += g.size
-    return out
-
-
-def rel(got, ref):
-    return G.norm([np.asarray(a, np.float64) - np.asarray(b, np.float64) for a, b in zip(got, ref)]) / G.norm(ref)
+    """data_entry_common.problem with the channel counts of LAYOUTS[layout]"""
+    return DC.problem(tmp, nt, LAYOUTS[layout], keys, name, misfit_key)
 
 
 # ---- against the reference ----------------------------------------------------------------------------------------------------------------
@@ -175,13 +130,21 @@ def test_existing_misfits_through_data_misfit(oracle, hip_ops, tmp_path, misfit)
     hip_ops.release()
 
 
-def test_data_entry_points_refuse_if_src_update(hip_ops, tmp_path):
+def test_data_entry_points_refuse_if_src_update(oracle, hip_ops, tmp_path):
+    """data_gn is refused (-1) under if_src_update; data_misfit is served: the misfit and adjoint source of
+    oracle.conditioned_residual(..., src_update=True) to the same tolerances (tests/test_gpu_source_update_data.py holds it at every
+    shape)."""
     from sepfwi import _native
     hip_ops.release()
     pb = problem(tmp_path, 64, "five", {}, "srcupd", misfit_key="if_src_update")
-    x = flat(traces(pb, 1)).cuda()
-    for call in (lambda: hip_ops.data_misfit(x, x, pb["Shot_ids"], pb["para_fname"]), lambda: hip_ops.data_gn(x, x, pb["Shot_ids"], pb["para_fname"])):
-        with pytest.raises(_native.SepFwiError) as e:
-            call()
-        assert e.value.code == -1 and "if_src_update" in str(e.value)
+    obs, syn = traces(pb, 1), traces(pb, 2)
+    x = flat(obs).cuda()
+    with pytest.raises(_native.SepFwiError) as e:
+        hip_ops.data_gn(x, x, pb["Shot_ids"], pb["para_fname"])
+    assert e.value.code == -1 and "if_src_update" in str(e.value)
+    obj, a_ref, _, _ = oracle.conditioned_residual(obs[0], syn[0], float(pb["para"]["dt"]), oracle.conditioning_of(pb["para"], pb["survey"], 0))
+    f, a = hip_ops.data_misfit(x, flat(syn).cuda(), pb["Shot_ids"], pb["para_fname"])
+    dev = (abs(f - 0.5 * obj) / (0.5 * obj), rel(unflat(a, obs), [a_ref]))
+    print("envelope data if_src_update file: misfit %.8e (oracle %.8e, relative gap %.2e), adj rel-L2 %.2e" % (f, 0.5 * obj, *dev))
+    assert obj > 0 and G.norm([a_ref]) > 0 and dev[0] <= MISFIT_TOL and dev[1] <= DATA_TOL
     hip_ops.release()
