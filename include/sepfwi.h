@@ -319,6 +319,8 @@ typedef struct sepfwi_stats {
     long long fwd_steps;      /* forward time steps executed                                  */
     long long bwd_steps;      /* backward time steps executed                                 */
     long long launches;       /* kernel launches issued                                       */
+                              /* (under a live data-conditioning key the chain of a shot is counted too: one per kernel and one per
+                                 hipFFT exec; conditioning an observed gather when it is installed belongs to no call) */
     long long device_bytes;   /* device memory held by the session: every block, at its allocated size, while it is held */
     int n_c;                  /* computed cells per step (nz-nPad)*(nx)  [PML included]       */
     double probe_kernel_us;   /* option "probe">0: mean duration of the sampled k_bwd_b launches (HIP events) */

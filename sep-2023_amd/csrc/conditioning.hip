@@ -33,6 +33,25 @@ __device__ __forceinline__ float ramp(float t, float t0, float t1, float t2, flo
     return 0.0f;
 }
 
+// The block reduction of every sum below: v[n] summed over a block of 256 threads (four waves), N sums side by side.  Per sum the 64-lane
+// shuffle tree, one partial per wave in LDS, then part[0] + part[1] + part[2] + part[3] -- in THAT order, which is what keeps the misfits
+// and norms the same bits from one build to the next.  The result is meant for thread 0; one use per kernel (nothing guards `part` against a
+// second round).
+template <int N> __device__ __forceinline__ void block_sum(double (&v)[N]) {
+    __shared__ double part[N][4];
+    for (int n = 0; n < N; n++) {
+        for (int off = 32; off > 0; off >>= 1) v[n] += __shfl_down(v[n], off, 64);
+        if ((threadIdx.x & 63) == 0) part[n][threadIdx.x >> 6] = v[n];
+    }
+    __syncthreads();
+    for (int n = 0; n < N; n++) v[n] = part[n][0] + part[n][1] + part[n][2] + part[n][3];
+}
+__device__ __forceinline__ double block_sum(double v) {
+    double one[1] = {v};
+    block_sum(one);
+    return one[0];
+}
+
 // cuda_window, both overloads (utilities.cu:787-884).  win_start == nullptr: one taper of `ratio` of the trace length at
 // both ends; else per-trace window [win_start, win_end] seconds, amplitude times weights[r] * src_weight.
 __global__ void k_window(int nt, int nrec, float dt, const float *__restrict__ win_start, const float *__restrict__ win_end,
@@ -86,11 +105,8 @@ __global__ void k_normfact(int nt, const float *__restrict__ a, const float *__r
     const int r = blockIdx.x;
     double s = 0.0;
     for (int it = threadIdx.x; it < nt; it += blockDim.x) s += (double)a[(size_t)r * nt + it] * (double)b[(size_t)r * nt + it];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[r] = part[0] + part[1] + part[2] + part[3] + (double)1e-9f;  // DIVCONST, utilities.h:24
+    s = block_sum(s);
+    if (threadIdx.x == 0) out[r] = s + (double)1e-9f;  // DIVCONST, utilities.h:24
 }
 
 // cuda_normal_misfit (utilities.cu:1056-1083): *acc += -2 sum_r cross / (sqrt(obs) sqrt(cal)) w_r  (the driver halves the total)
@@ -99,11 +115,8 @@ __global__ void k_cross_misfit(int nrec, const double *__restrict__ n_os, const 
     double s = 0.0;
     for (int r = threadIdx.x; r < nrec; r += blockDim.x)
         s += n_os[r] / (sqrt(n_oo[r]) * sqrt(n_ss[r])) * (double)(weights ? weights[r] * src_weight : 1.0f);
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(acc, -2.0 * (part[0] + part[1] + part[2] + part[3]));
+    s = block_sum(s);
+    if (threadIdx.x == 0) atomicAdd(acc, -2.0 * s);
 }
 
 // cuda_normal_adjoint_source (utilities.cu:1086-1111).  obs - (n_os / n_ss) syn is formed per element in double, from the double
@@ -130,11 +143,8 @@ __global__ void k_l2_residual(int nt, int nrec, const float *__restrict__ obs, c
         res[i] = v;
         s += (double)v * (double)v;
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(acc, part[0] + part[1] + part[2] + part[3]);
+    s = block_sum(s);
+    if (threadIdx.x == 0) atomicAdd(acc, s);
 }
 
 // the same residual for observed data syn - d (the Gauss-Newton product, d = C J v): r = -d, first sample zeroed.  No misfit.
@@ -152,30 +162,18 @@ __global__ void k_scattered_residual(int nt, int nrec, const float *__restrict__
 __global__ void k_matching_coef(int nf, int nrec, const hipfftComplex *__restrict__ O, const hipfftComplex *__restrict__ Cs,
                                 hipfftComplex *__restrict__ coef) {
     const int k = blockIdx.x;
-    double nr = 0.0, ni = 0.0, dn = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};  // Re and Im of the numerator, the denominator
     for (int r = threadIdx.x; r < nrec; r += blockDim.x) {
         const hipfftComplex o = O[(size_t)r * nf + k], c = Cs[(size_t)r * nf + k];
-        nr += (double)c.x * o.x + (double)c.y * o.y;   // conj(c) * o
-        ni += (double)c.x * o.y - (double)c.y * o.x;
-        dn += (double)c.x * c.x + (double)c.y * c.y;
+        s[0] += (double)c.x * o.x + (double)c.y * o.y;   // conj(c) * o
+        s[1] += (double)c.x * o.y - (double)c.y * o.x;
+        s[2] += (double)c.x * c.x + (double)c.y * c.y;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        nr += __shfl_down(nr, off, 64);
-        ni += __shfl_down(ni, off, 64);
-        dn += __shfl_down(dn, off, 64);
-    }
-    __shared__ double part[3][4];
-    if ((threadIdx.x & 63) == 0) {
-        part[0][threadIdx.x >> 6] = nr;
-        part[1][threadIdx.x >> 6] = ni;
-        part[2][threadIdx.x >> 6] = dn;
-    }
-    __syncthreads();
+    block_sum(s);
     if (threadIdx.x == 0) {
-        const double a = part[0][0] + part[0][1] + part[0][2] + part[0][3], b = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        const double d = part[2][0] + part[2][1] + part[2][2] + part[2][3] + 1e-6;
-        coef[k].x = (float)(a / d);
-        coef[k].y = (float)(b / d);
+        const double d = s[2] + 1e-6;
+        coef[k].x = (float)(s[0] / d);
+        coef[k].y = (float)(s[1] / d);
     }
 }
 
@@ -233,22 +231,16 @@ __global__ void k_env_residual(int nt, const float *__restrict__ o, const float 
         b[i] = hv * rho;
         acc += (double)rho * (double)rho;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) sum[r] = part[0] + part[1] + part[2] + part[3];
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) sum[r] = acc;
 }
 
 // *acc += sum_r sum[r], one block, a fixed order (the call's stream serialises the shots: no atomic is needed)
 __global__ void k_env_sum(int nrec, const double *__restrict__ sum, double *__restrict__ acc) {
     double s = 0.0;
     for (int r = threadIdx.x; r < nrec; r += blockDim.x) s += sum[r];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __shared__ double part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *acc += part[0] + part[1] + part[2] + part[3];
+    s = block_sum(s);
+    if (threadIdx.x == 0) *acc += s;
 }
 
 // The linearised twin at the background s for a data perturbation d: rho' = Z 2 (s d + (H s)(H d)) = Z D d, then a = s rho', b = (H s) rho'
@@ -323,27 +315,21 @@ Conditioner::~Conditioner() {
     }
 }
 
-void Conditioner::window(hipStream_t st, float *data, int nrec, float dt, const float *win_start, const float *win_end,
-                         const float *weights, float src_weight, float ratio) {
-    if (nrec <= 0) return;
-    hipLaunchKernelGGL(k_window, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, dt, win_start, win_end, weights, src_weight,
-                       ratio, data);
+// Every kernel of the chain runs in blocks of 256 threads and is counted as one launch (launches())
+template <class K, class... A> void Conditioner::launch(K kernel, dim3 grid, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, args...);
+    launches_++;
 }
 
-// bp_filter1d, utilities.cu:1115-1166
-void Conditioner::bandpass(hipStream_t st, float *data, int nrec, float dt, const float filt[4]) {
-    if (nrec <= 0) return;
+bool Conditioner::idle(int nrec) const {
     if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
-    const int npad = 2 * nt_, nf = nt_ + 1;
-    Plans &pl = plans_for(nrec, st);
-    hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
-    hipLaunchKernelGGL(k_embed, dim3((npad + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_.get());
-    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
-    const float df = (float)(1.0 / (double)dt / (double)npad);
-    hipLaunchKernelGGL(k_bp_filter, dim3((nf + 255) / 256, nrec), dim3(256), 0, st, nf, nrec, df, filt[0], filt[1], filt[2], filt[3],
-                       (hipfftComplex *)spec_.get());
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, data, pad_.get(), 1.0f / (float)npad);
+    return nrec <= 0;
+}
+
+void Conditioner::window(hipStream_t st, float *data, int nrec, float dt, const float *win_start, const float *win_end,
+                         const float *weights, float src_weight, float ratio) {
+    if (idle(nrec)) return;
+    launch(k_window, time_grid(nrec), st, nt_, nrec, dt, win_start, win_end, weights, src_weight, ratio, data);
 }
 
 Conditioner::Plans &Conditioner::plans_for(int nrec, hipStream_t st) {
@@ -366,6 +352,38 @@ Conditioner::Plans &Conditioner::plans_for(int nrec, hipStream_t st) {
     return it->second;
 }
 
+// ---- the steps of a spectral round trip (conditioning.hpp) ----
+void Conditioner::embed(hipStream_t st, const float *in, float *pad, int nrec) { launch(k_embed, pad_grid(nrec), st, nt_, nrec, in, pad); }
+void Conditioner::taper_padded(hipStream_t st, float *pad, int nrec, float dt) {  // cuda_window over the PADDED length, ratio 0.01 (utilities.cu:1199-1202)
+    launch(k_window, pad_grid(nrec), st, 2 * nt_, nrec, dt, nullptr, nullptr, nullptr, 1.0f, 0.01f, pad);
+}
+void Conditioner::forward(const Plans &pl, float *pad, float2 *spec) { fft_ok(fft().ExecR2C((hipfftHandle)pl.fwd, pad, spec), "hipfftExecR2C"), launches_++; }
+void Conditioner::inverse(const Plans &pl, float2 *spec, float *pad) { fft_ok(fft().ExecC2R((hipfftHandle)pl.inv, spec, pad), "hipfftExecC2R"), launches_++; }
+void Conditioner::crop(hipStream_t st, float *out, const float *pad, int nrec) { launch(k_crop, time_grid(nrec), st, nt_, nrec, out, pad, 1.0f / (float)(2 * nt_)); }
+
+// `multiply(grid over the bins, spec_)` launches the round trip's one kernel on the spectrum
+template <class M> void Conditioner::round_trip(hipStream_t st, const float *in, float *out, int nrec, M multiply) {
+    const Plans &pl = plans_for(nrec, st);
+    embed(st, in, pad_.get(), nrec);
+    forward(pl, pad_.get(), spec_.get());
+    multiply(spec_grid(nrec), spec_.get());
+    inverse(pl, spec_.get(), pad_.get());
+    crop(st, out, pad_.get(), nrec);
+}
+
+// bp_filter1d, utilities.cu:1115-1166
+void Conditioner::bandpass(hipStream_t st, float *data, int nrec, float dt, const float filt[4]) {
+    if (idle(nrec)) return;
+    const float df = (float)(1.0 / (double)dt / (double)(2 * nt_));
+    round_trip(st, data, data, nrec, [&](dim3 grid, float2 *spec) { launch(k_bp_filter, grid, st, nt_ + 1, nrec, df, filt[0], filt[1], filt[2], filt[3], spec); });
+}
+
+// H of the header
+void Conditioner::hilbert(hipStream_t st, const float *in, float *out, int nrec) {
+    if (idle(nrec)) return;
+    round_trip(st, in, out, nrec, [&](dim3 grid, float2 *spec) { launch(k_hilbert_mult, grid, st, nt_ + 1, nrec, spec); });
+}
+
 void Conditioner::ensure_source_buffers(hipStream_t st) {
     if (pad2_.get()) return;
     const size_t npad = 2 * (size_t)nt_, nf = (size_t)nt_ + 1;
@@ -381,63 +399,53 @@ void Conditioner::ensure_source_buffers(hipStream_t st) {
 
 // source_update, utilities.cu:1170-1281
 void Conditioner::source_update(hipStream_t st, const float *obs, float *syn, int nrec, float dt) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    if (idle(nrec)) return;
     ensure_source_buffers(st);
-    const int npad = 2 * nt_, nf = nt_ + 1;
-    Plans &pl = plans_for(nrec, st);
-    hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
-    const dim3 gpad((npad + 255) / 256, nrec), blk(256);
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, obs, pad_.get());
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)syn, pad2_.get());
-    // cuda_window over the PADDED length, ratio 0.01 (utilities.cu:1199-1202)
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_.get());
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad2_.get());
-    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
-    fft_ok(fft().ExecR2C(f, pad2_.get(), (hipfftComplex *)spec2_.get()), "hipfftExecR2C");
-    hipLaunchKernelGGL(k_matching_coef, dim3(nf), blk, 0, st, nf, nrec, (const hipfftComplex *)spec_.get(), (const hipfftComplex *)spec2_.get(), (hipfftComplex *)coef_.get());
-    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec2_.get(), (const hipfftComplex *)coef_.get(), 0);
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec2_.get(), pad2_.get()), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, syn, pad2_.get(), 1.0f / (float)npad);
+    const int nf = nt_ + 1;
+    const Plans &pl = plans_for(nrec, st);
+    embed(st, obs, pad_.get(), nrec);
+    embed(st, syn, pad2_.get(), nrec);
+    taper_padded(st, pad_.get(), nrec, dt);
+    taper_padded(st, pad2_.get(), nrec, dt);
+    forward(pl, pad_.get(), spec_.get());
+    forward(pl, pad2_.get(), spec2_.get());
+    launch(k_matching_coef, dim3(nf), st, nf, nrec, spec_.get(), spec2_.get(), coef_.get());
+    launch(k_apply_coef, spec_grid(nrec), st, nf, nrec, spec2_.get(), coef_.get(), 0);
+    inverse(pl, spec2_.get(), pad2_.get());
+    crop(st, syn, pad2_.get(), nrec);
 }
 
 void Conditioner::source_update_adj(hipStream_t st, float *res, int nrec, float dt) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    if (idle(nrec)) return;
     ensure_source_buffers(st);
-    const int npad = 2 * nt_, nf = nt_ + 1;
-    Plans &pl = plans_for(nrec, st);
-    hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
-    const dim3 gpad((npad + 255) / 256, nrec), blk(256);
-    hipLaunchKernelGGL(k_embed, gpad, blk, 0, st, nt_, nrec, (const float *)res, pad_.get());
-    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
-    hipLaunchKernelGGL(k_apply_coef, dim3((nf + 255) / 256, nrec), blk, 0, st, nf, nrec, (hipfftComplex *)spec_.get(), (const hipfftComplex *)coef_.get(), 1);
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_window, gpad, blk, 0, st, npad, nrec, dt, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 1.0f, 0.01f, pad_.get());
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), blk, 0, st, nt_, nrec, res, pad_.get(), 1.0f / (float)npad);
+    const Plans &pl = plans_for(nrec, st);
+    embed(st, res, pad_.get(), nrec);
+    forward(pl, pad_.get(), spec_.get());
+    launch(k_apply_coef, spec_grid(nrec), st, nt_ + 1, nrec, spec_.get(), coef_.get(), 1);
+    inverse(pl, spec_.get(), pad_.get());
+    taper_padded(st, pad_.get(), nrec, dt);
+    crop(st, res, pad_.get(), nrec);
 }
 
 void Conditioner::l2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc) {
-    if (nrec <= 0) return;
-    hipLaunchKernelGGL(k_l2_residual, dim3(nrec), dim3(256), 0, st, nt_, nrec, obs, syn, res, acc);
+    if (idle(nrec)) return;
+    launch(k_l2_residual, dim3(nrec), st, nt_, nrec, obs, syn, res, acc);
 }
 
 void Conditioner::scattered_residual(hipStream_t st, const float *d, float *res, int nrec, float sign) {
-    if (nrec <= 0) return;
-    hipLaunchKernelGGL(k_scattered_residual, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, d, res, sign);
+    if (idle(nrec)) return;
+    launch(k_scattered_residual, time_grid(nrec), st, nt_, nrec, d, res, sign);
 }
 
 void Conditioner::cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights,
                                  float src_weight, double *acc) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    if (idle(nrec)) return;
     double *n_oo = norm_.get(), *n_ss = n_oo + cap_, *n_os = n_oo + 2 * (size_t)cap_;
-    hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, obs, n_oo);
-    hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, syn, syn, n_ss);
-    hipLaunchKernelGGL(k_normfact, dim3(nrec), dim3(256), 0, st, nt_, obs, syn, n_os);
-    hipLaunchKernelGGL(k_cross_misfit, dim3(1), dim3(256), 0, st, nrec, n_os, n_oo, n_ss, weights, src_weight, acc);
-    hipLaunchKernelGGL(k_cross_adjoint, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, n_oo, n_ss, n_os, obs, syn, res, weights,
-                       src_weight);
+    launch(k_normfact, dim3(nrec), st, nt_, obs, obs, n_oo);
+    launch(k_normfact, dim3(nrec), st, nt_, syn, syn, n_ss);
+    launch(k_normfact, dim3(nrec), st, nt_, obs, syn, n_os);
+    launch(k_cross_misfit, dim3(1), st, nrec, n_os, n_oo, n_ss, weights, src_weight, acc);
+    launch(k_cross_adjoint, time_grid(nrec), st, nt_, nrec, n_oo, n_ss, n_os, obs, syn, res, weights, src_weight);
 }
 
 void Conditioner::ensure_envelope_buffers() {
@@ -446,48 +454,30 @@ void Conditioner::ensure_envelope_buffers() {
     env_sum_ = DevBuf<double>(&bytes_, (size_t)cap_);
 }
 
-// H of the header: pad, R2C, the multiplier, C2R, crop with 1 / (2 nt) -- the padding, plans and buffers of bandpass
-void Conditioner::hilbert(hipStream_t st, const float *in, float *out, int nrec) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
-    const int npad = 2 * nt_, nf = nt_ + 1;
-    Plans &pl = plans_for(nrec, st);
-    hipfftHandle f = (hipfftHandle)pl.fwd, b = (hipfftHandle)pl.inv;
-    hipLaunchKernelGGL(k_embed, dim3((npad + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, in, pad_.get());
-    fft_ok(fft().ExecR2C(f, pad_.get(), (hipfftComplex *)spec_.get()), "hipfftExecR2C");
-    hipLaunchKernelGGL(k_hilbert_mult, dim3((nf + 255) / 256, nrec), dim3(256), 0, st, nf, nrec, (hipfftComplex *)spec_.get());
-    fft_ok(fft().ExecC2R(b, (hipfftComplex *)spec_.get(), pad_.get()), "hipfftExecC2R");
-    hipLaunchKernelGGL(k_crop, dim3((nt_ + 255) / 256, nrec), dim3(256), 0, st, nt_, nrec, out, pad_.get(), 1.0f / (float)npad);
-}
-
 void Conditioner::envelope_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, double *acc) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    if (idle(nrec)) return;
     ensure_envelope_buffers();
     const size_t g = (size_t)nt_ * cap_;
     float *hd = env_.get(), *hs = hd + g, *b = hd + 2 * g;
-    const dim3 grid((nt_ + 255) / 256, nrec), blk(256);
-    hipLaunchKernelGGL(k_env_diff, grid, blk, 0, st, nt_, nrec, obs, syn, hd);
+    launch(k_env_diff, time_grid(nrec), st, nt_, nrec, obs, syn, hd);
     hilbert(st, hd, hd, nrec);  // H (obs - syn), in place (the transform reads its input into the padded buffer first)
     hilbert(st, syn, hs, nrec);
-    hipLaunchKernelGGL(k_env_residual, dim3(nrec), blk, 0, st, nt_, obs, (const float *)hd, syn, (const float *)hs, res, b, env_sum_.get());
-    hipLaunchKernelGGL(k_env_sum, dim3(1), blk, 0, st, nrec, (const double *)env_sum_.get(), acc);
+    launch(k_env_residual, dim3(nrec), st, nt_, obs, hd, syn, hs, res, b, env_sum_.get());
+    launch(k_env_sum, dim3(1), st, nrec, env_sum_.get(), acc);
     hilbert(st, b, b, nrec);
-    hipLaunchKernelGGL(k_env_combine, grid, blk, 0, st, nt_, nrec, res, (const float *)b, 1.0f);
+    launch(k_env_combine, time_grid(nrec), st, nt_, nrec, res, b, 1.0f);
 }
 
 void Conditioner::envelope_scattered(hipStream_t st, const float *syn, const float *d, float *res, int nrec, float sign) {
-    if (nrec <= 0) return;
-    if (nrec > cap_) throw std::invalid_argument("conditioning: more traces than the session was sized for");
+    if (idle(nrec)) return;
     ensure_envelope_buffers();
     const size_t g = (size_t)nt_ * cap_;
     float *hd = env_.get(), *hs = hd + g, *b = hd + 2 * g;
-    const dim3 grid((nt_ + 255) / 256, nrec), blk(256);
     hilbert(st, d, hd, nrec);
     hilbert(st, syn, hs, nrec);
-    hipLaunchKernelGGL(k_env_linear, grid, blk, 0, st, nt_, nrec, syn, (const float *)hs, d, (const float *)hd, res, b);
+    launch(k_env_linear, time_grid(nrec), st, nt_, nrec, syn, hs, d, hd, res, b);
     hilbert(st, b, b, nrec);
-    hipLaunchKernelGGL(k_env_combine, grid, blk, 0, st, nt_, nrec, res, (const float *)b, sign);
+    launch(k_env_combine, time_grid(nrec), st, nt_, nrec, res, b, sign);
 }
 
 }  // namespace sepfwi

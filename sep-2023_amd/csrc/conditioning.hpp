@@ -60,14 +60,40 @@ class Conditioner {
     // first use: a session whose file does not set the key never holds them
     void ensure_envelope_buffers();
     long long device_bytes() const { return bytes_; }  // what the buffers below hold
+    // What the methods above have issued so far: one per kernel launch and one per hipFFT exec (a plan's creation is none).  Per gather
+    // with channels:
+    //   window, l2_residual, scattered_residual   1
+    //   bandpass, hilbert                         5   embed, R2C, the spectrum's multiplier, C2R, crop
+    //   cross_residual                            5   three norms, misfit, adjoint source
+    //   source_update                            10   2 embeds, 2 tapers, 2 R2C, coefficients, their product, C2R, crop
+    //   source_update_adj                         6   embed, R2C, conj(coef), C2R, taper, crop
+    //   envelope_residual                        19   difference, 2 hilbert, residual, sum, hilbert, combination
+    //   envelope_scattered                       17   2 hilbert, linearised residual, hilbert, combination
+    long long launches() const { return launches_; }
 
   private:
     struct Plans {
         void *fwd, *inv;  // hipfftHandle
     };
     Plans &plans_for(int nrec, hipStream_t st);
+    // true: no traces, nothing to do.  Throws for a gather of more traces than the work space holds.
+    bool idle(int nrec) const;
+    template <class K, class... A> void launch(K kernel, dim3 grid, hipStream_t st, A... args);
+    dim3 time_grid(int nrec) const { return dim3((nt_ + 255) / 256, nrec); }      // one thread per sample of [nrec][nt]
+    dim3 pad_grid(int nrec) const { return dim3((2 * nt_ + 255) / 256, nrec); }   // ... of the padded [nrec][2 nt]
+    dim3 spec_grid(int nrec) const { return dim3((nt_ + 1 + 255) / 256, nrec); }  // ... per bin of the spectra [nrec][nt + 1]
+    // The spectral round trip of bandpass and hilbert: `in` zero-padded to 2 nt in pad_, R2C into spec_, `multiply` on the spectrum, C2R,
+    // crop with the 1 / (2 nt) of the unnormalised inverse transform into `out` (in == out is allowed: `in` is read into pad_ first).
+    template <class M> void round_trip(hipStream_t st, const float *in, float *out, int nrec, M multiply);
+    // Its steps; the source update composes them itself (two gathers, pad_ / spec_ and pad2_ / spec2_, and the end taper of the padded
+    // length, ratio 0.01).  `pl` is plans_for(nrec, st) of the same call.
+    void embed(hipStream_t st, const float *in, float *pad, int nrec);
+    void taper_padded(hipStream_t st, float *pad, int nrec, float dt);
+    void forward(const Plans &pl, float *pad, float2 *spec);
+    void inverse(const Plans &pl, float2 *spec, float *pad);
+    void crop(hipStream_t st, float *out, const float *pad, int nrec);
     int nt_, cap_;
-    long long bytes_ = 0;
+    long long bytes_ = 0, launches_ = 0;
     DevBuf<float> pad_, pad2_;
     DevBuf<double> norm_;          // the three per-trace norms of the cross-correlation misfit, 3 x [cap]
     DevBuf<float2> spec_;          // hipfftComplex [cap][nt + 1]

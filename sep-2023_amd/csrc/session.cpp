@@ -295,58 +295,6 @@ void Session::misfit_parts(double parts[3]) {
     for (int k = 0; k < 3; k++) parts[k] = parts_[k];
 }
 
-// Window and band-pass one [rec][it] gather in place, as the commented driver lines apply them to observed and synthetic
-// data alike (libCUFD.cu:353-374): per-channel windows with weights when if_win, else the plain end taper; then the filter.
-void Session::condition_gather(hipStream_t st, float *gather, int shot_id, int nrec) {
-    const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
-    const Shot &sh = survey_.shots[shot_id];
-    if (par_.if_win)
-        cond_->window(st, gather, nrec, par_.dt, win_ + off, win_ + tot + off, win_ + 2 * tot + off, sh.src_weight, 0.005f);
-    else
-        cond_->window(st, gather, nrec, par_.dt, nullptr, nullptr, nullptr, 1.0f, 0.005f);
-    if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
-}
-
-// Its transpose, as the commented lines apply it to the residual (libCUFD.cu:436-457): the (zero-phase, symmetric) filter, then the
-// (pointwise) window.
-void Session::condition_gather_t(hipStream_t st, float *gather, int shot_id, int nrec) {
-    const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
-    const Shot &sh = survey_.shots[shot_id];
-    if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
-    if (par_.if_win)
-        cond_->window(st, gather, nrec, par_.dt, win_ + off, win_ + tot + off, win_ + 2 * tot + off, sh.src_weight, 0.005f);
-    else
-        cond_->window(st, gather, nrec, par_.dt, nullptr, nullptr, nullptr, 1.0f, 0.005f);
-}
-
-// sepfwi_condition: C or C^T of the parameter file on the caller's gathers, [nrec_i][nSteps] shot after shot, in place.  A gather on
-// this device is conditioned where it lies, any other one in the session's scratch gather.  Neither the observed store nor the
-// statistics of the last call are touched.
-void Session::condition(float *data, bool transpose, int group_size, const int *shot_ids, hipStream_t ext_stream) {
-    std::lock_guard<std::mutex> lock(mu_);
-    check_shot_ids(group_size, shot_ids);
-    if (!cond_on_) return;  // the identity
-    HIP_OK(hipSetDevice(gpu_id_));
-    hipStream_t st = ext_stream ? ext_stream : own_stream_.get();
-    if (!ext_stream) order_after_null_stream(st);
-    size_t off = 0;
-    for (int is = 0; is < group_size; is++) {
-        const int id = shot_ids[is], nrec = survey_.shots[id].nrec;
-        const size_t cnt = (size_t)nrec * par_.nSteps;
-        if (cnt == 0) continue;
-        float *g = data + off;
-        const bool staged = ptr_device(g) != gpu_id_;
-        if (staged) {
-            HIP_OK(hipMemcpyAsync(xpose_, g, cnt * sizeof(float), hipMemcpyDefault, st));
-            g = xpose_;
-        }
-        transpose ? condition_gather_t(st, g, id, nrec) : condition_gather(st, g, id, nrec);
-        if (staged) HIP_OK(hipMemcpyAsync(data + off, xpose_, cnt * sizeof(float), hipMemcpyDefault, st));
-        off += cnt;
-    }
-    HIP_OK(hipStreamSynchronize(st));
-}
-
 // Test hook (sepfwi_debug_field): one wavefield of one forward lane as the last call left it, dense (nzc, nx).
 void Session::copy_field(int lane, int which, float *out) {
     std::lock_guard<std::mutex> lock(mu_);

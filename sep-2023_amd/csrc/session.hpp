@@ -87,10 +87,26 @@ class Session {
     void ensure_lanes(int n_lanes, bool with_frames);
     void ensure_batch(int n_fwd, int n_bwd, bool with_frames, int n_shots);
     void order_after_null_stream(hipStream_t st);
-    // C of the parameter file on one [rec][it] gather in place: window (if_win: per channel, with weights; else the end taper), then
-    // band-pass (filter); and C^T: band-pass, then window
-    void condition_gather(hipStream_t st, float *gather_rec_major, int shot_id, int nrec);
-    void condition_gather_t(hipStream_t st, float *gather_rec_major, int shot_id, int nrec);
+    // ---- the data-conditioning chain (session_data.cpp), on [rec][it] gathers of one shot ---------------------------------------
+    // C of the parameter file on one gather in place: window (if_win: per channel, with weights; else the end taper), then band-pass
+    // (filter); and C^T: band-pass, then window
+    void window_gather(hipStream_t st, float *gather, int shot_id, int nrec);
+    void condition_gather(hipStream_t st, float *gather, int shot_id, int nrec);
+    void condition_gather_t(hipStream_t st, float *gather, int shot_id, int nrec);
+    // What a call runs between its two transpositions, and the data-space entry points on a caller's gathers.
+    //   misfit_chain  obs_c: the shot's CONDITIONED observed gather, only read.  syn: the raw synthetic gather, conditioned (under
+    //                 if_src_update also updated) in place.  out: the raw-space adjoint source.  The misfit's sum is added to *acc.
+    //   gn_chain      d: the raw gather, conditioned in place.  bg: the raw background gather, conditioned in place, under
+    //                 if_envelope_misfit; else null.  out = sign C^T Z C d, or sign C^T D^T Z D C d.
+    // ALIASING: the gathers of one call are all different (the envelope kernels read the other two while they write out).  The callers
+    // pass the session's scratch gathers xpose_, xpose2_, xpose3_.
+    void misfit_chain(hipStream_t st, const float *obs_c, float *syn, float *out, int shot_id, int nrec, double *acc);
+    void gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign);
+    void ensure_data_scratch();  // xpose3_ / data_acc_
+    // prologue and shot loop of condition / data_misfit / data_gn: this device and the caller's stream, or the session's own ordered after
+    // the null stream; f(shot id, nrec, offset in the caller's arrays, length) for every shot with channels
+    hipStream_t data_stream(hipStream_t ext_stream);
+    template <class F> void for_each_gather(int group_size, const int *shot_ids, F f);
 
     // ---- one cufd call (run): its state and its passes -------------------------------------------------------------------
     struct Call {  // what every pass of one call shares; ONE snapshot of the kernel options
@@ -187,12 +203,8 @@ class Session {
     void residual(const ShotCtx &x);
     GeoResShot geo_res_shot(const ShotCtx &x) const;  // joint misfit: what the residual kernel needs of one shot (geophone.hpp)
     void residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int nb);
-    void residual_conditioned(const Call &c, const ShotCtx &x);
+    void residual_conditioned(const Call &c, const ShotCtx &x);        // session_data.cpp: the same through the conditioning chain
     void adjoint_source_conditioned(const Call &c, const ShotCtx &x);  // -C^T Z C (J v) from the shot's scattered gather (if_win / filter)
-    // what the two run between their transpositions, on the scratch gathers (session_run.cpp); the data-space entry points run them too
-    void misfit_chain(hipStream_t st, const float *d_obs, int shot_id, int nrec, double *acc);
-    void gn_chain(hipStream_t st, int shot_id, int nrec, float sign);
-    void ensure_data_scratch();  // xpose3_ / data_acc_
     // what a forward pass leaves behind, by kind of call
     void after_forward(Call &c, const ShotCtx &x);
     void export_gathers(const Call &c, const ShotCtx &x);

@@ -1,8 +1,15 @@
-// session_data.cpp -- Session::data_misfit / data_gn: the misfit of the parameter file as an operator on gathers (sepfwi_data_misfit,
-// sepfwi_data_gn), with no wave propagation.
+// session_data.cpp -- the data-conditioning chain of the misfit as the session composes it, and every way into it.
 //
-// Both take RAW axial-strain gathers, [nrec_i][nSteps] shot after shot like born()'s d_ett, host or device, and run them through the code a
-// gradient call or a Gauss-Newton product runs between its two transpositions (Session::misfit_chain, Session::gn_chain):
+// The Conditioner (conditioning.hip) owns the kernels, the FFT work space and the count of what it issues; the session owns the [rec][it]
+// scratch gathers xpose_, xpose2_, xpose3_ (one shot each: the chain runs on the call's MAIN stream, shot after shot) and the order of the
+// stages, that of the reference's commented lines (libCUFD.cu:353-457): C = band-pass . window (condition_gather), C^T
+// (condition_gather_t), and the two middles misfit_chain and gn_chain (session.hpp).  Inside a call the middles run between two
+// transpositions of the shot's time-major gathers: residual_conditioned (run, adjoint_exact) and adjoint_source_conditioned (born); these
+// charge their transpositions and what the Conditioner counted across the chain to sepfwi_stats.launches.  (The observed store conditions a
+// gather when it is installed, obs_store.cpp: that is charged to no call.)
+//
+// The entry points take RAW axial-strain gathers, [nrec_i][nSteps] shot after shot like born()'s d_ett, host or device, with no propagation:
+//   condition     sepfwi_condition: C or C^T in place
 //   data_misfit   the file's misfit of (obs, syn) and the raw-space adjoint source a = -d misfit / d syn: C^T Z (C obs - C syn) under an L2
 //                 file, the adjoint source of the normalised cross-correlation under if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under
 //                 if_envelope_misfit.  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
@@ -23,33 +30,144 @@
 
 namespace sepfwi {
 
+// the window stage of a shot (libCUFD.cu:353-374)
+void Session::window_gather(hipStream_t st, float *gather, int shot_id, int nrec) {
+    const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
+    const float *w = par_.if_win ? win_ + off : nullptr;  // [start | end | weight] per channel
+    cond_->window(st, gather, nrec, par_.dt, w, w ? w + tot : nullptr, w ? w + 2 * tot : nullptr, w ? survey_.shots[shot_id].src_weight : 1.0f, 0.005f);
+}
+
+// Window and band-pass one [rec][it] gather in place, as the commented driver lines apply them to observed and synthetic
+// data alike (libCUFD.cu:353-374)
+void Session::condition_gather(hipStream_t st, float *gather, int shot_id, int nrec) {
+    window_gather(st, gather, shot_id, nrec);
+    if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
+}
+
+// Its transpose, as the commented lines apply it to the residual (libCUFD.cu:436-457): the (zero-phase, symmetric) filter, then the
+// (pointwise) window.
+void Session::condition_gather_t(hipStream_t st, float *gather, int shot_id, int nrec) {
+    if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
+    window_gather(st, gather, shot_id, nrec);
+}
+
+void Session::misfit_chain(hipStream_t st, const float *obs_c, float *syn, float *out, int shot_id, int nrec, double *acc) {
+    const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
+    const Shot &sh = survey_.shots[shot_id];
+    condition_gather(st, syn, shot_id, nrec);
+    if (par_.if_src_update) cond_->source_update(st, obs_c, syn, nrec, par_.dt);  // libCUFD.cu:383-390
+    if (par_.if_cross_misfit)  // the trace weights belong to if_win, as the window's do: without the key w_r = 1 (oracle.conditioned_residual)
+        cond_->cross_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
+    else if (par_.if_envelope_misfit)
+        cond_->envelope_residual(st, obs_c, syn, out, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
+    else
+        cond_->l2_residual(st, obs_c, syn, out, nrec, acc);
+    if (par_.if_src_update) cond_->source_update_adj(st, out, nrec, par_.dt);  // libCUFD.cu:430-433
+    condition_gather_t(st, out, shot_id, nrec);
+}
+
+void Session::gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign) {
+    condition_gather(st, d, shot_id, nrec);
+    if (par_.if_envelope_misfit) {
+        condition_gather(st, bg, shot_id, nrec);
+        cond_->envelope_scattered(st, bg, d, out, nrec, sign);
+    } else {
+        cond_->scattered_residual(st, d, out, nrec, sign);
+    }
+    condition_gather_t(st, out, shot_id, nrec);
+}
+
+// residual + misfit of the axial-strain component with the chain (libCUFD.cu:353-457 as its commented lines compose it)
+void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
+    if (x.nrec <= 0) return;
+    hipStream_t st = c.st;
+    const int nSteps = par_.nSteps;
+    const long long before = cond_->launches();
+    launch_transpose(st, syn_of(x, 3), xpose_, nSteps, x.nrec);  // [it][rec] -> [rec][it]
+    misfit_chain(st, x.d_obs, xpose_, xpose2_, x.id, x.nrec, scal_);
+    launch_transpose(st, xpose2_, x.res, x.nrec, nSteps);  // [rec][it] -> [it][rec]: the adjoint source
+    cs_.launches += 2 + (cond_->launches() - before);
+}
+
+// The adjoint source of a Gauss-Newton product under a file whose live conditioning keys are if_win / filter: from the shot's
+// scattered axial-strain gather d = J v (time-major, where the samplers left it) the residual buffer gets -C^T Z C d -- what
+// residual_conditioned leaves for observed data syn - J v, and the sign k_adjoint_source leaves.  Z (sample 0 zeroed) and the sign
+// are one kernel, in the place of the residual kernel; no misfit, no observed data.
+// Under if_envelope_misfit the buffer gets -C^T D^T Z D C d, D the derivative of the squared envelope at C of the shot's BACKGROUND
+// gather, which Session::born recorded time-major in born_bg_.
+void Session::adjoint_source_conditioned(const Call &c, const ShotCtx &x) {
+    if (x.nrec <= 0) return;
+    hipStream_t st = c.st;
+    const bool env = par_.if_envelope_misfit;
+    const long long before = cond_->launches();
+    if (env) launch_transpose(st, born_bg_.get(), xpose3_.get(), par_.nSteps, x.nrec);
+    launch_transpose(st, syn_of(x, 3), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
+    gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, x.id, x.nrec, -1.0f);
+    launch_transpose(st, xpose2_, x.res, x.nrec, par_.nSteps);  // [rec][it] -> [it][rec]
+    cs_.launches += (env ? 3 : 2) + (cond_->launches() - before);
+}
+
 // the third [rec][it] scratch gather and the sum of the data-space entry points (and of the envelope product of Session::born)
 void Session::ensure_data_scratch() {
     if (!xpose3_) xpose3_ = dev<float>(data_len_);
     if (!data_acc_) data_acc_ = dev<double>(1);
 }
 
+// ---- the entry points on the caller's gathers: each holds the lock and makes its refusals first ----
+hipStream_t Session::data_stream(hipStream_t ext_stream) {
+    HIP_OK(hipSetDevice(gpu_id_));
+    hipStream_t st = ext_stream ? ext_stream : own_stream_.get();
+    if (!ext_stream) order_after_null_stream(st);
+    return st;
+}
+
+// f(shot id, nrec, offset of the shot's gather in the caller's arrays, its length), shots without channels skipped
+template <class F> void Session::for_each_gather(int group_size, const int *shot_ids, F f) {
+    size_t off = 0;
+    for (int is = 0; is < group_size; is++) {
+        const int id = shot_ids[is], nrec = survey_.shots[id].nrec;
+        const size_t cnt = (size_t)nrec * par_.nSteps;
+        if (cnt == 0) continue;
+        f(id, nrec, off, cnt);
+        off += cnt;
+    }
+}
+
+// A gather on this device is conditioned where it lies, any other one in the session's scratch gather.
+void Session::condition(float *data, bool transpose, int group_size, const int *shot_ids, hipStream_t ext_stream) {
+    std::lock_guard<std::mutex> lock(mu_);
+    check_shot_ids(group_size, shot_ids);
+    if (!cond_on_) return;  // the identity
+    hipStream_t st = data_stream(ext_stream);
+    for_each_gather(group_size, shot_ids, [&](int id, int nrec, size_t off, size_t cnt) {
+        float *g = data + off;
+        const bool staged = ptr_device(g) != gpu_id_;
+        if (staged) {
+            HIP_OK(hipMemcpyAsync(xpose_, g, cnt * sizeof(float), hipMemcpyDefault, st));
+            g = xpose_;
+        }
+        transpose ? condition_gather_t(st, g, id, nrec) : condition_gather(st, g, id, nrec);
+        if (staged) HIP_OK(hipMemcpyAsync(data + off, xpose_, cnt * sizeof(float), hipMemcpyDefault, st));
+    });
+    HIP_OK(hipStreamSynchronize(st));
+}
+
 void Session::data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int group_size, const int *shot_ids, hipStream_t ext_stream) {
     std::lock_guard<std::mutex> lock(mu_);
     if (joint_) throw std::invalid_argument("data_misfit: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);
-    HIP_OK(hipSetDevice(gpu_id_));
-    hipStream_t st = ext_stream ? ext_stream : own_stream_.get();
-    if (!ext_stream) order_after_null_stream(st);
+    hipStream_t st = data_stream(ext_stream);
     ensure_data_scratch();
     double *acc = data_acc_.get();
     HIP_OK(hipMemsetAsync(acc, 0, sizeof(double), st));
     const int nSteps = par_.nSteps;
-    size_t off = 0;
-    for (int is = 0; is < group_size; is++) {
-        const int id = shot_ids[is], nrec = survey_.shots[id].nrec;
-        const size_t cnt = (size_t)nrec * nSteps, bytes = cnt * sizeof(float);
-        if (cnt == 0) continue;
+    for_each_gather(group_size, shot_ids, [&](int id, int nrec, size_t off, size_t cnt) {
+        const size_t bytes = cnt * sizeof(float);
         if (cond_on_) {  // the observed gather is kept conditioned (obs_store.cpp): C obs, then the chain on the raw synthetic gather
             HIP_OK(hipMemcpyAsync(xpose3_.get(), obs + off, bytes, hipMemcpyDefault, st));
             condition_gather(st, xpose3_.get(), id, nrec);
             HIP_OK(hipMemcpyAsync(xpose_, syn + off, bytes, hipMemcpyDefault, st));
-            misfit_chain(st, xpose3_.get(), id, nrec, acc);
+            misfit_chain(st, xpose3_.get(), xpose_, xpose2_, id, nrec, acc);
             if (adj) HIP_OK(hipMemcpyAsync(adj + off, xpose2_, bytes, hipMemcpyDefault, st));
         } else {  // the plain residual kernel of a gradient call, on time-major gathers: lane 0's gather and residual buffers
             float *t_obs = syn_, *t_syn = syn_ + data_len_;
@@ -61,8 +179,7 @@ void Session::data_misfit(float *misfit, float *adj, const float *obs, const flo
             launch_transpose(st, res_, xpose_, nSteps, nrec);  // [it][rec] -> [rec][it]
             if (adj) HIP_OK(hipMemcpyAsync(adj + off, xpose_, bytes, hipMemcpyDefault, st));
         }
-        off += cnt;
-    }
+    });
     double sum = 0.0;
     HIP_OK(hipMemcpyAsync(&sum, acc, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -77,27 +194,21 @@ void Session::data_gn(float *out, const float *syn, const float *d, int group_si
                                     " (not a least-squares misfit of the data); if_win, filter and if_envelope_misfit are served");
     if (joint_) throw std::invalid_argument("data_gn: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);
-    HIP_OK(hipSetDevice(gpu_id_));
-    hipStream_t st = ext_stream ? ext_stream : own_stream_.get();
-    if (!ext_stream) order_after_null_stream(st);
-    if (par_.if_envelope_misfit) ensure_data_scratch();
-    const int nSteps = par_.nSteps;
-    size_t off = 0;
-    for (int is = 0; is < group_size; is++) {
-        const int id = shot_ids[is], nrec = survey_.shots[id].nrec;
-        const size_t cnt = (size_t)nrec * nSteps, bytes = cnt * sizeof(float);
-        if (cnt == 0) continue;
+    hipStream_t st = data_stream(ext_stream);
+    const bool env = par_.if_envelope_misfit;
+    if (env) ensure_data_scratch();
+    for_each_gather(group_size, shot_ids, [&](int id, int nrec, size_t off, size_t cnt) {
+        const size_t bytes = cnt * sizeof(float);
         HIP_OK(hipMemcpyAsync(xpose_, d + off, bytes, hipMemcpyDefault, st));
         if (cond_on_) {
-            if (par_.if_envelope_misfit) HIP_OK(hipMemcpyAsync(xpose3_.get(), syn + off, bytes, hipMemcpyDefault, st));
-            gn_chain(st, id, nrec, 1.0f);
+            if (env) HIP_OK(hipMemcpyAsync(xpose3_.get(), syn + off, bytes, hipMemcpyDefault, st));
+            gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, id, nrec, 1.0f);
             HIP_OK(hipMemcpyAsync(out + off, xpose2_, bytes, hipMemcpyDefault, st));
         } else {  // Z alone: sample 0 of every trace zeroed
-            HIP_OK(hipMemset2DAsync(xpose_, (size_t)nSteps * sizeof(float), 0, sizeof(float), (size_t)nrec, st));
+            HIP_OK(hipMemset2DAsync(xpose_, (size_t)par_.nSteps * sizeof(float), 0, sizeof(float), (size_t)nrec, st));
             HIP_OK(hipMemcpyAsync(out + off, xpose_, bytes, hipMemcpyDefault, st));
         }
-        off += cnt;
-    }
+    });
     HIP_OK(hipStreamSynchronize(st));
 }
 

@@ -1,6 +1,7 @@
 // session_run.cpp -- Session::run, the cufd call (Src/libCUFD.cu:170-724), split into its passes:
 //   prepare_media / prepare_buffers     set-up of one call (libCUFD.cu:39-165, the part that is not kept between calls)
-//   forward_*  / residual*              forward time loop of one shot and its misfit (libCUFD.cu:268-332, 410-427)
+//   forward_*  / residual*              forward time loop of one shot and its misfit (libCUFD.cu:268-332, 410-427); the misfit under a
+//                                       data-conditioning key, residual_conditioned: session_data.cpp
 //   after_forward                       seismogram files / HBM store / scratch dumps (libCUFD.cu:732-769)
 //   backward_* / backward               boundary-saving adjoint time loop of one shot (libCUFD.cu:500-675); as one persistent launch:
 //                                       session_persist.cpp
@@ -233,69 +234,6 @@ void Session::residual_batch(const Call &c, const std::vector<ShotCtx> &cx, int 
     HIP_OK(hipMemcpyAsync(d_geo_res_.get(), geo_res_tab_.data(), (size_t)nb * sizeof(GeoResShot), hipMemcpyHostToDevice, c.st));
     launch_geo_residual_batch(c.st, d_geo_res_.get(), nb, max_nrec, geo_ncomp_, par_.nSteps, geo_sums_);
     cs_.launches++;
-}
-
-// the same with the data-conditioning chain (libCUFD.cu:353-457 as its commented lines compose it), on the MAIN stream:
-// the scratch gathers and the FFT work space are shared by the shots of a call
-void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
-    if (x.nrec <= 0) return;
-    hipStream_t st = c.st;
-    const int nSteps = par_.nSteps;
-    launch_transpose(st, syn_of(x, 3), xpose_, nSteps, x.nrec);  // [it][rec] -> [rec][it]
-    misfit_chain(st, x.d_obs, x.id, x.nrec, scal_);
-    launch_transpose(st, xpose2_, x.res, x.nrec, nSteps);  // [rec][it] -> [it][rec]: the adjoint source
-    cs_.launches += 8;
-    if (par_.if_envelope_misfit) cs_.launches += 18;  // the data residual, three Hilbert transforms of five launches each, residual, sum, combination -- for the one of l2_residual
-}
-
-// The middle of it, between the two transpositions: the raw [rec][it] synthetic gather in xpose_ and the shot's CONDITIONED observed gather
-// -> the raw-space adjoint source in xpose2_, the misfit's sum added to *acc.  (sepfwi_data_misfit runs it on a caller's gathers.)
-void Session::misfit_chain(hipStream_t st, const float *d_obs, int shot_id, int nrec, double *acc) {
-    const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
-    const Shot &sh = survey_.shots[shot_id];
-    condition_gather(st, xpose_, shot_id, nrec);
-    if (par_.if_src_update) cond_->source_update(st, d_obs, xpose_, nrec, par_.dt);  // libCUFD.cu:383-390
-    if (par_.if_cross_misfit)  // the trace weights belong to if_win, as the window's do: without the key w_r = 1 (oracle.conditioned_residual)
-        cond_->cross_residual(st, d_obs, xpose_, xpose2_, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
-    else if (par_.if_envelope_misfit)
-        cond_->envelope_residual(st, d_obs, xpose_, xpose2_, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
-    else
-        cond_->l2_residual(st, d_obs, xpose_, xpose2_, nrec, acc);
-    if (par_.if_src_update) cond_->source_update_adj(st, xpose2_, nrec, par_.dt);  // libCUFD.cu:430-433
-    condition_gather_t(st, xpose2_, shot_id, nrec);
-}
-
-// The adjoint source of a Gauss-Newton product under a file whose live conditioning keys are if_win / filter: from the shot's
-// scattered axial-strain gather d = J v (time-major, where the samplers left it) the residual buffer gets -C^T Z C d -- what
-// residual_conditioned leaves for observed data syn - J v, and the sign k_adjoint_source leaves.  Z (sample 0 zeroed) and the sign
-// are one kernel, in the place of the residual kernel; no misfit, no observed data.
-// Under if_envelope_misfit the buffer gets -C^T D^T Z D C d, D the derivative of the squared envelope at C of the shot's BACKGROUND
-// gather, which Session::born recorded time-major in born_bg_.
-void Session::adjoint_source_conditioned(const Call &c, const ShotCtx &x) {
-    if (x.nrec <= 0) return;
-    hipStream_t st = c.st;
-    if (par_.if_envelope_misfit) {
-        launch_transpose(st, born_bg_.get(), xpose3_.get(), par_.nSteps, x.nrec);
-        // the transposition and C of the background; three Hilbert transforms, the linearised residual, the combination -- for one kernel
-        cs_.launches += 2 + (par_.has_filter ? 5 : 0) + 17;
-    }
-    launch_transpose(st, syn_of(x, 3), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
-    gn_chain(st, x.id, x.nrec, -1.0f);
-    launch_transpose(st, xpose2_, x.res, x.nrec, par_.nSteps);  // [rec][it] -> [it][rec]
-    cs_.launches += 8;
-}
-
-// Its middle: the raw [rec][it] gather d in xpose_ (under if_envelope_misfit also the raw background gather in xpose3_) -> xpose2_ =
-// sign C^T Z C d, or sign C^T D^T Z D C d.  (sepfwi_data_gn runs it with sign = 1.)
-void Session::gn_chain(hipStream_t st, int shot_id, int nrec, float sign) {
-    condition_gather(st, xpose_, shot_id, nrec);
-    if (par_.if_envelope_misfit) {
-        condition_gather(st, xpose3_.get(), shot_id, nrec);
-        cond_->envelope_scattered(st, xpose3_.get(), xpose_, xpose2_, nrec, sign);
-    } else {
-        cond_->scattered_residual(st, xpose_, xpose2_, nrec, sign);
-    }
-    condition_gather_t(st, xpose2_, shot_id, nrec);
 }
 
 // ---- what a forward pass leaves behind -----------------------------------------------------------------------------------
