@@ -7,6 +7,7 @@ import changed: `from sepfwi import ...` instead of the reference's `FWI_ops` / 
     python examples/fwi_anomaly_vp_vs_den.py --niter 10 --device cuda   # every tensor of the iteration in HBM
     torchrun --nproc-per-node 8 examples/fwi_anomaly_vp_vs_den.py       # shots sharded over 8 GPUs, one all-reduce
     python examples/fwi_anomaly_vp_vs_den.py --device cuda --precond 1e-3   # L-BFGS-B on variables scaled by the pseudo-Hessian
+    python examples/fwi_anomaly_vp_vs_den.py --device cuda --smooth 60      # L-BFGS in y, the model p_ref + s S y, S a 60 m Gaussian
 
 Model files of the reference are replaced by their analytic definition (homogeneous + three 16x16-cell boxes).
 The printed iterate-0 misfit is the reference's own 1.51116e4 (tests/golden/known_answers.json)."""
@@ -55,7 +56,11 @@ def main():
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--precond", type=float, default=None, metavar="EPS",
                     help="scale the variables by (H + EPS max H)^(-1/2), H the diagonal pseudo-Hessian of the start model (default: off)")
+    ap.add_argument("--smooth", type=float, default=None, metavar="METRES",
+                    help="invert in the smoothed variables y, the model p_ref + s S y with S a Gaussian of this width (sepfwi.smooth; no bounds) (default: off)")
     a = ap.parse_args()
+    if a.smooth is not None and a.precond is not None:
+        ap.error("--precond scales the model variables, --smooth replaces them: use one")
     if "RANK" in os.environ:   # one process per GPU
         import torch.distributed as td
         torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
@@ -101,7 +106,11 @@ def main():
     # ---- inversion: Main-001-...py:112-168
     T = lambda m: torch.tensor(m, dtype=torch.float32, device=dev, requires_grad=True)
     fwi = M.FWI(T(vp0), T(vs0), T(rho0), Stf, opt, Mask=torch.tensor(Mask, device=dev))
-    obj = PyTorchObjective(fwi, lambda: fwi(Shot_ids, ngpu=a.ngpu))
+    if a.smooth is not None:
+        from sepfwi.smooth import Smoother
+        obj = PyTorchObjective(fwi, lambda: fwi(Shot_ids, ngpu=a.ngpu), smoother=Smoother(fwi, a.smooth, a.smooth))
+    else:
+        obj = PyTorchObjective(fwi, lambda: fwi(Shot_ids, ngpu=a.ngpu))
     fun, jac = obj.fun, obj.jac   # bound methods (cache() later shadows .jac with the array, as in the reference)
     hist = [fun(obj.x0)]
     if rank == 0:
@@ -123,7 +132,11 @@ def main():
                                 options={"gtol": 1e-16, "maxiter": a.niter, "ftol": 1e-12, "maxcor": 5, "maxfun": 1500, "maxls": 6})
     if rank == 0:
         n = nz * nx
-        dvp = res.x[:n].reshape(nz, nx) - vp0
+        if a.smooth is not None:      # res.x is y: the model is the module's, loaded at y
+            obj.load(res.x)
+            dvp = fwi.Vp.detach().cpu().numpy() - vp0
+        else:
+            dvp = res.x[:n].reshape(nz, nx) - vp0
         print("done: %d evaluations, misfit %.4e -> %.4e; recovered Vp anomaly peak %.1f m/s (true 80)" %
               (res.nfev, hist[0], hist[-1], dvp[42:58, 42:58].max()))
     if fdist.active():

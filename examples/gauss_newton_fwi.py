@@ -11,6 +11,7 @@ Gauss-Newton curvature -- as damping matrix and preconditioner, and takes a back
     python examples/gauss_newton_fwi.py --device cuda --outer 2 --inner 3 --nsteps 600 --shot-stride 3
     python examples/gauss_newton_fwi.py --device cuda --param vp_vs_den --exact-adjoint
     python examples/gauss_newton_fwi.py --device cuda --param vp_vs_den --exact-adjoint --tikhonov 1e3 --tv 10
+    python examples/gauss_newton_fwi.py --device cuda --exact-adjoint --smooth-precond 0.5
 
 With --param vp_vs_den the gradient is module(ids).backward(), D is module.diag(pseudo-Hessian) and the product is module.gauss_newton
 (P^T J^T J P v with P the tangent of the parameter chain); calibration, CG and backtracking are the same.
@@ -18,6 +19,10 @@ With --param vp_vs_den the gradient is module(ids).backward(), D is module.diag(
 With --tikhonov BETA, --tv GAMMA or --prior ALPHA (--param vp_vs_den; all 0 by default, the run without them) the objective gains the model
 term R of sepfwi.regularize.Regularizer on the three fields -- first-order Tikhonov, smoothed total variation, damping towards the starting
 model: the gradient carries its gradient, the CG operator its exact Hessian-vector product, the backtracking its value.
+
+With --smooth-precond FRACTION the inner CG is preconditioned by D^-1/2 S S^T D^-1/2 instead of the Jacobi D^-1 (D still damps): S is
+sepfwi.smooth.Smoother.from_wavelength with sigma = FRACTION vs / fmax, fmax = 2.5 f0 the top of the Ricker band -- an update cannot
+resolve less than a share of the shortest wavelength, so the preconditioner does not let CG spend its few iterations there.
 
 Prints the CG residual of every inner iteration and the misfit of every outer one (with a model term: the data misfit and R separately)."""
 import argparse
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--tikhonov", type=float, default=0.0, metavar="BETA", help="weight of the first-order Tikhonov term of the three fields (--param vp_vs_den)")
     ap.add_argument("--tv", type=float, default=0.0, metavar="GAMMA", help="weight of the smoothed total-variation term (--param vp_vs_den)")
     ap.add_argument("--prior", type=float, default=0.0, metavar="ALPHA", help="weight of the damping towards the starting model (--param vp_vs_den)")
+    ap.add_argument("--smooth-precond", type=float, default=None, metavar="FRACTION",
+                    help="precondition the inner CG with D^-1/2 S S^T D^-1/2, S a Gaussian of width FRACTION vs / fmax (default: the Jacobi D^-1)")
     a = ap.parse_args()
     regularised = a.tikhonov > 0 or a.tv > 0 or a.prior > 0
     if regularised and a.param != "vp_vs_den":
@@ -142,6 +149,12 @@ def main():
             return float(out[0]), [Mask * t for t in out[1:4]], [Mask * t for t in out[5:8]]
         misfit = lambda mm: float(fwi_ops.forward(*mm, Stf, 0, ids, para_fname)[0])
         product = lambda mm, v: [Mask * t for t in fwi_ops.gauss_newton(*mm, *[Mask * x for x in v], Stf, 1, ids, para_fname, exact=a.exact_adjoint)]
+    smoother = None
+    if a.smooth_precond is not None:
+        from sepfwi.smooth import Smoother
+        vs_start = torch.tensor(vs0 if a.param == "vp_vs_den" else ft.padding_numpy_array(vs0, nPml, nPad))
+        smoother = Smoother.from_wavelength(fwi if a.param == "vp_vs_den" else tuple(m[0].shape), vs_start, fmax=2.5 * f0, fraction=a.smooth_precond, dx=dx, dz=dz)
+        print("smoothing preconditioner: sigma %.2f .. %.2f cells, radii %s" % (float(smoother.sigma[0].min()), float(smoother.sigma[0].max()), smoother.radius), flush=True)
     f0_ = None
     for k in range(a.outer):
         f, g, D = gradient(m)
@@ -167,7 +180,11 @@ def main():
                 D[j] = D[j] + (reg.alpha[n] / s_n ** 2 + (reg.beta[n] + reg.gamma[n] / reg.eps) * (2.0 / (s_n * reg.dx) ** 2 + 2.0 / (s_n * reg.dz) ** 2))
         hv = lambda v: product(m, v)
         lam = a.damping
-        p, hist = gauss_newton_cg(hv, g, damping=lam, diag=D, maxiter=a.inner, rtol=a.rtol,
+        precond = None
+        if smoother is not None:      # (W keeps the preconditioned residual inside the inverted region, as the products are)
+            inner = smoother.preconditioner(D)
+            precond = lambda r: [w * t for w, t in zip(W, inner(r))]
+        p, hist = gauss_newton_cg(hv, g, damping=lam, diag=D, maxiter=a.inner, rtol=a.rtol, precond=precond,
                                   callback=lambda i, r: print("  outer %d cg %d: relative residual %.4e" % (k + 1, i, r), flush=True))
         step, f_new = 1.0, None
         for _ in range(6):      # backtracking on the misfit

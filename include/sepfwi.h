@@ -434,6 +434,38 @@ int sepfwi_regularizer_hvp(int nz, int nx, float dx, float dz, const float *cons
                            const float *const v[3], float *const hv[3], void *hip_stream);
 
 /*
+ * A model-space smoothing operator S with its exact transpose S^T (an unpinned extension: the reference has nothing of the kind): a
+ * separable, normalised Gaussian, truncated at a radius, whose width varies from cell to cell.  All quantities are in cells; fields,
+ * widths and normalisers are (nz, nx) float32, x fastest.  sigx, sigz are non-negative widths, rx, rz integer radii in 0 .. 64.
+ * Along x, in row i:
+ *     Kx[j, m] = 1                                                  for m = j
+ *     Kx[j, m] = exp(-(m - j)^2 / (sigx[i,j]^2 + sigx[i,m]^2))      for 0 < |m - j| <= rx with both cells inside the grid, where the sum
+ *                                                                   of squares is > 0 (otherwise 0); nothing else is cut off
+ *     Kx[j, m] = 0                                                  everywhere else
+ *     Nx[i,j]  = sum over m of Kx[j, m]   (>= 1)
+ *     Sx u   = (Kx u) / Nx                     Sx^T y = Kx (y / Nx)        Kx is symmetric: the same gather, the scaling moved in front
+ * Along z the same down every column with sigz, rz and Nz.  In two dimensions
+ *     S = Sx Sz  (the z pass first, then the x pass)             S^T = Sz^T Sx^T  (the order matters: the widths vary)
+ * A NULL width array or a radius of 0 makes that axis the identity.  It follows that S 1 = 1 (constants are kept), S = I where both
+ * widths are 0, a constant width gives the Gaussian truncated at the radius, <S u, y> = <u, S^T y> exactly, and S S^T is symmetric and
+ * non-negative: a legitimate preconditioner for conjugate gradients, and p = p_ref + s S y a change of variables with gradient s S^T g.
+ *   sepfwi_smooth_plan    inv_nx = 1 / Nx and inv_nz = 1 / Nz from the widths (one launch); an axis with a NULL width array is left alone.
+ *   sepfwi_smooth_apply   out[k] = S in[k] (transpose == 0) or S^T in[k] (transpose != 0) for every field k with in[k] != NULL, with the
+ *                         inv_* arrays that sepfwi_smooth_plan made for the same widths and radii.  in[k] == out[k] is allowed.  Every
+ *                         pass is a gather, one thread per cell, no atomics: the same input gives the same bits, and three fields in
+ *                         one call the bits of three calls.  At most two launches; the intermediate lives in a grow-only block per
+ *                         (device, stream) that sepfwi_release_all frees.  float32 with a fixed operation list (csrc/smoother.hip).
+ * Arrays are host or device memory (of one device), in any mix; host arrays are staged and the call then synchronises the stream, device
+ * arrays are only enqueued on hip_stream.
+ * SEPFWI_EINVAL before anything is touched: nz or nx < 1; a radius outside 0 .. 64; a width array without its inv_* array; all three
+ * fields NULL (or a NULL triple); in[k] without out[k] or out[k] without in[k]; arrays on different devices.
+ */
+int sepfwi_smooth_plan(int nz, int nx, int rx, int rz, const float *sigx, const float *sigz, float *inv_nx, float *inv_nz,
+                       void *hip_stream);
+int sepfwi_smooth_apply(int nz, int nx, int rx, int rz, const float *sigx, const float *sigz, const float *inv_nx, const float *inv_nz,
+                        int transpose, const float *const in[3], float *const out[3], void *hip_stream);
+
+/*
  * Test hook: wavefield `which` (0..4: vz, vx, szz, sxx, sxz; 5..9: their adjoint twins; 10..14: the scattered fields of the last
  * sepfwi_born call) of forward lane `lane` as the last sepfwi_cufd* / sepfwi_born call on (para_fname, gpu_id) left it, dense (nz - nPad, nx) row-major float32, host or device pointer.
  * After a gradient call the forward fields are the reverse-time RECONSTRUCTION run back to time step 0, i.e. they must

@@ -10,6 +10,7 @@
 #include "param_maps.hpp"
 #include "regularizer.hpp"
 #include "session.hpp"
+#include "smoother.hpp"
 
 using namespace sepfwi;
 
@@ -84,6 +85,7 @@ int sepfwi_cufd(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_D
 void sepfwi_release_all(void) {
     try { release_all_sessions(); } catch (...) {}
     release_regularizer_workspaces();
+    release_smoother_workspaces();
 }
 
 int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const float *ett, int nrec, int nSteps) {
@@ -380,6 +382,22 @@ int sepfwi_regularizer_hvp(int nz, int nx, float dx, float dz, const float *cons
         if (!v || !hv) throw std::invalid_argument("regularizer: the product needs v and hv");
         const RegModel m{nz, nx, dx, dz, p, p0, W, alpha, beta, gamma, scale, eps};
         run_regularizer(m, v, nullptr, hv, (hipStream_t)hip_stream);
+    });
+}
+
+int sepfwi_smooth_plan(int nz, int nx, int rx, int rz, const float *sigx, const float *sigz, float *inv_nx, float *inv_nz,
+                       void *hip_stream) {
+    return guarded([&] {
+        const SmoothGeom g{nz, nx, rx, rz, sigx, sigz};
+        run_smooth_plan(g, inv_nx, inv_nz, (hipStream_t)hip_stream);
+    });
+}
+
+int sepfwi_smooth_apply(int nz, int nx, int rx, int rz, const float *sigx, const float *sigz, const float *inv_nx, const float *inv_nz,
+                        int transpose, const float *const in[3], float *const out[3], void *hip_stream) {
+    return guarded([&] {
+        const SmoothGeom g{nz, nx, rx, rz, sigx, sigz};
+        run_smooth_apply(g, inv_nx, inv_nz, transpose != 0, in, out, (hipStream_t)hip_stream);
     });
 }
 

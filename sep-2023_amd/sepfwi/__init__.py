@@ -9,6 +9,7 @@ Host side (Python, mirrors DAS_Waveform_Inversion/Ops/FWI of the reference):
     obj_wrapper            SciPy L-BFGS-B glue                                 (obj_wrapper.py:10-97)
     propagator             Model / Survey / ElasticPropagator, the non-autograd caller (propagator.py:8-226, survey.py:3-38)
     regularize             Regularizer: damping, Tikhonov and total-variation terms of the model with gradient and exact Hessian product
+    smooth                 Smoother: a variable-width Gaussian smoothing operator S with its exact transpose (preconditioner, change of variables)
     dist                   one-process-per-GPU shot sharding + RCCL all-reduce
 
 Device side: libsepfwi.so (csrc/, C ABI in include/sepfwi.h), hand-written HIP for gfx950.
@@ -18,3 +19,4 @@ from .ops import FWIFunction, fwi_ops  # noqa: F401
 from .modules import (FWI, FWI_obscalc, FWI_Lame_Den, FWI_IP_IS_Den, FWI_Vp_Vs_IP, FWI_Vp_Vs_IS,  # noqa: F401
                       FWI_Rock_Physics_VRH, FWI_Rock_Physics_gassmann)
 from .regularize import Regularizer  # noqa: F401
+from .smooth import Smoother  # noqa: F401

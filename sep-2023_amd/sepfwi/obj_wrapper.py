@@ -10,7 +10,17 @@ from scipy import optimize
 
 
 class PyTorchObjective(object):
-    def __init__(self, obj, loss, shot_ids=None, exact=True, regularizer=None):
+    """fun / jac / hessp of `loss` over the parameters of the module `obj` as flat float64 vectors.
+
+    smoother=  a sepfwi.smooth.Smoother S (None: the unknowns are the parameters themselves, every bit as without the argument): the
+               unknown is y with x0 = 0, and the module's parameter k is loaded as p_ref_k + s_k S y_k, p_ref the parameters at
+               construction.  jac packs s_k S^T grad_k and hessp returns s S^T H (s S p) with the regulariser's product inside: the
+               gradient and the (Gauss-Newton) Hessian of the same loss in y, exactly, because S^T is the exact transpose.
+    scales=    s_k: a number, a tuple in named_parameters() order or a dict by name; None: mean |p_ref_k| (1 where that is 0).
+    With a smoother `bounds` is None: a box p_lo <= p <= p_hi has no separable image under S -- every y_k moves a neighbourhood of
+    cells -- so the per-variable bounds that L-BFGS-B takes cannot express it."""
+
+    def __init__(self, obj, loss, shot_ids=None, exact=True, regularizer=None, smoother=None, scales=None):
         self.obj = obj      # nn.Module holding the parameters (and .Bounds)
         self.loss = loss    # callable -> scalar tensor
         self.shot_ids = shot_ids   # for hessp: the shots of obj.gauss_newton (None: no hessp)
@@ -20,6 +30,29 @@ class PyTorchObjective(object):
         self.param_shapes = OrderedDict((n, tuple(p.shape)) for n, p in params.items())
         self.x0 = np.concatenate([p.data.cpu().numpy().ravel() for p in params.values()]).astype(np.float64)
         self.bounds = self.pack_bounds() if getattr(obj, "Bounds", {}) != {} else None
+        self.smoother = smoother
+        if smoother is not None:
+            self.p_ref = OrderedDict((n, p.detach().clone()) for n, p in params.items())
+            if scales is None:
+                scales = [float(p.abs().double().mean()) or 1.0 for p in self.p_ref.values()]
+            elif isinstance(scales, dict):
+                scales = [float(scales[n]) for n in params]
+            elif not isinstance(scales, (tuple, list)):
+                scales = [float(scales)] * len(params)
+            if len(scales) != len(params) or not all(np.isfinite(x) and x > 0 for x in scales):
+                raise ValueError("scales must be one finite positive number per parameter")
+            self.scales = OrderedDict(zip(params, (float(x) for x in scales)))
+            self.x0 = np.zeros_like(self.x0)
+            self.bounds = None
+
+    def smoothed(self, by_name, transpose=False):
+        """{name: tensor} -> {name: s_k S tensor} (or s_k S^T tensor) on the parameters' device and dtype"""
+        names = tuple(getattr(self.obj, "NAMES", ()))
+        if not all(n in names for n in self.p_ref):
+            names = tuple(self.p_ref)
+        ts = tuple(by_name[n].to(device=self.p_ref[n].device, dtype=self.p_ref[n].dtype) if n in by_name else None for n in names)
+        out = self.smoother.apply_t(ts) if transpose else self.smoother.apply(ts)
+        return OrderedDict((n, self.scales[n] * t) for n, t in zip(names, out) if t is not None)
 
     def unpack_parameters(self, x):
         out, i = OrderedDict(), 0
@@ -30,6 +63,9 @@ class PyTorchObjective(object):
         return out
 
     def pack_grads(self):
+        if self.smoother is not None:
+            g = self.smoothed(OrderedDict((n, p.grad.data) for n, p in self.obj.named_parameters()), transpose=True)
+            return np.concatenate([g[n].cpu().numpy().ravel() for n in self.param_shapes]).astype(np.float64)
         return np.concatenate([p.grad.data.cpu().numpy().ravel() for p in self.obj.parameters()]).astype(np.float64)
 
     def pack_bounds(self):
@@ -44,6 +80,8 @@ class PyTorchObjective(object):
 
     def load(self, x):
         state = self.unpack_parameters(x)
+        if self.smoother is not None:
+            state = OrderedDict((n, self.p_ref[n] + t) for n, t in self.smoothed(state).items())
         for name, buf in self.obj.named_buffers():
             state[name] = buf
         self.obj.load_state_dict(state)
@@ -74,7 +112,8 @@ class PyTorchObjective(object):
         obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient.
         Under a parameter file with if_envelope_misfit the product is the envelope misfit's own Gauss-Newton Hessian (include/sepfwi.h,
         sepfwi_born): nothing changes here.  With `regularizer=` its exact Hessian-vector product regularizer.hvp(v) is added, field by
-        field, to the Gauss-Newton product: the Hessian of the model term that `loss` carries as `+ regularizer()`."""
+        field, to the Gauss-Newton product: the Hessian of the model term that `loss` carries as `+ regularizer()`.  With `smoother=`
+        x and p are in the smoothed variables y: the product is s S^T H (s S p), H the sum above at the model p_ref + s S x."""
         if self.shot_ids is None:
             raise ValueError("hessp needs the shots of the Gauss-Newton product: PyTorchObjective(obj, loss, shot_ids=...)")
         if not hasattr(self.obj, "gauss_newton"):
@@ -85,10 +124,15 @@ class PyTorchObjective(object):
         params = OrderedDict(self.obj.named_parameters())
         fields = tuple(getattr(self.obj, "NAMES", tuple(params)))
         chunks = self.unpack_parameters(np.asarray(p, dtype=np.float64))
+        if self.smoother is not None:
+            chunks = self.smoothed(chunks)
         v = tuple(chunks[n].to(device=params[n].device, dtype=params[n].dtype) if n in params else None for n in fields)
         hv = self.obj.gauss_newton(v, self.shot_ids, exact=self.exact)
         if self.regularizer is not None:
             hv = tuple(h if r is None else h + r.to(h.dtype) for h, r in zip(hv, self.regularizer.hvp(v)))
+        if self.smoother is not None:
+            back = self.smoothed(OrderedDict((n, hv[fields.index(n)].detach()) for n in params), transpose=True)
+            return np.concatenate([back[n].cpu().numpy().ravel() for n in params]).astype(np.float64)
         return np.concatenate([hv[fields.index(n)].detach().cpu().numpy().ravel() for n in params]).astype(np.float64)
 
 
@@ -197,7 +241,7 @@ def minimize_lbfgsb(fun, x0, jac, bounds=None, callback=None, maxiter=15000, max
                                    hess_inv=optimize.LbfgsInvHessProduct(s[:n_corrs], y[:n_corrs]))
 
 
-def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2, callback=None):
+def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2, callback=None, precond=None):
     """Matrix-free (preconditioned) conjugate gradients for the Gauss-Newton step:  (H + damping D) p = -g.
 
     hessvec   callable: a tuple of tensors v -> the tuple H v (fwi_ops.gauss_newton at a fixed model; an extension without a
@@ -207,6 +251,9 @@ def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2
     grad      the gradient g, a tuple of tensors shaped like v
     diag      optional tuple of non-negative tensors, e.g. the diagonal pseudo-Hessian: D in the damping term AND the Jacobi
               preconditioner M = D (zero entries -- outside the illuminated region -- are floored at 1e-12 max D); None: D = M = I
+    precond   optional callable: a tuple of tensors r -> the tuple M^-1 r, M^-1 symmetric and non-negative, e.g.
+              sepfwi.smooth.Smoother.preconditioner(diag) = D^-1/2 S S^T D^-1/2.  It REPLACES the Jacobi preconditioner; diag keeps its
+              role in the damping term.  None: every bit as without the argument
     maxiter   fixed cap on the products; rtol: stop once |r| <= rtol |g| in the preconditioned norm sqrt(r^T M^-1 r)
     -> (p, history): the step as a list of tensors and the relative residual before every iteration and after the last one
     (history[0] = 1).  An iteration that meets non-positive curvature (the reference's adjoint is not exact) stops the solve with the
@@ -220,6 +267,8 @@ def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2
         D = [d.detach().clamp_min(0) for d in diag]
         minv = [1.0 / d.clamp_min(1e-12 * float(d.max()) if float(d.max()) > 0 else 1.0) for d in D]
     prec = (lambda r: [t.clone() for t in r]) if minv is None else (lambda r: [a * b for a, b in zip(minv, r)])
+    if precond is not None:
+        prec = lambda r: [t.detach() for t in precond(tuple(r))]
 
     def A(v):
         hv = [t.detach() for t in hessvec(tuple(v))]
