@@ -3,10 +3,10 @@
 // Src/utilities.h:28-36, which would take the Python interpreter down).
 #include <cstdio>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 
 #include "kernels.hpp"
+#include "model_call.hpp"
 #include "param_maps.hpp"
 #include "regularizer.hpp"
 #include "session.hpp"
@@ -84,8 +84,7 @@ int sepfwi_cufd(float *misfit, float *grad_Lambda, float *grad_Mu, float *grad_D
 
 void sepfwi_release_all(void) {
     try { release_all_sessions(); } catch (...) {}
-    release_regularizer_workspaces();
-    release_smoother_workspaces();
+    release_model_workspaces();
 }
 
 int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const float *ett, int nrec, int nSteps) {
@@ -284,86 +283,58 @@ int sepfwi_debug_live_bytes(long long *device, long long *pinned) {
     });
 }
 
-// The calling thread's current HIP device, restored on scope exit: the parameterisation maps run on the autograd thread, whose
-// current device torch's own guards read back with hipGetDevice.
-struct DeviceRestore {
-    int prev = -1;
-    DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; } }
-    ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// every pointer of the fused parameterisation maps must be device memory of ONE device (the maps run where the tensors live)
-static int common_device(std::initializer_list<const void *> ptrs, bool skip_null = false) {
-    int dev = -1;
-    for (const void *p : ptrs) {
-        if (!p && skip_null) continue;  // an optional array (sepfwi_param_jvp's tangents)
-        const int d = ptr_device(p);
-        if (d < 0) throw std::invalid_argument("param maps: every array must be device memory (the host chain stays in torch)");
-        if (dev >= 0 && d != dev) throw std::invalid_argument("param maps: arrays live on different devices");
-        dev = d;
-    }
-    return dev;
-}
-
-static void check_param_dims(int kind, int nz, int nx, int nPml, int nPad) {
-    if (kind < 0 || kind >= PARAM_KINDS) throw std::invalid_argument("param maps: unknown parameterisation " + std::to_string(kind));
-    if (nz < 1 || nx < 1 || nPml < 0 || nPad < 0) throw std::invalid_argument("param maps: bad sizes");
+// The fused parameterisation maps run where the tensors live: every array must be device memory of ONE device (the tangents of
+// sepfwi_param_jvp may be NULL; the forward map has no `in`), made current for the launch (model_call.hpp) -- they
+// run on the autograd thread, whose current device torch's own guards read back with hipGetDevice.
+enum class ParamIn { None, Required, Optional };
+static int param_call(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C, const float *A_ref,
+                      const float *B_ref, const float *C_ref, const float *Mask, const float *in0, const float *in1, const float *in2,
+                      ParamIn in, float *out0, float *out1, float *out2, void *hip_stream,
+                      void (*launch)(hipStream_t, const ParamArgs &)) {
+    return guarded([&] {
+        if (kind < 0 || kind >= PARAM_KINDS) throw std::invalid_argument("param maps: unknown parameterisation " + std::to_string(kind));
+        if (nz < 1 || nx < 1 || nPml < 0 || nPad < 0) throw std::invalid_argument("param maps: bad sizes");
+        const ParamArgs p{kind, nz, nx, nPml, nz + 2 * nPml + nPad, nx + 2 * nPml, A, B, C, A_ref, B_ref, C_ref, Mask, {in0, in1, in2}, {out0, out1, out2}};
+        ModelCall call("param maps", 0, (hipStream_t)hip_stream, true);
+        for (const float *q : {A, B, C, A_ref, B_ref, C_ref, Mask}) call.see(q);
+        if (in == ParamIn::Required)
+            for (const float *q : p.in) call.see(q);
+        for (const float *q : p.out) call.see(q);
+        if (in == ParamIn::Optional)
+            for (const float *q : p.in)
+                if (q) call.see(q);
+        call.enter();
+        launch((hipStream_t)hip_stream, p);
+        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
+    });
 }
 
 int sepfwi_param_forward(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
                          const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, float *Lambda, float *Mu,
                          float *Den, void *hip_stream) {
-    return guarded([&] {
-        check_param_dims(kind, nz, nx, nPml, nPad);
-        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, Lambda, Mu, Den});
-        DeviceRestore restore;
-        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
-        launch_param_fwd((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, Lambda, Mu, Den);
-        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
-    });
+    return param_call(kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, nullptr, nullptr, nullptr, ParamIn::None, Lambda, Mu, Den,
+                      hip_stream, launch_param_fwd);
 }
 
 int sepfwi_param_backward(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
                           const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *gLambda,
                           const float *gMu, const float *gDen, float *gA, float *gB, float *gC, void *hip_stream) {
-    return guarded([&] {
-        check_param_dims(kind, nz, nx, nPml, nPad);
-        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, gLambda, gMu, gDen, gA, gB, gC});
-        DeviceRestore restore;
-        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
-        launch_param_bwd((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, gLambda, gMu, gDen, gA,
-                         gB, gC);
-        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
-    });
+    return param_call(kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, gLambda, gMu, gDen, ParamIn::Required, gA, gB, gC, hip_stream,
+                      launch_param_bwd);
 }
 
 int sepfwi_param_jvp(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C, const float *A_ref,
                      const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB, const float *dC,
                      float *dLambda, float *dMu, float *dDen, void *hip_stream) {
-    return guarded([&] {
-        check_param_dims(kind, nz, nx, nPml, nPad);
-        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, dLambda, dMu, dDen});
-        if (common_device({A, dA, dB, dC}, true) != dev) throw std::invalid_argument("param maps: arrays live on different devices");
-        DeviceRestore restore;
-        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
-        launch_param_jvp((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, dA, dB, dC, dLambda, dMu,
-                         dDen);
-        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
-    });
+    return param_call(kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, dA, dB, dC, ParamIn::Optional, dLambda, dMu, dDen, hip_stream,
+                      launch_param_jvp);
 }
 
 int sepfwi_param_diag(int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C, const float *A_ref,
                       const float *B_ref, const float *C_ref, const float *Mask, const float *hLambda, const float *hMu,
                       const float *hDen, float *hA, float *hB, float *hC, void *hip_stream) {
-    return guarded([&] {
-        check_param_dims(kind, nz, nx, nPml, nPad);
-        const int dev = common_device({A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, hA, hB, hC});
-        DeviceRestore restore;
-        if (hipSetDevice(dev) != hipSuccess) throw HipError("hipSetDevice failed");
-        launch_param_diag((hipStream_t)hip_stream, kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, hA,
-                          hB, hC);
-        if (hipGetLastError() != hipSuccess) throw HipError("param map launch failed");
-    });
+    return param_call(kind, nz, nx, nPml, nPad, A, B, C, A_ref, B_ref, C_ref, Mask, hLambda, hMu, hDen, ParamIn::Required, hA, hB, hC, hip_stream,
+                      launch_param_diag);
 }
 
 int sepfwi_regularizer(int nz, int nx, float dx, float dz, const float *const p[3], const float *const p0[3], const float *W,

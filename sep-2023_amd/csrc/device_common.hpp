@@ -34,6 +34,12 @@ __device__ __forceinline__ int frame_slot(const Grid &g, int z, int x) {
 
 __device__ __forceinline__ bool in_pml_z(const Grid &g, int z) { return z < g.nPml || z > g.nzc - g.nPml - 1; }
 
+// the sum of x over the 64 lanes of a wave, in lane 0: a shuffle tree from offset 32 down to 1, a fixed order (float or double)
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
 
 }  // namespace dev
 }  // namespace sepfwi

@@ -17,9 +17,11 @@
 //
 // The linearised chain (no counterpart in the reference): its tangent P = Dmap_kind(p_m) diag(Mask) E in one launch over the padded
 // grid (k_param_jvp; the backward launch above is P^T), and diag(P^T diag(h) P) in the backward's launch structure (k_param_diag,
-// k_param_diag_rim), both from map_jvp, forward-mode differentiation of the same float32 operation lists.
+// k_param_diag_rim: param_cell and param_rim with another per-cell term), both from map_jvp, forward-mode differentiation of the same
+// float32 operation lists.
 #include <hip/hip_runtime.h>
 
+#include "device_common.hpp"
 #include "param_maps.hpp"
 
 namespace sepfwi {
@@ -445,50 +447,53 @@ __device__ __forceinline__ Triple map_diag(int kind, float m, float a, float b, 
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-}  // namespace
-
-// one thread per PADDED cell
-__global__ void k_param_fwd(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                            const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                            const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                            float *__restrict__ Lam, float *__restrict__ Mu, float *__restrict__ Den) {
-    const int X = blockIdx.x * blockDim.x + threadIdx.x, Z = blockIdx.y * blockDim.y + threadIdx.y;
-    if (X >= nxp || Z >= nzp) return;
-    const size_t o = (size_t)Z * nxp + X;
-    const size_t s = (size_t)clampi(Z - nPml, 0, nz - 1) * nx + clampi(X - nPml, 0, nx - 1);  // replicate padding
-    const float m = Mask[o], w = 1.0f - m;
-    const Triple r = map_fwd(kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o]);
-    Lam[o] = r.a;
-    Mu[o] = r.b;
-    Den[o] = r.c;
-}
+// What one padded cell adds to its physical cell in the two launches over the physical grid and its rim: from the cell's mask m, the
+// blended parameters (a, b, c) and the three inputs there.
+struct BwdTerm {  // P^T: the chain rule of the map, times the mask
+    __device__ __forceinline__ Triple operator()(int kind, float m, float a, float b, float c, float gl, float gm, float gd) const {
+        const Triple d = map_bwd(kind, a, b, c, gl, gm, gd);
+        Triple o;
+        o.a = m * d.a;
+        o.b = m * d.b;
+        o.c = m * d.c;
+        return o;
+    }
+};
+struct DiagTerm {  // diag(P^T diag(h) P): map_diag carries Mask^2 itself
+    __device__ __forceinline__ Triple operator()(int kind, float m, float a, float b, float c, float hl, float hm, float hd) const {
+        return map_diag(kind, m, a, b, c, hl, hm, hd);
+    }
+};
 
 // one thread per PHYSICAL cell: the padded cell that is the cell itself
-__global__ void k_param_bwd(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                            const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                            const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                            const float *__restrict__ gLam, const float *__restrict__ gMu, const float *__restrict__ gDen,
-                            float *__restrict__ gA, float *__restrict__ gB, float *__restrict__ gC) {
+template <class Term>
+__device__ __forceinline__ void param_cell(const ParamArgs &P) {
+    const float *__restrict__ A = P.A, *__restrict__ B = P.B, *__restrict__ C = P.C, *__restrict__ Mask = P.Mask;
+    const float *__restrict__ A_ref = P.A_ref, *__restrict__ B_ref = P.B_ref, *__restrict__ C_ref = P.C_ref;
+    const float *__restrict__ i0 = P.in[0], *__restrict__ i1 = P.in[1], *__restrict__ i2 = P.in[2];
+    float *__restrict__ o0 = P.out[0], *__restrict__ o1 = P.out[1], *__restrict__ o2 = P.out[2];
     const int x = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= nx || z >= nz) return;
-    const size_t s = (size_t)z * nx + x, o = (size_t)(z + nPml) * nxp + (x + nPml);
+    if (x >= P.nx || z >= P.nz) return;
+    const size_t s = (size_t)z * P.nx + x, o = (size_t)(z + P.nPml) * P.nxp + (x + P.nPml);
     const float m = Mask[o], w = 1.0f - m;
-    const Triple d = map_bwd(kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], gLam[o], gMu[o], gDen[o]);
-    gA[s] = m * d.a;
-    gB[s] = m * d.b;
-    gC[s] = m * d.c;
+    const Triple d = Term()(P.kind, m, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], i0[o], i1[o], i2[o]);
+    o0[s] = d.a;
+    o1[s] = d.b;
+    o2[s] = d.c;
 }
 
 // Transpose of the replicate padding: one WAVE per cell of the physical grid's rim adds the padded cells that replicate
 // it (a strip of the padding for an edge cell, a rectangle for the four corners; its own cell is done above).  Lanes
-// stride over the cells row-major, then a shuffle tree: a fixed summation order, no atomics.
-__global__ void k_param_bwd_rim(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                                const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                                const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                                const float *__restrict__ gLam, const float *__restrict__ gMu, const float *__restrict__ gDen,
-                                float *__restrict__ gA, float *__restrict__ gB, float *__restrict__ gC) {
+// stride over the cells row-major, then a shuffle tree, lane 0 adds: a fixed summation order, no atomics.
+template <class Term>
+__device__ __forceinline__ void param_rim(const ParamArgs &P) {
+    const float *__restrict__ A = P.A, *__restrict__ B = P.B, *__restrict__ C = P.C, *__restrict__ Mask = P.Mask;
+    const float *__restrict__ A_ref = P.A_ref, *__restrict__ B_ref = P.B_ref, *__restrict__ C_ref = P.C_ref;
+    const float *__restrict__ i0 = P.in[0], *__restrict__ i1 = P.in[1], *__restrict__ i2 = P.in[2];
+    float *__restrict__ o0 = P.out[0], *__restrict__ o1 = P.out[1], *__restrict__ o2 = P.out[2];
+    const int nz = P.nz, nx = P.nx, nPml = P.nPml;
     const int lane = threadIdx.x & 63;
-    int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // rim cell: top row, bottom row, then the two columns
+    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // rim cell: top row, bottom row, then the two columns
     int z, x;
     if (r < nx) { z = 0; x = r; }
     else if (r < 2 * nx) { z = nz - 1; x = r - nx; }
@@ -498,153 +503,95 @@ __global__ void k_param_bwd_rim(int kind, int nz, int nx, int nPml, int nzp, int
     if (nz == 1 && r >= nx) return;  // a one-row grid has one rim row
     if (nx == 1 && r >= 2 * nx && r >= 2 * nx + (nz - 2)) return;
     const size_t s = (size_t)z * nx + x;
-    const int Z0 = (z == 0) ? 0 : z + nPml, Z1 = (z == nz - 1) ? nzp - 1 : z + nPml;
-    const int X0 = (x == 0) ? 0 : x + nPml, X1 = (x == nx - 1) ? nxp - 1 : x + nPml;
+    const int Z0 = (z == 0) ? 0 : z + nPml, Z1 = (z == nz - 1) ? P.nzp - 1 : z + nPml;
+    const int X0 = (x == 0) ? 0 : x + nPml, X1 = (x == nx - 1) ? P.nxp - 1 : x + nPml;
     const int w_ = X1 - X0 + 1, cnt = (Z1 - Z0 + 1) * w_;
     const float a0 = A[s], b0 = B[s], c0 = C[s];
-    float ga = 0.0f, gb = 0.0f, gc = 0.0f;
+    float ta = 0.0f, tb = 0.0f, tc = 0.0f;
     for (int k = lane; k < cnt; k += 64) {
         const int Z = Z0 + k / w_, X = X0 + k % w_;
         if (Z == z + nPml && X == x + nPml) continue;  // the cell itself
-        const size_t o = (size_t)Z * nxp + X;
+        const size_t o = (size_t)Z * P.nxp + X;
         const float m = Mask[o];
         if (m == 0.0f) continue;
         const float w = 1.0f - m;
-        const Triple d = map_bwd(kind, m * a0 + w * A_ref[o], m * b0 + w * B_ref[o], m * c0 + w * C_ref[o], gLam[o], gMu[o], gDen[o]);
-        ga += m * d.a;
-        gb += m * d.b;
-        gc += m * d.c;
+        const Triple d = Term()(P.kind, m, m * a0 + w * A_ref[o], m * b0 + w * B_ref[o], m * c0 + w * C_ref[o], i0[o], i1[o], i2[o]);
+        ta += d.a;
+        tb += d.b;
+        tc += d.c;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        ga += __shfl_down(ga, off, 64);
-        gb += __shfl_down(gb, off, 64);
-        gc += __shfl_down(gc, off, 64);
-    }
+    ta = dev::wave_sum(ta), tb = dev::wave_sum(tb), tc = dev::wave_sum(tc);
     if (lane == 0) {
-        gA[s] += ga;
-        gB[s] += gb;
-        gC[s] += gc;
+        o0[s] += ta;
+        o1[s] += tb;
+        o2[s] += tc;
     }
+}
+
+}  // namespace
+
+// one thread per PADDED cell
+__global__ void k_param_fwd(ParamArgs P) {
+    const float *__restrict__ A = P.A, *__restrict__ B = P.B, *__restrict__ C = P.C, *__restrict__ Mask = P.Mask;
+    const float *__restrict__ A_ref = P.A_ref, *__restrict__ B_ref = P.B_ref, *__restrict__ C_ref = P.C_ref;
+    float *__restrict__ Lam = P.out[0], *__restrict__ Mu = P.out[1], *__restrict__ Den = P.out[2];
+    const int X = blockIdx.x * blockDim.x + threadIdx.x, Z = blockIdx.y * blockDim.y + threadIdx.y;
+    if (X >= P.nxp || Z >= P.nzp) return;
+    const size_t o = (size_t)Z * P.nxp + X;
+    const size_t s = (size_t)clampi(Z - P.nPml, 0, P.nz - 1) * P.nx + clampi(X - P.nPml, 0, P.nx - 1);  // replicate padding
+    const float m = Mask[o], w = 1.0f - m;
+    const Triple r = map_fwd(P.kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o]);
+    Lam[o] = r.a;
+    Mu[o] = r.b;
+    Den[o] = r.c;
 }
 
 // The tangent of the whole chain, P = Dmap(p_m) diag(Mask) E: one thread per PADDED cell, index math of k_param_fwd.  A NULL dA / dB /
 // dC is a field that is not inverted: read as 0.0f through the same arithmetic, so the result equals that of an array of zeros.
-__global__ void k_param_jvp(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                            const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                            const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                            const float *__restrict__ dA, const float *__restrict__ dB, const float *__restrict__ dC,
-                            float *__restrict__ dLam, float *__restrict__ dMu, float *__restrict__ dDen) {
+__global__ void k_param_jvp(ParamArgs P) {
+    const float *__restrict__ A = P.A, *__restrict__ B = P.B, *__restrict__ C = P.C, *__restrict__ Mask = P.Mask;
+    const float *__restrict__ A_ref = P.A_ref, *__restrict__ B_ref = P.B_ref, *__restrict__ C_ref = P.C_ref;
+    const float *__restrict__ dA = P.in[0], *__restrict__ dB = P.in[1], *__restrict__ dC = P.in[2];
+    float *__restrict__ dLam = P.out[0], *__restrict__ dMu = P.out[1], *__restrict__ dDen = P.out[2];
     const int X = blockIdx.x * blockDim.x + threadIdx.x, Z = blockIdx.y * blockDim.y + threadIdx.y;
-    if (X >= nxp || Z >= nzp) return;
-    const size_t o = (size_t)Z * nxp + X;
-    const size_t s = (size_t)clampi(Z - nPml, 0, nz - 1) * nx + clampi(X - nPml, 0, nx - 1);  // replicate padding
+    if (X >= P.nxp || Z >= P.nzp) return;
+    const size_t o = (size_t)Z * P.nxp + X;
+    const size_t s = (size_t)clampi(Z - P.nPml, 0, P.nz - 1) * P.nx + clampi(X - P.nPml, 0, P.nx - 1);  // replicate padding
     const float m = Mask[o], w = 1.0f - m;
     const float da = dA ? dA[s] : 0.0f, db = dB ? dB[s] : 0.0f, dc = dC ? dC[s] : 0.0f;
-    const Triple r = map_jvp(kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], m * da, m * db, m * dc);
+    const Triple r = map_jvp(P.kind, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], m * da, m * db, m * dc);
     dLam[o] = r.a;
     dMu[o] = r.b;
     dDen[o] = r.c;
 }
 
-// diag(P^T diag(h) P), launch structure of k_param_bwd / k_param_bwd_rim: one thread per PHYSICAL cell for the padded cell that is
-// the cell itself ...
-__global__ void k_param_diag(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                             const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                             const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                             const float *__restrict__ hLam, const float *__restrict__ hMu, const float *__restrict__ hDen,
-                             float *__restrict__ hA, float *__restrict__ hB, float *__restrict__ hC) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= nx || z >= nz) return;
-    const size_t s = (size_t)z * nx + x, o = (size_t)(z + nPml) * nxp + (x + nPml);
-    const float m = Mask[o], w = 1.0f - m;
-    const Triple d = map_diag(kind, m, m * A[s] + w * A_ref[o], m * B[s] + w * B_ref[o], m * C[s] + w * C_ref[o], hLam[o], hMu[o], hDen[o]);
-    hA[s] = d.a;
-    hB[s] = d.b;
-    hC[s] = d.c;
+// the transpose P^T and diag(P^T diag(h) P) share one launch structure: the physical grid, then its rim
+__global__ void k_param_bwd(ParamArgs P) { param_cell<BwdTerm>(P); }
+__global__ void k_param_bwd_rim(ParamArgs P) { param_rim<BwdTerm>(P); }
+__global__ void k_param_diag(ParamArgs P) { param_cell<DiagTerm>(P); }
+__global__ void k_param_diag_rim(ParamArgs P) { param_rim<DiagTerm>(P); }
+
+namespace {
+
+const dim3 kTile(64, 4);
+dim3 tiles(int nz, int nx) { return dim3((nx + 63) / 64, (nz + 3) / 4); }
+dim3 rim_blocks(const ParamArgs &p) { return dim3((2 * p.nx + 2 * (p.nz > 2 ? p.nz - 2 : 0) + 3) / 4); }  // four waves, a rim cell each
+
+}  // namespace
+
+void launch_param_fwd(hipStream_t st, const ParamArgs &p) { hipLaunchKernelGGL(k_param_fwd, tiles(p.nzp, p.nxp), kTile, 0, st, p); }
+
+void launch_param_jvp(hipStream_t st, const ParamArgs &p) { hipLaunchKernelGGL(k_param_jvp, tiles(p.nzp, p.nxp), kTile, 0, st, p); }
+
+void launch_param_bwd(hipStream_t st, const ParamArgs &p) {
+    hipLaunchKernelGGL(k_param_bwd, tiles(p.nz, p.nx), kTile, 0, st, p);
+    hipLaunchKernelGGL(k_param_bwd_rim, rim_blocks(p), dim3(256), 0, st, p);
 }
 
-// ... and one WAVE per rim cell for the padded cells that replicate it: lanes stride row-major, a shuffle tree, lane 0 adds.
-__global__ void k_param_diag_rim(int kind, int nz, int nx, int nPml, int nzp, int nxp, const float *__restrict__ A,
-                                 const float *__restrict__ B, const float *__restrict__ C, const float *__restrict__ A_ref,
-                                 const float *__restrict__ B_ref, const float *__restrict__ C_ref, const float *__restrict__ Mask,
-                                 const float *__restrict__ hLam, const float *__restrict__ hMu, const float *__restrict__ hDen,
-                                 float *__restrict__ hA, float *__restrict__ hB, float *__restrict__ hC) {
-    const int lane = threadIdx.x & 63;
-    int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // rim cell, numbered as in k_param_bwd_rim
-    int z, x;
-    if (r < nx) { z = 0; x = r; }
-    else if (r < 2 * nx) { z = nz - 1; x = r - nx; }
-    else if (r < 2 * nx + (nz - 2)) { z = r - 2 * nx + 1; x = 0; }
-    else if (r < 2 * nx + 2 * (nz - 2)) { z = r - 2 * nx - (nz - 2) + 1; x = nx - 1; }
-    else return;
-    if (nz == 1 && r >= nx) return;
-    if (nx == 1 && r >= 2 * nx && r >= 2 * nx + (nz - 2)) return;
-    const size_t s = (size_t)z * nx + x;
-    const int Z0 = (z == 0) ? 0 : z + nPml, Z1 = (z == nz - 1) ? nzp - 1 : z + nPml;
-    const int X0 = (x == 0) ? 0 : x + nPml, X1 = (x == nx - 1) ? nxp - 1 : x + nPml;
-    const int w_ = X1 - X0 + 1, cnt = (Z1 - Z0 + 1) * w_;
-    const float a0 = A[s], b0 = B[s], c0 = C[s];
-    float ha = 0.0f, hb = 0.0f, hc = 0.0f;
-    for (int k = lane; k < cnt; k += 64) {
-        const int Z = Z0 + k / w_, X = X0 + k % w_;
-        if (Z == z + nPml && X == x + nPml) continue;  // the cell itself
-        const size_t o = (size_t)Z * nxp + X;
-        const float m = Mask[o];
-        if (m == 0.0f) continue;
-        const float w = 1.0f - m;
-        const Triple d = map_diag(kind, m, m * a0 + w * A_ref[o], m * b0 + w * B_ref[o], m * c0 + w * C_ref[o], hLam[o], hMu[o], hDen[o]);
-        ha += d.a;
-        hb += d.b;
-        hc += d.c;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        ha += __shfl_down(ha, off, 64);
-        hb += __shfl_down(hb, off, 64);
-        hc += __shfl_down(hc, off, 64);
-    }
-    if (lane == 0) {
-        hA[s] += ha;
-        hB[s] += hb;
-        hC[s] += hc;
-    }
-}
-
-void launch_param_fwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, float *Lam, float *Mu,
-                      float *Den) {
-    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
-    hipLaunchKernelGGL(k_param_fwd, dim3((nxp + 63) / 64, (nzp + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
-                       A_ref, B_ref, C_ref, Mask, Lam, Mu, Den);
-}
-
-void launch_param_bwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *gLam,
-                      const float *gMu, const float *gDen, float *gA, float *gB, float *gC) {
-    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
-    hipLaunchKernelGGL(k_param_bwd, dim3((nx + 63) / 64, (nz + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
-                       A_ref, B_ref, C_ref, Mask, gLam, gMu, gDen, gA, gB, gC);
-    const int rim = 2 * nx + 2 * (nz > 2 ? nz - 2 : 0);
-    hipLaunchKernelGGL(k_param_bwd_rim, dim3((rim + 3) / 4), dim3(256), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C, A_ref, B_ref,
-                       C_ref, Mask, gLam, gMu, gDen, gA, gB, gC);
-}
-
-void launch_param_jvp(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB,
-                      const float *dC, float *dLam, float *dMu, float *dDen) {
-    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
-    hipLaunchKernelGGL(k_param_jvp, dim3((nxp + 63) / 64, (nzp + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
-                       A_ref, B_ref, C_ref, Mask, dA, dB, dC, dLam, dMu, dDen);
-}
-
-void launch_param_diag(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *hLam,
-                       const float *hMu, const float *hDen, float *hA, float *hB, float *hC) {
-    const int nzp = nz + 2 * nPml + nPad, nxp = nx + 2 * nPml;
-    hipLaunchKernelGGL(k_param_diag, dim3((nx + 63) / 64, (nz + 3) / 4), dim3(64, 4), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C,
-                       A_ref, B_ref, C_ref, Mask, hLam, hMu, hDen, hA, hB, hC);
-    const int rim = 2 * nx + 2 * (nz > 2 ? nz - 2 : 0);
-    hipLaunchKernelGGL(k_param_diag_rim, dim3((rim + 3) / 4), dim3(256), 0, st, kind, nz, nx, nPml, nzp, nxp, A, B, C, A_ref, B_ref,
-                       C_ref, Mask, hLam, hMu, hDen, hA, hB, hC);
+void launch_param_diag(hipStream_t st, const ParamArgs &p) {
+    hipLaunchKernelGGL(k_param_diag, tiles(p.nz, p.nx), kTile, 0, st, p);
+    hipLaunchKernelGGL(k_param_diag_rim, rim_blocks(p), dim3(256), 0, st, p);
 }
 
 }  // namespace sepfwi
+

@@ -16,19 +16,20 @@ enum ParamKind {
     PARAM_KINDS = 7
 };
 
-void launch_param_fwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, float *Lam, float *Mu,
-                      float *Den);
-void launch_param_bwd(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *gLam,
-                      const float *gMu, const float *gDen, float *gA, float *gB, float *gC);
-// the tangent P = Dmap(p_m) diag(Mask) E of the chain (launch_param_bwd is its transpose); dA, dB, dC may each be NULL (= 0)
-void launch_param_jvp(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                      const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *dA, const float *dB,
-                      const float *dC, float *dLam, float *dMu, float *dDen);
-// diag(P^T diag(h) P): h on the padded grid -> the (nz, nx) grid, rim sum and Mask^2 included
-void launch_param_diag(hipStream_t st, int kind, int nz, int nx, int nPml, int nPad, const float *A, const float *B, const float *C,
-                       const float *A_ref, const float *B_ref, const float *C_ref, const float *Mask, const float *hLam,
-                       const float *hMu, const float *hDen, float *hA, float *hB, float *hC);
+// One call's arguments, by value into the kernels.  (nz, nx) is the physical grid of A, B, C; (nzp, nxp) = (nz + 2 nPml + nPad,
+// nx + 2 nPml) the padded one of the reference model, the mask and (Lambda, Mu, Den).
+struct ParamArgs {
+    int kind, nz, nx, nPml, nzp, nxp;
+    const float *A, *B, *C, *A_ref, *B_ref, *C_ref, *Mask;
+    const float *in[3];  // what the map is applied to, on the grid it lives on (none for the forward map)
+    float *out[3];
+};
+
+void launch_param_fwd(hipStream_t st, const ParamArgs &p);  // out = (Lambda, Mu, Den), padded
+void launch_param_bwd(hipStream_t st, const ParamArgs &p);  // in = dL/d(Lambda, Mu, Den), padded -> out = dL/d(A, B, C)
+// the tangent P = Dmap(p_m) diag(Mask) E of the chain (launch_param_bwd is its transpose); each of in = (dA, dB, dC) may be NULL (= 0)
+void launch_param_jvp(hipStream_t st, const ParamArgs &p);
+// diag(P^T diag(h) P): in = h on the padded grid -> out on the (nz, nx) grid, rim sum and Mask^2 included
+void launch_param_diag(hipStream_t st, const ParamArgs &p);
 
 }  // namespace sepfwi

@@ -14,20 +14,14 @@
 // non-negative float32 with a relative error of a few roundings, exactly 0 for a constant field.
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <utility>
-#include <vector>
 
-#include "device_alloc.hpp"
 #include "hip_check.hpp"
+#include "model_call.hpp"
 #include "regularizer.hpp"
 
 namespace sepfwi {
-
-int ptr_device(const void *p);  // session_run.cpp: the device of a device pointer, -1 for host memory
 
 namespace {
 
@@ -124,6 +118,8 @@ __global__ void k_reg_value_grad(RegArgs A, double *__restrict__ partial) {
     }
     if (!partial) return;
     double acc = (double)e;
+    // (the tree of dev::wave_sum, written out here and in k_reg_sum: through the helper the compiler orders the same instructions
+    // differently, and these kernels' code is held fixed)
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     __shared__ double part[4];
     if (threadIdx.x == 0) part[threadIdx.y] = acc;
@@ -176,15 +172,6 @@ __global__ void k_reg_hvp(RegArgs A) {
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct Workspaces {  // one grow-only block of doubles per (device, stream): the block partials, then the value
-    std::mutex mu;
-    std::map<std::pair<int, hipStream_t>, DevBuf<double>> blocks;
-};
-Workspaces &workspaces() {
-    static Workspaces w;
-    return w;
-}
-
 void validate(const RegModel &m, const float *const *v, double *value, float *const *out) {
     auto bad = [](const std::string &what) { throw std::invalid_argument("regularizer: " + what); };
     if (m.nz < 1 || m.nx < 1) bad("nz and nx must be at least 1");
@@ -208,113 +195,61 @@ void validate(const RegModel &m, const float *const *v, double *value, float *co
 
 }  // namespace
 
-void release_regularizer_workspaces() noexcept {
-    Workspaces &w = workspaces();
-    std::lock_guard<std::mutex> lock(w.mu);
-    w.blocks.clear();
-}
-
 void run_regularizer(const RegModel &m, const float *const *v, double *value, float *const *out, hipStream_t st) {
     validate(m, v, value, out);
     const bool product = v != nullptr;
     const size_t n = (size_t)m.nz * (size_t)m.nx;
 
-    // the device: that of the first device array, else the calling thread's current one
-    int dev = -1;
-    auto see = [&](const void *q) {
-        const int d = ptr_device(q);
-        if (d < 0) return;
-        if (dev >= 0 && d != dev) throw std::invalid_argument("regularizer: arrays live on different devices");
-        dev = d;
-    };
-    see(m.W);
-    see(value);
+    ModelCall call("regularizer", n, st);
+    call.see(m.W), call.see(value);
     for (int k = 0; k < 3; k++) {
-        see(m.p[k]), see(m.p0[k]);
-        if (v) see(v[k]);
-        if (out) see(out[k]);
+        call.see(m.p[k]), call.see(m.p0[k]);
+        if (v) call.see(v[k]);
+        if (out) call.see(out[k]);
     }
-    int prev = -1;
-    HIP_OK(hipGetDevice(&prev));
-    if (dev < 0) dev = prev;
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
-    HIP_OK(hipSetDevice(dev));
-
-    std::vector<DevBuf<float>> staged;  // host arrays, for the length of this call
-    staged.reserve(16);
-    bool to_host = false;
-    auto in = [&](const float *q) -> const float * {
-        if (!q || ptr_device(q) == dev) return q;
-        staged.emplace_back(nullptr, n);
-        HIP_OK(hipMemcpyAsync(staged.back().get(), q, n * sizeof(float), hipMemcpyHostToDevice, st));
-        return staged.back().get();
-    };
+    const int dev = call.enter();
 
     RegArgs A{};
     A.nz = m.nz, A.nx = m.nx;
-    A.W = in(m.W);
+    A.W = call.in(m.W);
     A.eps = m.eps;
     A.e2 = (float)((double)m.eps * (double)m.eps);
-    float *host_out[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; k++) {
         const bool on = m.p[k] && (!product || v[k]);
         if (out && out[k] && !on) {  // a field that is skipped: zeros
-            if (ptr_device(out[k]) == dev)
+            if (call.on_device(out[k]))
                 HIP_OK(hipMemsetAsync(out[k], 0, n * sizeof(float), st));
             else
                 std::fill(out[k], out[k] + n, 0.0f);
         }
         if (!on) continue;
         const double s = (double)m.scale[k];
-        A.p[k] = in(m.p[k]);
-        A.p0[k] = m.alpha[k] > 0.0f ? in(m.p0[k]) : nullptr;
-        A.v[k] = product ? in(v[k]) : nullptr;
+        A.p[k] = call.in(m.p[k]);
+        A.p0[k] = m.alpha[k] > 0.0f ? call.in(m.p0[k]) : nullptr;
+        A.v[k] = product ? call.in(v[k]) : nullptr;
         A.a2[k] = (float)((double)m.alpha[k] / (s * s));
         A.beta[k] = m.beta[k], A.gamma[k] = m.gamma[k];
         A.rx[k] = (float)(1.0 / (s * (double)m.dx));
         A.rz[k] = (float)(1.0 / (s * (double)m.dz));
-        if (out && out[k]) {
-            if (ptr_device(out[k]) == dev) {
-                A.out[k] = out[k];
-            } else {
-                staged.emplace_back(nullptr, n);
-                A.out[k] = staged.back().get();
-                host_out[k] = out[k];
-                to_host = true;
-            }
-        }
+        if (out) A.out[k] = call.out(out[k]);
     }
 
     const dim3 grid((m.nx + 63) / 64, (m.nz + 3) / 4, 3), block(64, 4);
     if (product) {
         hipLaunchKernelGGL(k_reg_hvp, grid, block, 0, st, A);
     } else {
-        double *partial = nullptr, *dvalue = nullptr;
+        double *partial = nullptr;
         const size_t blocks = (size_t)grid.x * grid.y * grid.z;
-        if (value) {
-            Workspaces &w = workspaces();
-            std::lock_guard<std::mutex> lock(w.mu);
-            DevBuf<double> &b = w.blocks[std::make_pair(dev, st)];
-            b.ensure(blocks + 1);
-            partial = b.get();
-            dvalue = ptr_device(value) == dev ? value : partial + blocks;
-        }
+        if (value) partial = model_workspace<double>(ModelOp::Regularizer, dev, st, blocks + 1);  // the block partials, then the value
         hipLaunchKernelGGL(k_reg_value_grad, grid, block, 0, st, A, partial);
         if (value) {
+            double *dvalue = call.on_device(value) ? value : partial + blocks;
             hipLaunchKernelGGL(k_reg_sum, dim3(1), dim3(1024), 0, st, (int)blocks, (const double *)partial, dvalue);
-            if (dvalue != value) {
-                HIP_OK(hipMemcpyAsync(value, dvalue, sizeof(double), hipMemcpyDeviceToHost, st));
-                to_host = true;
-            }
+            if (dvalue != value) call.host_result(value, dvalue, sizeof(double));
         }
     }
     HIP_OK(hipGetLastError());
-    for (int k = 0; k < 3; k++)
-        if (host_out[k]) HIP_OK(hipMemcpyAsync(host_out[k], A.out[k], n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (to_host || !staged.empty()) HIP_OK(hipStreamSynchronize(st));  // results in host memory; the staging blocks are freed on return
+    call.finish();
 }
 
 }  // namespace sepfwi

@@ -18,10 +18,7 @@ struct RegModel {
 
 // Value and gradient (v == NULL; value, g or single entries of g may be NULL), or the product (v and out = hv; value NULL).  Arrays
 // may be host or device memory; validates before it touches a device (std::invalid_argument), stages what is not on the device and
-// synchronises the stream only when something has to reach host memory.
+// synchronises the stream only when something has to reach host memory.  The block partials are a workspace of model_call.hpp.
 void run_regularizer(const RegModel &m, const float *const *v, double *value, float *const *out, hipStream_t st);
-
-// frees the per-(device, stream) partial-sum blocks (sepfwi_release_all)
-void release_regularizer_workspaces() noexcept;
 
 }  // namespace sepfwi

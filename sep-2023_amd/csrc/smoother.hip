@@ -18,20 +18,14 @@
 // An axis without a width array or with radius 0 is the identity and runs no pass.
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <utility>
-#include <vector>
 
-#include "device_alloc.hpp"
 #include "hip_check.hpp"
+#include "model_call.hpp"
 #include "smoother.hpp"
 
 namespace sepfwi {
-
-int ptr_device(const void *p);  // session_run.cpp: the device of a device pointer, -1 for host memory
 
 namespace {
 
@@ -130,15 +124,6 @@ __global__ void k_smooth_norm(int nz, int nx, int rx, int rz, const float *__res
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct Workspaces {  // one grow-only block of three fields per (device, stream): what the first pass hands to the second
-    std::mutex mu;
-    std::map<std::pair<int, hipStream_t>, DevBuf<float>> blocks;
-};
-Workspaces &workspaces() {
-    static Workspaces w;
-    return w;
-}
-
 void bad(const std::string &what) { throw std::invalid_argument("smoother: " + what); }
 
 void validate(const SmoothGeom &g, const float *inv_nx, const float *inv_nz) {
@@ -149,63 +134,21 @@ void validate(const SmoothGeom &g, const float *inv_nx, const float *inv_nz) {
     if (g.sigz && !inv_nz) bad("sigz is given without inv_nz");
 }
 
-// the device of the arrays seen so far: that of the first device array, else the calling thread's current one
-struct DeviceOf {
-    int dev = -1;
-    void see(const void *q) {
-        const int d = ptr_device(q);
-        if (d < 0) return;
-        if (dev >= 0 && d != dev) bad("arrays live on different devices");
-        dev = d;
-    }
-};
-
-struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-};
-
 }  // namespace
-
-void release_smoother_workspaces() noexcept {
-    Workspaces &w = workspaces();
-    std::lock_guard<std::mutex> lock(w.mu);
-    w.blocks.clear();
-}
 
 void run_smooth_plan(const SmoothGeom &g, float *inv_nx, float *inv_nz, hipStream_t st) {
     validate(g, inv_nx, inv_nz);
     if (!g.sigx && !g.sigz) return;
     const size_t n = (size_t)g.nz * (size_t)g.nx;
-    DeviceOf where;
-    where.see(g.sigx), where.see(g.sigz), where.see(inv_nx), where.see(inv_nz);
-    int prev = -1;
-    HIP_OK(hipGetDevice(&prev));
-    const int dev = where.dev < 0 ? prev : where.dev;
-    Restore restore{prev};
-    HIP_OK(hipSetDevice(dev));
-
-    std::vector<DevBuf<float>> staged;  // host arrays, for the length of this call
-    staged.reserve(4);
-    auto in = [&](const float *q) -> const float * {
-        if (!q || ptr_device(q) == dev) return q;
-        staged.emplace_back(nullptr, n);
-        HIP_OK(hipMemcpyAsync(staged.back().get(), q, n * sizeof(float), hipMemcpyHostToDevice, st));
-        return staged.back().get();
-    };
-    auto out = [&](float *q) -> float * {
-        if (!q || ptr_device(q) == dev) return q;
-        staged.emplace_back(nullptr, n);
-        return staged.back().get();
-    };
-    const float *sx = in(g.sigx), *sz = in(g.sigz);
-    float *ix = g.sigx ? out(inv_nx) : nullptr, *iz = g.sigz ? out(inv_nz) : nullptr;
+    ModelCall call("smoother", n, st);
+    call.see(g.sigx), call.see(g.sigz), call.see(inv_nx), call.see(inv_nz);
+    call.enter();
+    const float *sx = call.in(g.sigx), *sz = call.in(g.sigz);
+    float *ix = g.sigx ? call.out(inv_nx) : nullptr, *iz = g.sigz ? call.out(inv_nz) : nullptr;
     const dim3 grid((g.nx + 63) / 64, (g.nz + 3) / 4, 2), block(64, 4);
     hipLaunchKernelGGL(k_smooth_norm, grid, block, 0, st, g.nz, g.nx, g.rx, g.rz, sx, sz, ix, iz);
     HIP_OK(hipGetLastError());
-    if (ix && ix != inv_nx) HIP_OK(hipMemcpyAsync(inv_nx, ix, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (iz && iz != inv_nz) HIP_OK(hipMemcpyAsync(inv_nz, iz, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (!staged.empty()) HIP_OK(hipStreamSynchronize(st));  // results in host memory; the staging blocks are freed on return
+    call.finish();
 }
 
 void run_smooth_apply(const SmoothGeom &g, const float *inv_nx, const float *inv_nz, bool transpose, const float *const *in,
@@ -221,41 +164,19 @@ void run_smooth_apply(const SmoothGeom &g, const float *inv_nx, const float *inv
     if (!any) bad("all three fields are NULL");
     const size_t n = (size_t)g.nz * (size_t)g.nx;
 
-    DeviceOf where;
-    where.see(g.sigx), where.see(g.sigz), where.see(inv_nx), where.see(inv_nz);
-    for (int k = 0; k < 3; k++) where.see(in[k]), where.see(out[k]);
-    int prev = -1;
-    HIP_OK(hipGetDevice(&prev));
-    const int dev = where.dev < 0 ? prev : where.dev;
-    Restore restore{prev};
-    HIP_OK(hipSetDevice(dev));
+    ModelCall call("smoother", n, st);
+    call.see(g.sigx), call.see(g.sigz), call.see(inv_nx), call.see(inv_nz);
+    for (int k = 0; k < 3; k++) call.see(in[k]), call.see(out[k]);
+    const int dev = call.enter();
 
-    std::vector<DevBuf<float>> staged;  // host arrays, for the length of this call
-    staged.reserve(10);
-    auto stage = [&](const float *q) -> const float * {
-        if (!q || ptr_device(q) == dev) return q;
-        staged.emplace_back(nullptr, n);
-        HIP_OK(hipMemcpyAsync(staged.back().get(), q, n * sizeof(float), hipMemcpyHostToDevice, st));
-        return staged.back().get();
-    };
     const bool on_x = g.sigx && g.rx > 0, on_z = g.sigz && g.rz > 0;
-    const float *sig[2] = {on_x ? stage(g.sigx) : nullptr, on_z ? stage(g.sigz) : nullptr};
-    const float *inv[2] = {on_x ? stage(inv_nx) : nullptr, on_z ? stage(inv_nz) : nullptr};
+    const float *sig[2] = {on_x ? call.in(g.sigx) : nullptr, on_z ? call.in(g.sigz) : nullptr};
+    const float *inv[2] = {on_x ? call.in(inv_nx) : nullptr, on_z ? call.in(inv_nz) : nullptr};
     const int radius[2] = {g.rx, g.rz};
 
-    const float *src[3] = {nullptr, nullptr, nullptr};
-    float *dst[3] = {nullptr, nullptr, nullptr}, *host_out[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++) {
-        if (!in[k]) continue;
-        src[k] = stage(in[k]);
-        if (ptr_device(out[k]) == dev) {
-            dst[k] = out[k];
-        } else {
-            staged.emplace_back(nullptr, n);
-            dst[k] = staged.back().get();
-            host_out[k] = out[k];
-        }
-    }
+    const float *src[3];  // (a host array given as input and output is staged twice: the passes then run out of place)
+    float *dst[3];
+    for (int k = 0; k < 3; k++) src[k] = call.in(in[k]), dst[k] = call.out(out[k]);
 
     // S = Sx Sz runs the z pass first, S^T = Sz^T Sx^T the x pass; an identity axis runs none
     int axes[2], passes = 0;
@@ -288,14 +209,9 @@ void run_smooth_apply(const SmoothGeom &g, const float *inv_nx, const float *inv
     } else if (passes <= 1 && !aliased) {
         launch(first, r_first, src, dst);
     } else {
-        float *mid[3];
-        {
-            Workspaces &w = workspaces();
-            std::lock_guard<std::mutex> lock(w.mu);
-            DevBuf<float> &b = w.blocks[std::make_pair(dev, st)];
-            b.ensure(3 * n);
-            for (int k = 0; k < 3; k++) mid[k] = b.get() + (size_t)k * n;
-        }
+        float *mid[3];  // three fields: what the first pass hands to the second
+        mid[0] = model_workspace<float>(ModelOp::Smoother, dev, st, 3 * n);
+        mid[1] = mid[0] + n, mid[2] = mid[1] + n;
         launch(first, r_first, src, mid);
         if (passes == 2)
             launch(axes[1], radius[axes[1]], mid, dst);
@@ -303,9 +219,7 @@ void run_smooth_apply(const SmoothGeom &g, const float *inv_nx, const float *inv
             launch(0, 0, mid, dst);
     }
     HIP_OK(hipGetLastError());
-    for (int k = 0; k < 3; k++)
-        if (host_out[k]) HIP_OK(hipMemcpyAsync(host_out[k], dst[k], n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (!staged.empty()) HIP_OK(hipStreamSynchronize(st));  // results in host memory; the staging blocks are freed on return
+    call.finish();
 }
 
 }  // namespace sepfwi

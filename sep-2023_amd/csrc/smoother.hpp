@@ -20,11 +20,8 @@ struct SmoothGeom {
 void run_smooth_plan(const SmoothGeom &g, float *inv_nx, float *inv_nz, hipStream_t st);
 
 // out = S in (transpose false: the z pass, then the x pass) or S^T in (the x pass, then the z pass), field by field; a NULL field is
-// skipped, in[k] == out[k] is allowed.  At most two launches.
+// skipped, in[k] == out[k] is allowed.  At most two launches; the intermediate of three fields is a workspace of model_call.hpp.
 void run_smooth_apply(const SmoothGeom &g, const float *inv_nx, const float *inv_nz, bool transpose, const float *const *in,
                       float *const *out, hipStream_t st);
-
-// frees the per-(device, stream) intermediates (sepfwi_release_all)
-void release_smoother_workspaces() noexcept;
 
 }  // namespace sepfwi

@@ -22,8 +22,8 @@ PROBES_LIB_PATH = os.path.join(_ROOT, "libsepfwi_probes.so")
 FAULT_LIB_PATH = os.path.join(_ROOT, "libsepfwi_fault.so")
 VARIANTS = {"default": (LIB_PATH, []), "probes": (PROBES_LIB_PATH, ["-DSEPFWI_PROBES"]), "fault": (FAULT_LIB_PATH, ["-DSEPFWI_PK_FAULT=17"])}
 PUBLIC_OPTIONS = ("bwd_fuse", "batch", "img_every", "quiet_skip", "obs_cache_mb", "probe")
-SOURCES = ["kernels.hip", "schedule.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
-HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
+SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
+HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
            os.path.join("..", "..", "include", "sepfwi.h")]
 
 _libs = {}
@@ -136,6 +136,24 @@ EXPORTS = ["sepfwi_last_error", "sepfwi_version", "sepfwi_device_count", "sepfwi
            "sepfwi_shot_split", "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes",
            "sepfwi_set_observed", "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact",
            "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply"]
+
+
+def ptr(t):
+    """a tensor's data pointer as a C argument; None stays None (NULL)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def triple(ts):
+    """up to three tensors as a C array of three pointers, padded with NULL"""
+    ts = list(ts)
+    return (C.c_void_p * 3)(*([t.data_ptr() for t in ts] + [None] * (3 - len(ts))))
+
+
+def stream_arg(device):
+    """torch's current stream on `device` as a C argument; None for the null stream"""
+    import torch
+    cs = torch.cuda.current_stream(device).cuda_stream
+    return C.c_void_p(cs) if cs else None
 
 
 class SepFwiError(RuntimeError):

@@ -9,8 +9,6 @@ scripts work unchanged.  One generic base replaces the reference's copy-per-para
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
@@ -31,10 +29,9 @@ class _FusedParamMap(torch.autograd.Function):
         a, b, c = [t.detach().contiguous() for t in (a, b, c)]
         nz, nx = a.shape
         outs = [torch.empty_like(a_ref) for _ in range(3)]
-        st = torch.cuda.current_stream(a.device).cuda_stream
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _native.ptr
         _native.check(L.sepfwi_param_forward(kind, nz, nx, nPml, nPad, p(a), p(b), p(c), p(a_ref), p(b_ref), p(c_ref), p(mask),
-                                             p(outs[0]), p(outs[1]), p(outs[2]), C.c_void_p(st) if st else None))
+                                             p(outs[0]), p(outs[1]), p(outs[2]), _native.stream_arg(a.device)))
         ctx.save_for_backward(a, b, c, a_ref, b_ref, c_ref, mask)
         ctx.meta = (kind, nPml, nPad)
         return tuple(outs)
@@ -53,11 +50,10 @@ class _FusedParamMap(torch.autograd.Function):
                 g = zero
             gs.append(g.contiguous())
         outs = [torch.empty_like(a) for _ in range(3)]
-        st = torch.cuda.current_stream(a.device).cuda_stream
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _native.ptr
         _native.check(L.sepfwi_param_backward(kind, nz, nx, nPml, nPad, p(a), p(b), p(c), p(a_ref), p(b_ref), p(c_ref), p(mask),
                                               p(gs[0]), p(gs[1]), p(gs[2]), p(outs[0]), p(outs[1]), p(outs[2]),
-                                              C.c_void_p(st) if st else None))
+                                              _native.stream_arg(a.device)))
         return outs[0], outs[1], outs[2], None, None, None, None, None, None, None
 
 
@@ -139,10 +135,9 @@ class _MaskedTriple(nn.Module):
         return [getattr(self, n).detach() for n in self.NAMES]
 
     def _native_args(self, cur):
-        p = lambda t: C.c_void_p(t.data_ptr())
         keep = [t.contiguous() for t in cur] + [getattr(self, n + "_ref").contiguous() for n in self.NAMES] + [self.Mask.contiguous()]
-        st = torch.cuda.current_stream(self.Mask.device).cuda_stream
-        return keep, [int(self.KIND), self.nz_orig, self.nx_orig, int(self.nPml), int(self.nPad)] + [p(t) for t in keep], C.c_void_p(st) if st else None
+        dims = [int(self.KIND), self.nz_orig, self.nx_orig, int(self.nPml), int(self.nPad)]
+        return keep, dims + [_native.ptr(t) for t in keep], _native.stream_arg(self.Mask.device)
 
     def _like(self, t, ref, what):
         if t is None:
@@ -161,8 +156,7 @@ class _MaskedTriple(nn.Module):
         if self._fusable():
             keep, args, st = self._native_args(cur)
             outs = [torch.empty_like(keep[-1]) for _ in range(3)]      # the padded grid, contiguous
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            _native.check(_native.lib().sepfwi_param_jvp(*args, *[ptr(t) for t in v], *[ptr(t) for t in outs], st))
+            _native.check(_native.lib().sepfwi_param_jvp(*args, *[_native.ptr(t) for t in v + outs], st))
             return tuple(outs)
         v = [torch.zeros_like(f) if t is None else t for t, f in zip(v, cur)]
         return tuple(torch.func.jvp(self._chain, tuple(cur), tuple(v))[1])
@@ -191,8 +185,7 @@ class _MaskedTriple(nn.Module):
         if self._fusable():
             keep, args, st = self._native_args(cur)
             outs = [torch.empty_like(t) for t in keep[:3]]
-            ptr = lambda t: C.c_void_p(t.data_ptr())
-            _native.check(_native.lib().sepfwi_param_diag(*args, *[ptr(t) for t in h], *[ptr(t) for t in outs], st))
+            _native.check(_native.lib().sepfwi_param_diag(*args, *[_native.ptr(t) for t in h + outs], st))
             return tuple(outs)
         if (self.nz, self.nx) != (self.nz_orig, self.nx_orig):
             raise NotImplementedError("diag: the padding's entries are 0 / 1 only without the bilinear resize")

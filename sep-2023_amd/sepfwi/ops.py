@@ -73,10 +73,6 @@ def _para_dims(para_fname):
     return _DIMS_CACHE[key]
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _checked(Lambda, Mu, Den, Stf, shot_ids, para_fname, what, v=(), need_dims=True):
     """What _cufd, _born and _adjoint_exact do to their arguments before anything is allocated: float32 contiguous tensors, one
     shape and one device for the model (and the perturbation v), Stf and Shot_ids against the parameter file.
@@ -116,8 +112,7 @@ def _stream_or_sync(Lambda, Stf, gpu_id, sync_current=False):
     session's GPU, else NULL (the legacy default stream: the library orders itself behind it) after the model's device has finished."""
     stream = None
     if Lambda.is_cuda and Lambda.device.index == gpu_id:
-        cs = torch.cuda.current_stream(Lambda.device).cuda_stream
-        stream = C.c_void_p(cs) if cs else None
+        stream = _native.stream_arg(Lambda.device)
         if sync_current:
             torch.cuda.current_stream(Lambda.device).synchronize()
     elif Lambda.is_cuda:
@@ -197,12 +192,12 @@ class _FwiOps:
             if k > 0:
                 _native.check(L.sepfwi_pseudo_hessian_arm(fn, gpu_id, k))
             try:
-                rc = L.sepfwi_cufd_stream(_ptr(misfit), _ptr(gL), _ptr(gM), _ptr(gD), _ptr(gS), _ptr(Lambda), _ptr(Mu), _ptr(Den),
-                                          _ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
+                rc = L.sepfwi_cufd_stream(_native.ptr(misfit), _native.ptr(gL), _native.ptr(gM), _native.ptr(gD), _native.ptr(gS), _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den),
+                                          _native.ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
                 _native.check(rc)
                 if k > 0:   # ONE buffer [hLambda | hMu | hDen], the unit of the all-reduce under torch.distributed
                     H = torch.empty((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
-                    _native.check(L.sepfwi_get_pseudo_hessian(fn, gpu_id, _ptr(H[0]), _ptr(H[1]), _ptr(H[2])))
+                    _native.check(L.sepfwi_get_pseudo_hessian(fn, gpu_id, _native.ptr(H[0]), _native.ptr(H[1]), _native.ptr(H[2])))
             finally:
                 if k > 0:
                     L.sepfwi_pseudo_hessian_arm(fn, gpu_id, 0)   # disarm, also on error
@@ -352,10 +347,10 @@ class _FwiOps:
         hv = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev) if with_hv else None
         ds = None if dStf is None else _local_rows(dStf, Stf, ids, gdev)
         stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=ds is not None)   # (ds: read with a blocking copy inside the library)
-        args = (_ptr(bufs[2]), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(hv[0]) if with_hv else None, _ptr(hv[1]) if with_hv else None,
-                _ptr(hv[2]) if with_hv else None, _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(dLambda), _ptr(dMu), _ptr(dDen), _ptr(Stf), gpu_id,
+        args = (_native.ptr(bufs[2]), _native.ptr(bufs[0]), _native.ptr(bufs[1]), _native.ptr(hv[0]) if with_hv else None, _native.ptr(hv[1]) if with_hv else None,
+                _native.ptr(hv[2]) if with_hv else None, _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den), _native.ptr(dLambda), _native.ptr(dMu), _native.ptr(dDen), _native.ptr(Stf), gpu_id,
                 int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
-        rc = L.sepfwi_born(*args) if ds is None else L.sepfwi_born_src(*args, _ptr(ds))
+        rc = L.sepfwi_born(*args) if ds is None else L.sepfwi_born_src(*args, _native.ptr(ds))
         _native.check(rc)
         out, off = [], 0
         for n in nrec:
@@ -435,10 +430,10 @@ class _FwiOps:
         g = torch.zeros((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
         misfit = torch.zeros(1, dtype=torch.float32)
         stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=True)   # (w was assembled on this stream; the library may run on its own)
-        vp = [_ptr(t) for t in v] if v else [None, None, None]
-        args = (_ptr(misfit), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(wbuf["ett"]), _ptr(wbuf["vx"]), _ptr(wbuf["vz"]), *vp,
-                _ptr(Lambda), _ptr(Mu), _ptr(Den), _ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
-        rc = L.sepfwi_adjoint_exact_src(*args, _ptr(ds), _ptr(g_loc)) if src else L.sepfwi_adjoint_exact(*args)
+        vp = [_native.ptr(t) for t in v] if v else [None, None, None]
+        args = (_native.ptr(misfit), _native.ptr(g[0]), _native.ptr(g[1]), _native.ptr(g[2]), _native.ptr(wbuf["ett"]), _native.ptr(wbuf["vx"]), _native.ptr(wbuf["vz"]), *vp,
+                _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den), _native.ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+        rc = L.sepfwi_adjoint_exact_src(*args, _native.ptr(ds), _native.ptr(g_loc)) if src else L.sepfwi_adjoint_exact(*args)
         _native.check(rc)
         g = g.to(Lambda.device)
         if src:
@@ -486,11 +481,10 @@ class _FwiOps:
         out = _f32c(d, "d").clone()
         stream = None
         if out.is_cuda and out.device.index == dev:
-            cs = torch.cuda.current_stream(out.device).cuda_stream
-            stream = C.c_void_p(cs) if cs else None
+            stream = _native.stream_arg(out.device)
         elif out.is_cuda:
             torch.cuda.synchronize(out.device)
-        _native.check(_native.lib().sepfwi_condition(_ptr(out), int(bool(transpose)), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
+        _native.check(_native.lib().sepfwi_condition(_native.ptr(out), int(bool(transpose)), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
                                                      str(para_fname).encode(), stream))
         return out
 
@@ -510,8 +504,7 @@ class _FwiOps:
                                  % (names[0], dims[2], want, ts[0].numel()))
         stream = None
         if ts[0].is_cuda and ts[0].device.index == dev:
-            cs = torch.cuda.current_stream(ts[0].device).cuda_stream
-            stream = C.c_void_p(cs) if cs else None
+            stream = _native.stream_arg(ts[0].device)
         elif ts[0].is_cuda:
             torch.cuda.synchronize(ts[0].device)
         return ts, ids, dev, stream
@@ -527,7 +520,7 @@ class _FwiOps:
         (obs, syn), ids, dev, stream = self._data_args((obs, syn), ("obs", "syn"), Shot_ids, para_fname, gpu_id)
         adj = torch.empty_like(syn)
         mis = C.c_float(0.0)
-        _native.check(_native.lib().sepfwi_data_misfit(C.cast(C.byref(mis), C.c_void_p), _ptr(adj), _ptr(obs), _ptr(syn), dev, int(ids.size),
+        _native.check(_native.lib().sepfwi_data_misfit(C.cast(C.byref(mis), C.c_void_p), _native.ptr(adj), _native.ptr(obs), _native.ptr(syn), dev, int(ids.size),
                                                        C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
         return float(mis.value), adj
 
@@ -538,7 +531,7 @@ class _FwiOps:
         `born_adjoint` compose the product J^T (.) J v."""
         (syn, d), ids, dev, stream = self._data_args((syn, d), ("syn", "d"), Shot_ids, para_fname, gpu_id)
         out = torch.empty_like(d)
-        _native.check(_native.lib().sepfwi_data_gn(_ptr(out), _ptr(syn), _ptr(d), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
+        _native.check(_native.lib().sepfwi_data_gn(_native.ptr(out), _native.ptr(syn), _native.ptr(d), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
                                                    str(para_fname).encode(), stream))
         return out
 
@@ -552,7 +545,7 @@ class _FwiOps:
         if ett.is_cuda:     # the library copies on its own stream, ordered only behind the legacy default stream
             torch.cuda.current_stream(ett.device).synchronize()
         dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_set_observed(str(para_fname).encode(), dev, int(shot_id), C.c_void_p(ett.data_ptr()),
+        _native.check(_native.lib().sepfwi_set_observed(str(para_fname).encode(), dev, int(shot_id), _native.ptr(ett),
                                                         int(ett.shape[0]), int(ett.shape[1])))
 
     def set_observed_component(self, para_fname, shot_id, comp, data, gpu_id=0):
@@ -565,7 +558,7 @@ class _FwiOps:
         if data.is_cuda:
             torch.cuda.current_stream(data.device).synchronize()
         dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_set_observed_component(str(para_fname).encode(), dev, int(shot_id), int(comp), C.c_void_p(data.data_ptr()),
+        _native.check(_native.lib().sepfwi_set_observed_component(str(para_fname).encode(), dev, int(shot_id), int(comp), _native.ptr(data),
                                                                   int(data.shape[0]), int(data.shape[1])))
 
     def misfit_parts(self, para_fname, gpu_id=0):
@@ -584,7 +577,7 @@ class _FwiOps:
             j = json.loads(fp.readline())
         out = torch.empty((int(j["nz"]) - int(j["nPad"]), int(j["nx"])), dtype=torch.float32)
         dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_debug_field(str(para_fname).encode(), dev, int(lane), int(which), C.c_void_p(out.data_ptr())))
+        _native.check(_native.lib().sepfwi_debug_field(str(para_fname).encode(), dev, int(lane), int(which), _native.ptr(out)))
         return out
 
     def stats(self, para_fname, gpu_id=0):

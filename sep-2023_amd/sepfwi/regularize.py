@@ -168,19 +168,15 @@ class Regularizer(object):
         L = _native.lib()
         dev = fields[0].device
         nz, nx = fields[0].shape
-        st = torch.cuda.current_stream(dev).cuda_stream
-        pad = 3 - len(names)
-        triple = lambda ts: (C.c_void_p * 3)(*([t.data_ptr() for t in ts] + [None] * pad))
-        floats = lambda d, fill=0.0: (C.c_float * 3)(*([d[n] for n in names] + [fill] * pad))
+        triple, stream = _native.triple, _native.stream_arg(dev)
+        floats = lambda d, fill=0.0: (C.c_float * 3)(*([d[n] for n in names] + [fill] * (3 - len(names))))
         f = [t.contiguous() for t in fields]
         outs = [torch.empty_like(t) for t in f]
-        args = [int(nz), int(nx), self.dx, self.dz, triple(f), triple([self.prior[n] for n in names]),
-                None if self.weight is None else C.c_void_p(self.weight.data_ptr()), floats(self.alpha), floats(self.beta),
-                floats(self.gamma), floats(self.scale, 1.0), self.eps]
-        stream = C.c_void_p(st) if st else None
+        args = [int(nz), int(nx), self.dx, self.dz, triple(f), triple([self.prior[n] for n in names]), _native.ptr(self.weight),
+                floats(self.alpha), floats(self.beta), floats(self.gamma), floats(self.scale, 1.0), self.eps]
         if v is None:
             value = torch.empty((), dtype=torch.float64, device=dev)      # the sum kernel writes it: nothing waits for it here
-            _native.check(L.sepfwi_regularizer(*args, C.c_void_p(value.data_ptr()), triple(outs), stream))
+            _native.check(L.sepfwi_regularizer(*args, _native.ptr(value), triple(outs), stream))
             return value, outs
         vv = [t.contiguous() for t in v]
         _native.check(L.sepfwi_regularizer_hvp(*args, triple(vv), triple(outs), stream))

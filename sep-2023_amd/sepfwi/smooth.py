@@ -19,7 +19,6 @@ definition runs in torch.  The operator acts on the model only: under sepfwi.dis
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import math
 
@@ -159,10 +158,9 @@ class Smoother(object):
         sig = [None if s is None else s.to(device=key[0], dtype=dtype).contiguous() for s in self.sigma]
         if fused:
             inv = [None if s is None else torch.empty_like(s) for s in sig]
-            st = torch.cuda.current_stream(key[0]).cuda_stream
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            ptr = _native.ptr
             _native.check(_native.lib().sepfwi_smooth_plan(self.shape[0], self.shape[1], self.radius[0], self.radius[1], ptr(sig[0]), ptr(sig[1]),
-                                                           ptr(inv[0]), ptr(inv[1]), C.c_void_p(st) if st else None))
+                                                           ptr(inv[0]), ptr(inv[1]), _native.stream_arg(key[0])))
         else:
             one = torch.ones(self.shape, dtype=dtype, device=key[0])
             inv = [None if s is None else 1.0 / _axis_pass(one, s, one, r, dim, True) for s, r, dim in zip(sig, self.radius, (1, 0))]      # N = K 1
@@ -198,12 +196,10 @@ class Smoother(object):
         dev = ts[0].device
         sigx, sigz, invx, invz = self.plan(dev, torch.float32)
         outs = [torch.empty_like(t) for t in ts]
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        triple = lambda xs: (C.c_void_p * 3)(*([x.data_ptr() for x in xs] + [None] * (3 - len(xs))))
+        ptr, triple = _native.ptr, _native.triple
         _native.check(_native.lib().sepfwi_smooth_apply(self.shape[0], self.shape[1], self.radius[0], self.radius[1], ptr(sigx), ptr(sigz),
                                                         ptr(invx), ptr(invz), 1 if transpose else 0, triple(ts), triple(outs),
-                                                        C.c_void_p(st) if st else None))
+                                                        _native.stream_arg(dev)))
         return outs
 
     def _torch_apply(self, u, transpose):

@@ -96,6 +96,33 @@ def test_value_or_gradient_alone_and_mixed_pointers(hip_ops):
     assert _same(R._host(mixed[:2]), g[:2])
 
 
+def test_workspace_is_accounted_and_released(hip_ops):
+    """the block partials and the value are the regulariser's only device memory between calls: (blocks + 1) doubles per (device,
+    stream), blocks = ceil(129 / 64) ceil(33 / 4) 3 = 81, allocated once and freed by sepfwi_release_all"""
+    import ctypes as C
+    L = _lib(hip_ops)
+    c = R.case((33, 129), "full")
+    keep, args = R._model_args(c, True)
+
+    def live():
+        dev, pin = C.c_longlong(0), C.c_longlong(0)
+        assert L.sepfwi_debug_live_bytes(C.byref(dev), C.byref(pin)) == 0
+        return dev.value
+
+    L.sepfwi_release_all()
+    start = live()
+    val = C.c_double(-1.0)
+    assert L.sepfwi_regularizer(*args, C.cast(C.byref(val), C.c_void_p), None, None) == 0, L.sepfwi_last_error()
+    first = live()
+    print("regulariser workspace at 33x129: %d bytes (expected %d)" % (first - start, (81 + 1) * 8))
+    assert first - start == (81 + 1) * 8 == 656
+    again = C.c_double(-1.0)
+    assert L.sepfwi_regularizer(*args, C.cast(C.byref(again), C.c_void_p), None, None) == 0 and again.value == val.value
+    assert live() == first
+    L.sepfwi_release_all()
+    assert live() == start
+
+
 def test_identities_that_need_no_tolerance(hip_ops):
     L = _lib(hip_ops)
     grid = (33, 129)
