@@ -9,6 +9,7 @@ and the last one uses the unfiltered data.
     python examples/multiscale_fwi.py --niter 4 [--bands 3]
     python examples/multiscale_fwi.py --gauss-newton --niter 2 [--inner 3]
     python examples/multiscale_fwi.py --envelope [--gauss-newton]
+    python examples/multiscale_fwi.py --w2
 
 --gauss-newton (off by default; without it every printed line is what it was): every stage runs --niter truncated Gauss-Newton steps in
 the Lame parameters instead of L-BFGS-B -- the band's own parameter file serves the conditioned misfit, its exact gradient
@@ -22,6 +23,11 @@ stages -- the stage for data whose low band is noise, where the first low-pass s
 after every iteration of that stage.  With --gauss-newton the stage runs as truncated Gauss-Newton steps on the envelope misfit's own
 Gauss-Newton product J^T C^T D^T Z D C J v.  Whether the stage helps depends on the starting model: on this example's 2 % anomalies the
 waveform misfit does not cycle-skip, and the stage is a demonstration of the plumbing, not of a rescue.
+
+--w2 (off by default; without it every printed line is what it was): the same first stage on the trace-wise quadratic Wasserstein misfit
+(parameter key "if_w2_misfit": every trace becomes a density in time, softplus(3 x / max |observed trace|), and the misfit is the squared
+transport distance between the synthetic and the observed density) -- the other standard remedy for cycle-skipped data.  L-BFGS-B only:
+the misfit has no Gauss-Newton product here, and --w2 with --gauss-newton is refused.
 """
 import argparse
 import os
@@ -40,10 +46,11 @@ from sepfwi.obj_wrapper import PyTorchObjective, minimize_lbfgsb  # noqa: E402
 FILTER_TABLE = [[0.0, 0.0, 2.0, 2.5], [0.0, 0.0, 2.0, 3.5], [0.0, 0.0, 2.0, 4.5], [0.0, 0.0, 2.0, 5.5], [0.0, 0.0, 2.0, 6.5],
                 [0.0, 0.0, 2.0, 7.5]]    # Main-001-...py:46-51
 ENVELOPE = "envelope"                    # in the place of a band: the stage on the envelope misfit (--envelope)
+W2 = "w2"                                # ... and the stage on the W2 misfit (--w2)
 
 
 def stage_name(band):
-    return "envelope misfit" if band == ENVELOPE else ("low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies")
+    return "envelope misfit" if band == ENVELOPE else "W2 misfit" if band == W2 else ("low-pass %g-%g Hz" % (band[2], band[3]) if band else "all frequencies")
 
 
 def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping=0.05, rtol=0.1, say=None):
@@ -86,10 +93,13 @@ def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping
     return m, f_start, f, taken
 
 
-def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False):
+def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False, w2=False):
     """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage.
     gauss_newton: every stage is `niter` truncated Gauss-Newton steps (at most `inner` conjugate-gradient iterations each) on the stage's
-    own parameter file instead of L-BFGS-B (gauss_newton_stage).  envelope: a first stage on the envelope misfit, band = ENVELOPE in the log."""
+    own parameter file instead of L-BFGS-B (gauss_newton_stage).  envelope: a first stage on the envelope misfit, band = ENVELOPE in the log; w2: a first stage on
+    the W2 misfit, band = W2 (L-BFGS-B only)."""
+    if w2 and gauss_newton:
+        raise ValueError("--w2 with --gauss-newton: the W2 misfit has no Gauss-Newton product (the library refuses it under if_w2_misfit)")
     dev = torch.device(device)
     nx, nz, dx, dz, dt, nt, f0, nPml = 201, 101, 20.0, 20.0, 0.002, 1501, 10.0, 32
     vp = np.ones((nz, nx), np.float32) * 4000.0
@@ -116,6 +126,8 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
         fn = os.path.join(work, "para_%s.json" % tag)
         if band == ENVELOPE:
             ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_envelope_misfit=True)
+        elif band == W2:
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_w2_misfit=True)
         else:
             ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band)
         return fn
@@ -127,6 +139,8 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
     bands = FILTER_TABLE[len(FILTER_TABLE) - n_bands:] + [None]      # the widest n_bands rows: a 10 Hz Ricker has little below 4 Hz
     if envelope:
         bands = [ENVELOPE] + bands
+    if w2:
+        bands = [W2] + bands
     if gauss_newton:
         lame = lambda c: [((pad(c[0]) ** 2 - 2.0 * pad(c[1]) ** 2) * pad(c[2]) / 1e6).contiguous(), (pad(c[1]) ** 2 * pad(c[2]) / 1e6).contiguous(), pad(c[2])]
         m, mask = lame(cur), torch.tensor(Mask, device=dev)
@@ -148,7 +162,7 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
         fun, jac = obj.fun, obj.jac
         f_start = fun(obj.x0)
         history = []      # the envelope stage prints its misfit after every iteration (the value of the iterate: no further evaluation)
-        each = (lambda x: (history.append(fun(x)), print("  iteration %d: envelope misfit %.4e" % (len(history), history[-1]), flush=True))) if (band == ENVELOPE and verbose) else None
+        each = (lambda x: (history.append(fun(x)), print("  iteration %d: %s %.4e" % (len(history), stage_name(band), history[-1]), flush=True))) if (band in (ENVELOPE, W2) and verbose) else None
         res = minimize_lbfgsb(fun, obj.x0, jac, bounds=obj.bounds, callback=each, maxiter=niter, maxcor=5, ftol=1e-12, gtol=1e-16, maxfun=1500, maxls=6)
         n = nz * nx
         cur = [res.x[i * n:(i + 1) * n].reshape(nz, nx).astype(np.float32) for i in range(3)]
@@ -171,5 +185,6 @@ if __name__ == "__main__":
     ap.add_argument("--gauss-newton", action="store_true", help="truncated Gauss-Newton steps on every band's conditioned misfit instead of L-BFGS-B (--niter: steps per band)")
     ap.add_argument("--inner", type=int, default=3, help="with --gauss-newton: conjugate-gradient iterations per step (cap)")
     ap.add_argument("--envelope", action="store_true", help="a first stage on the envelope misfit (parameter key if_envelope_misfit) before the band stages; prints the misfit per iteration")
+    ap.add_argument("--w2", action="store_true", help="a first stage on the W2 misfit (parameter key if_w2_misfit) before the band stages; prints the misfit per iteration; not with --gauss-newton")
     a = ap.parse_args()
-    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope)
+    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope, w2=a.w2)

@@ -97,6 +97,23 @@ int sepfwi_device_count(void);
  *                composes with if_win and filter; with "conditioning": "reference" it is parsed and ignored like the other four.
  *                Refused (SEPFWI_EINVAL): together with if_cross_misfit, with if_src_update, or with weights other than (1, 0, 0).
  *                Absent or false: every launch, allocation and bit as before.
+ *                "if_w2_misfit": true, "w2_beta": b (an extension that no reference run pins) -- the trace-wise quadratic Wasserstein
+ *                (optimal-transport) misfit of Engquist & Froese 2014 and Yang et al. 2018, the other remedy for cycle-skipped data.
+ *                Per trace, o = C obs, s = C syn with n = nSteps samples, t_i = i dt, i = 1 ... n - 1 (sample 0 carries no mass):
+ *                  A = max |o| over the trace (A == 0: a dead trace, misfit 0 and adjoint source 0);
+ *                  q(x) = softplus(b x / A);  f = q(s) / sum q(s),  g = q(o) / sum q(o);  F, G their prefix sums (G_0 = 0);
+ *                  j(i) the first j >= 1 with G_j >= F_i;  T_i = t_{j-1} + dt (F_i - G_{j-1}) / g_j;  W = sum_i f_i (t_i - T_i)^2;
+ *                  misfit = 0.5 sum_shots sum_r w_r W_r,  w_r = weights[r] * src_weight under if_win, else 1 (the window's amplitude
+ *                  weight cancels in the densities, so the trace weight is explicit -- the rule of if_cross_misfit);
+ *                  adjoint source = -d misfit / d syn = -0.5 C^T w dW / ds, the exact derivative at fixed j (csrc/w2_misfit.hpp).
+ *                The scale A comes from the observed trace alone: a constant under differentiation, and a synthetic of the wrong
+ *                amplitude is still penalised.  w2_beta in (0, 16], default 3 (the smallest whole value at which the misfit of a
+ *                two-arrival 15 Hz Ricker trace grows monotonically over 2.25 periods of shift).  ARITHMETIC: the map amplifies a
+ *                relative 1e-7 of its inputs to 1e-5 of the adjoint source, so everything from q onwards is double and the adjoint
+ *                source is rounded to float32 once; no atomics, the same input gives the same bits.  A live conditioning key: it
+ *                composes with if_win and filter; with "conditioning": "reference" it is parsed and ignored.  Refused
+ *                (SEPFWI_EINVAL): together with if_cross_misfit, if_envelope_misfit, if_src_update or weights other than (1, 0, 0);
+ *                a w2_beta outside (0, 16].  Absent or false: every launch, allocation and bit as before.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.
@@ -185,8 +202,8 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
  *                       symmetric, non-negative, the full Hessian where the residual vanishes; the second-order term of the envelope map is
  *                       left out.  d_* stay the raw gathers, bit for bit those of the file without the key.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, perturbation, stf or para_fname; a bad shot list; the product
- * (hv_* set) under if_cross_misfit (a misfit that is not quadratic in the data) or if_src_update (a matching filter that depends on the
- * synthetics) -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
+ * (hv_* set) under if_cross_misfit (a misfit that is not quadratic in the data), if_src_update (a matching filter that depends on the
+ * synthetics) or if_w2_misfit (no least-squares Gauss-Newton form; the message names the key) -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
  * background model only.  The session's observed data, its misfit, sepfwi_get_misfit_parts and the pseudo-Hessian state are neither
  * read nor written; sepfwi_get_stats afterwards describes this call (fwd_ms: the Born time loops).
  * Schedule: one shot after the other on the call's stream (hip_stream, NULL: the session's own), synchronous; the batched multi-lane
@@ -223,6 +240,8 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
  * Envelope misfit (if_envelope_misfit; D, H, e as under sepfwi_cufd and sepfwi_born): the product is g = P J^T C^T D^T Z D C J P v
  *   (v^T g = |Z D C J P v|^2); the gradient mode returns the exact gradient on Omega of 1/2 |Z (e(C obs) - e(C syn))|^2 and that value in
  *   *misfit; the w mode is untouched and stays in raw data space (sepfwi_data_misfit / sepfwi_data_gn give the operators to compose).
+ * W2 misfit (if_w2_misfit, as under sepfwi_cufd): the gradient mode returns the exact gradient on Omega of 1/2 sum_r w_r W_r and that value
+ *   in *misfit; the w mode is untouched; the product (v set) is refused with SEPFWI_EINVAL, as sepfwi_born refuses it.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
  * shot list; if_cross_misfit or if_src_update in any mode; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
  * gradient of the source time function is returned by sepfwi_adjoint_exact_src (below), not here.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
@@ -278,12 +297,12 @@ int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, con
  *   sepfwi_data_misfit   *misfit = the file's misfit of (obs, syn), halved as sepfwi_cufd reports it; adj (may be NULL) = the raw-space
  *       adjoint source a = -d misfit / d syn, what the backward pass injects:  C^T Z (C obs - C syn) for the L2 misfit (C = 1 without a
  *       conditioning key),  the adjoint source of the normalised cross-correlation under if_cross_misfit,  C^T D^T Z (e(C obs) - e(C syn))
- *       under if_envelope_misfit.  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot, as
+ *       under if_envelope_misfit,  -1/2 C^T w dW / d(C syn) under if_w2_misfit (W, w as under sepfwi_cufd).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot, as
  *       a gradient call computes it: the misfit is that of the updated synthetics, a is taken with the filter held fixed.  SEPFWI_EINVAL
  *       under weights other than (1, 0, 0).
  *   sepfwi_data_gn       out = the Gauss-Newton operator of the misfit at syn applied to d:  C^T Z C d for the L2 misfit (syn is not
  *       read),  C^T D^T Z D C d under if_envelope_misfit, D at C syn.  Symmetric and non-negative.  SEPFWI_EINVAL under if_cross_misfit,
- *       if_src_update and under weights other than (1, 0, 0).
+ *       if_src_update, if_w2_misfit (the transport misfit has no least-squares form in the data) and under weights other than (1, 0, 0).
  */
 int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int gpu_id, int group_size, const int *shot_ids,
                        const char *para_fname, void *hip_stream);

@@ -18,6 +18,7 @@
 
 #include "conditioning.hpp"
 #include "device_alloc.hpp"
+#include "w2_misfit.hpp"
 
 namespace sepfwi {
 
@@ -466,6 +467,21 @@ void Conditioner::envelope_residual(hipStream_t st, const float *obs, const floa
     launch(k_env_sum, dim3(1), st, nrec, env_sum_.get(), acc);
     hilbert(st, b, b, nrec);
     launch(k_env_combine, time_grid(nrec), st, nt_, nrec, res, b, 1.0f);
+}
+
+void Conditioner::ensure_w2_buffers() {
+    if (w2_.get()) return;
+    w2_ = DevBuf<double>(&bytes_, kW2Planes * (size_t)nt_ * cap_);
+    w2_sum_ = DevBuf<double>(&bytes_, (size_t)cap_);
+}
+
+void Conditioner::w2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight,
+                              float dt, double beta, double *acc) {
+    if (idle(nrec)) return;
+    ensure_w2_buffers();
+    launch_w2_trace(st, nt_, nrec, obs, syn, res, weights, src_weight, dt, beta, w2_.get(), (size_t)nt_ * cap_, w2_sum_.get());
+    launches_++;
+    launch(k_env_sum, dim3(1), st, nrec, w2_sum_.get(), acc);  // the traces in a fixed order
 }
 
 void Conditioner::envelope_scattered(hipStream_t st, const float *syn, const float *d, float *res, int nrec, float sign) {

@@ -1,5 +1,5 @@
 // conditioning.hpp -- data-conditioning chain of the misfit (conditioning.hip): windows, band-pass (hipFFT), normalised
-// cross-correlation misfit, envelope misfit.  All gathers are [rec][nt] float32 device arrays.
+// cross-correlation misfit, envelope misfit, trace-wise W2 misfit.  All gathers are [rec][nt] float32 device arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +44,12 @@ class Conditioner {
     // *acc += -2 sum_r <obs,syn>_r / (|obs|_r |syn|_r) w_r ; res = the adjoint source.  weights may be null (all ones).
     void cross_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight,
                         double *acc);
+    // ---- trace-wise quadratic Wasserstein misfit (parameter key if_w2_misfit; w2_misfit.hpp holds the definition) ----
+    // *acc += sum_r w_r W_r (the driver halves the total), W_r the squared transport distance between the softplus densities of syn and obs
+    // in time; res = -1/2 w_r dW_r / d syn, the sign of l2_residual.  w_r = weights[r] * src_weight, or 1 where weights is null (the rule of
+    // cross_residual).  Double from the densities onwards, res rounded once; no atomics.  obs, syn and res: three different gathers.
+    void w2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight, float dt,
+                     double beta, double *acc);
     // source_update (utilities.cu:1170-1281, cuda_spectrum_update :905-977): the source-signature update as a matching filter.
     // Both gathers zero-padded to 2 nt and end-tapered over the padded length (ratio 0.01); per frequency one coefficient
     // coef(f) = sum_r conj(C_r) O_r / (sum_r |C_r|^2 + 1e-6), kept for the adjoint step; the synthetic spectra are multiplied by
@@ -59,6 +65,8 @@ class Conditioner {
     // three [cap][nt] scratch gathers (H obs or H d, H syn, (H syn) rho) and the per-trace sums of the envelope misfit, allocated on
     // first use: a session whose file does not set the key never holds them
     void ensure_envelope_buffers();
+    // five [cap][nt] double scratch planes (the CDFs, the densities, c) and the per-trace w_r W_r of the W2 misfit, allocated on first use
+    void ensure_w2_buffers();
     long long device_bytes() const { return bytes_; }  // what the buffers below hold
     // What the methods above have issued so far: one per kernel launch and one per hipFFT exec (a plan's creation is none).  Per gather
     // with channels:
@@ -69,6 +77,7 @@ class Conditioner {
     //   source_update_adj                         6   embed, R2C, conj(coef), C2R, taper, crop
     //   envelope_residual                        19   difference, 2 hilbert, residual, sum, hilbert, combination
     //   envelope_scattered                       17   2 hilbert, linearised residual, hilbert, combination
+    //   w2_residual                               2   the traces (one block each), their sum
     long long launches() const { return launches_; }
 
   private:
@@ -100,6 +109,7 @@ class Conditioner {
     DevBuf<float2> spec2_, coef_;  // second padded gather / spectrum and the nt + 1 matching-filter coefficients (source update)
     DevBuf<float> env_;            // envelope misfit: 3 x [cap][nt]
     DevBuf<double> env_sum_;       // ... and sum rho^2 per trace
+    DevBuf<double> w2_, w2_sum_;   // W2 misfit: kW2Planes x [cap][nt], and w_r W_r per trace
     std::map<int, Plans> plans_;  // by number of traces
 };
 

@@ -43,6 +43,12 @@ Params parse_params(const std::string &text) {
     if (j.has("if_src_update")) p.if_src_update = j.at("if_src_update").as_bool("if_src_update");
     if (j.has("if_cross_misfit")) p.if_cross_misfit = j.at("if_cross_misfit").as_bool("if_cross_misfit");
     if (j.has("if_envelope_misfit")) p.if_envelope_misfit = j.at("if_envelope_misfit").as_bool("if_envelope_misfit");
+    if (j.has("if_w2_misfit")) p.if_w2_misfit = j.at("if_w2_misfit").as_bool("if_w2_misfit");
+    if (j.has("w2_beta")) {
+        p.w2_beta = j.at("w2_beta").as_number("w2_beta");
+        if (!(std::isfinite(p.w2_beta) && p.w2_beta > 0.0 && p.w2_beta <= 16.0))
+            throw std::invalid_argument("parameter file: w2_beta must be finite, above 0 and at most 16");
+    }
     p.has_filter = j.has("filter");
     if (p.has_filter) {
         const JsonValue &f = j.at("filter");
@@ -56,7 +62,7 @@ Params parse_params(const std::string &text) {
         const std::string c = j.at("conditioning").as_string("conditioning");
         if (c == "reference") {
             p.conditioning_reference = true;
-            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = false;
+            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = p.if_w2_misfit = false;
         } else if (c != "live") {
             throw std::runtime_error("parameter JSON: conditioning must be \"live\" or \"reference\"");
         }
@@ -105,9 +111,14 @@ Params parse_params(const std::string &text) {
     if (p.if_envelope_misfit && (p.if_cross_misfit || p.if_src_update))
         throw std::invalid_argument(std::string("parameter file: if_envelope_misfit together with ") + (p.if_cross_misfit ? "if_cross_misfit" : "if_src_update") +
                                     " is not supported");
-    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit)) {
+    // the W2 misfit is one misfit kind among three, and its densities are normalised trace by trace: a matching filter fitted to the
+    // gathers has no meaning for it either
+    if (p.if_w2_misfit && (p.if_cross_misfit || p.if_envelope_misfit || p.if_src_update))
+        throw std::invalid_argument(std::string("parameter file: if_w2_misfit together with ") +
+                                    (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : "if_src_update")) + " is not supported");
+    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit)) {
         const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
-        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : "if_envelope_misfit")));
+        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : "if_w2_misfit"))));
         throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
                                     " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
     }

@@ -24,7 +24,13 @@ struct Params {
     // e(x) = x^2 + (H x)^2 of the conditioned gathers instead of the gathers.  A live conditioning key like the four above; refused
     // together with if_cross_misfit or if_src_update.
     bool if_envelope_misfit = false;
-    // optional key "conditioning": "live" (default) -- the five keys above switch their stage on; "reference" -- they are parsed
+    // optional keys "if_w2_misfit" / "w2_beta" (no counterpart in the reference; w2_misfit.hpp): the misfit is the trace-wise quadratic
+    // Wasserstein distance between the softplus densities of the conditioned gathers, softplus(w2_beta x / max |obs trace|); w2_beta in
+    // (0, 16], default 3.  A live conditioning key like the five above; refused together with if_cross_misfit, if_envelope_misfit,
+    // if_src_update or joint weights.
+    bool if_w2_misfit = false;
+    double w2_beta = 3.0;
+    // optional key "conditioning": "live" (default) -- the keys above switch their stage on; "reference" -- they are parsed
     // and validated like the reference does and then IGNORED like its driver does (every call site commented out,
     // libCUFD.cu:353-457): results are those of a file without them.  if_win_key keeps what the file said, because the survey
     // file must carry win_start / win_end whenever if_win is set, used or not (Src_Rec.cu:144-174).

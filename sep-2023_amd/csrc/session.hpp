@@ -98,7 +98,8 @@ class Session {
     //                 if_src_update also updated) in place.  out: the raw-space adjoint source.  The misfit's sum is added to *acc.
     //   gn_chain      d: the raw gather, conditioned in place.  bg: the raw background gather, conditioned in place, under
     //                 if_envelope_misfit; else null.  out = sign C^T Z C d, or sign C^T D^T Z D C d.
-    // ALIASING: the gathers of one call are all different (the envelope kernels read the other two while they write out).  The callers
+    //                 The misfit kind is the file's: L2, if_cross_misfit, if_envelope_misfit or if_w2_misfit.
+    // ALIASING: the gathers of one call are all different (the envelope and W2 kernels read the other two while they write out).  The callers
     // pass the session's scratch gathers xpose_, xpose2_, xpose3_.
     void misfit_chain(hipStream_t st, const float *obs_c, float *syn, float *out, int shot_id, int nrec, double *acc);
     void gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign);

@@ -53,6 +53,9 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     std::lock_guard<std::mutex> lock(mu_);
     const bool want_hv = hv_Lambda != nullptr, have_v = dLambda != nullptr;
     // refusals first: nothing is touched
+    if (want_hv && par_.if_w2_misfit)
+        throw std::invalid_argument("born: the Gauss-Newton product is not defined under if_w2_misfit (the transport misfit has no least-squares form in the data); "
+                                    "the scattered gathers alone are served (hv_* = NULL)");
     if (want_hv && (par_.if_cross_misfit || par_.if_src_update))
         throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit with if_cross_misfit or if_src_update (not "
                                     "quadratic in the data); if_win and filter are served; the scattered gathers alone are served under every key (hv_* = NULL)");

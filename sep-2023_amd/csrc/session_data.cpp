@@ -12,11 +12,11 @@
 //   condition     sepfwi_condition: C or C^T in place
 //   data_misfit   the file's misfit of (obs, syn) and the raw-space adjoint source a = -d misfit / d syn: C^T Z (C obs - C syn) under an L2
 //                 file, the adjoint source of the normalised cross-correlation under if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under
-//                 if_envelope_misfit.  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
+//                 if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (w2_misfit.hpp).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
 //                 as a gradient call computes it; the misfit is that of the updated synthetics and a is taken with the filter held fixed
 //                 (nothing is carried from one shot or call to the next).
 //   data_gn       the Gauss-Newton operator of the misfit in data space at syn: C^T Z C d, or C^T D^T Z D C d under if_envelope_misfit.
-//                 Refused under if_cross_misfit and if_src_update (not a least-squares misfit of the data), as the products are.
+//                 Refused under if_cross_misfit, if_src_update and if_w2_misfit (not a least-squares misfit of the data), as the products are.
 // A file without a live conditioning key has C = 1 and no conditioner: its misfit runs through the residual kernel of its gradient calls
 // (time-major, lane 0's gather and residual buffers), its operator is Z.  A joint misfit (misfit_w_*) is refused: it is not one of axial
 // strain alone.  The session's observed store, misfit, misfit parts and call statistics are neither read nor written; the callers' inputs
@@ -60,6 +60,8 @@ void Session::misfit_chain(hipStream_t st, const float *obs_c, float *syn, float
         cond_->cross_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
     else if (par_.if_envelope_misfit)
         cond_->envelope_residual(st, obs_c, syn, out, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
+    else if (par_.if_w2_misfit)  // the trace weights are explicit (the window's amplitude cancels in the densities): the rule of cross_residual
+        cond_->w2_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, par_.dt, par_.w2_beta, acc);
     else
         cond_->l2_residual(st, obs_c, syn, out, nrec, acc);
     if (par_.if_src_update) cond_->source_update_adj(st, out, nrec, par_.dt);  // libCUFD.cu:430-433
@@ -189,8 +191,8 @@ void Session::data_misfit(float *misfit, float *adj, const float *obs, const flo
 
 void Session::data_gn(float *out, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream) {
     std::lock_guard<std::mutex> lock(mu_);
-    if (par_.if_cross_misfit || par_.if_src_update)
-        throw std::invalid_argument(std::string("data_gn: not defined under ") + (par_.if_cross_misfit ? "if_cross_misfit" : "if_src_update") +
+    if (par_.if_cross_misfit || par_.if_src_update || par_.if_w2_misfit)
+        throw std::invalid_argument(std::string("data_gn: not defined under ") + (par_.if_cross_misfit ? "if_cross_misfit" : (par_.if_src_update ? "if_src_update" : "if_w2_misfit")) +
                                     " (not a least-squares misfit of the data); if_win, filter and if_envelope_misfit are served");
     if (joint_) throw std::invalid_argument("data_gn: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);

@@ -22,8 +22,8 @@ PROBES_LIB_PATH = os.path.join(_ROOT, "libsepfwi_probes.so")
 FAULT_LIB_PATH = os.path.join(_ROOT, "libsepfwi_fault.so")
 VARIANTS = {"default": (LIB_PATH, []), "probes": (PROBES_LIB_PATH, ["-DSEPFWI_PROBES"]), "fault": (FAULT_LIB_PATH, ["-DSEPFWI_PK_FAULT=17"])}
 PUBLIC_OPTIONS = ("bwd_fuse", "batch", "img_every", "quiet_skip", "obs_cache_mb", "probe")
-SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
-HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
+SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "w2_misfit.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
+HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "w2_misfit.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
            os.path.join("..", "..", "include", "sepfwi.h")]
 
 _libs = {}

@@ -36,7 +36,7 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
             das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None,
-            if_envelope_misfit=False):
+            if_envelope_misfit=False, if_w2_misfit=False, w2_beta=None):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
@@ -48,7 +48,11 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
     misfit and adjoint source (csrc/geophone.hpp; defaults ett 1, vx 0, vz 0).  Only the keys given are written.
     if_envelope_misfit (extension): the misfit compares the squared envelopes of the conditioned gathers instead of the gathers
     (include/sepfwi.h, sepfwi_cufd); refused by the library together with if_cross_misfit, if_src_update or misfit_weights.  Written
-    only when set."""
+    only when set.
+    if_w2_misfit / w2_beta (extension): the misfit is the trace-wise quadratic Wasserstein distance between the softplus densities of the
+    conditioned gathers, softplus(w2_beta x / max |observed trace|) (include/sepfwi.h, sepfwi_cufd); w2_beta in (0, 16], the library's
+    default 3.  Refused by the library together with if_cross_misfit, if_envelope_misfit, if_src_update or misfit_weights.  Each key is
+    written only when set."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
     if if_win:
@@ -64,6 +68,12 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
         para["if_cross_misfit"] = True
     if if_envelope_misfit:
         para["if_envelope_misfit"] = True
+    if if_w2_misfit:
+        para["if_w2_misfit"] = True
+    if w2_beta is not None:
+        if not (np.isfinite(w2_beta) and 0 < w2_beta <= 16):
+            raise ValueError("w2_beta must be in (0, 16]")
+        para["w2_beta"] = float(w2_beta)
     if das_fiber != "horizontal":
         if das_fiber != "vertical":
             raise ValueError("das_fiber must be 'horizontal' or 'vertical'")
