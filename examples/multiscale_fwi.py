@@ -10,6 +10,7 @@ and the last one uses the unfiltered data.
     python examples/multiscale_fwi.py --gauss-newton --niter 2 [--inner 3]
     python examples/multiscale_fwi.py --envelope [--gauss-newton]
     python examples/multiscale_fwi.py --w2
+    python examples/multiscale_fwi.py --robust {huber,cauchy} --robust-delta X [--spikes M] [--gauss-newton]
 
 --gauss-newton (off by default; without it every printed line is what it was): every stage runs --niter truncated Gauss-Newton steps in
 the Lame parameters instead of L-BFGS-B -- the band's own parameter file serves the conditioned misfit, its exact gradient
@@ -28,6 +29,13 @@ waveform misfit does not cycle-skip, and the stage is a demonstration of the plu
 (parameter key "if_w2_misfit": every trace becomes a density in time, softplus(3 x / max |observed trace|), and the misfit is the squared
 transport distance between the synthetic and the observed density) -- the other standard remedy for cycle-skipped data.  L-BFGS-B only:
 the misfit has no Gauss-Newton product here, and --w2 with --gauss-newton is refused.
+
+--robust huber|cauchy with --robust-delta X (off by default; without it every printed line is what it was): EVERY stage runs on the robust
+misfit of its band (parameter keys "robust_misfit" / "robust_delta", composed with the band's filter: the Huber or Cauchy penalty of the
+conditioned residual with the threshold X times the 0.9-quantile of every observed trace's |samples|).  --robust-delta has no default, as in
+the library: it depends on the data's noise.  With --gauss-newton the steps use the misfit's IRLS Gauss-Newton product.  --spikes M writes M
+spikes of 100 x the trace's peak into every observed trace after the data are modelled (interrogator spikes: what the robust misfit is for),
+with or without --robust: the pair of runs shows what the spikes do to the L2 inversion and what is left of that under the robust one.
 """
 import argparse
 import os
@@ -93,11 +101,15 @@ def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping
     return m, f_start, f, taken
 
 
-def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False, w2=False):
+def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False, w2=False, robust=None,
+        robust_delta=None, spikes=0):
     """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage.
     gauss_newton: every stage is `niter` truncated Gauss-Newton steps (at most `inner` conjugate-gradient iterations each) on the stage's
     own parameter file instead of L-BFGS-B (gauss_newton_stage).  envelope: a first stage on the envelope misfit, band = ENVELOPE in the log; w2: a first stage on
-    the W2 misfit, band = W2 (L-BFGS-B only)."""
+    the W2 misfit, band = W2 (L-BFGS-B only).  robust ("huber" | "cauchy") with robust_delta: every band stage on that robust misfit; spikes: that many
+    spikes of 100 x the trace's peak in every observed trace."""
+    if robust and robust_delta is None:
+        raise ValueError("--robust needs --robust-delta (there is no default: the threshold depends on the data's noise)")
     if w2 and gauss_newton:
         raise ValueError("--w2 with --gauss-newton: the W2 misfit has no Gauss-Newton product (the library refuses it under if_w2_misfit)")
     dev = torch.device(device)
@@ -129,11 +141,20 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
         elif band == W2:
             ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_w2_misfit=True)
         else:
-            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band)
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band,
+                       robust_misfit=robust if tag != "obs" else None, robust_delta=robust_delta if (robust and tag != "obs") else None)
         return fn
 
     pad = lambda m: torch.tensor(ft.padding_numpy_array(m, nPml, nPad), dtype=torch.float32, device=dev)
     M.FWI_obscalc(pad(vp), pad(vs), pad(rho), Stf, para_for("obs", None))(Shot_ids, ngpu=1)   # raw gathers, written once
+    if spikes:      # the axial-strain files again, with spikes
+        rng = np.random.default_rng(0)
+        for sid in range(len(src_x)):
+            g = ft.read_shot_gather(data_dir, "ett", sid, nt).copy()
+            for r in range(g.shape[0]):
+                at = 1 + rng.choice(nt - 1, size=spikes, replace=False)
+                g[r, at] = (100.0 * np.abs(g[r]).max() * rng.choice([-1.0, 1.0], size=spikes)).astype(np.float32)
+            g.tofile(os.path.join(data_dir, "Shot_ett%d.bin" % sid))      # (no stage's session has read the files yet)
 
     log = []
     bands = FILTER_TABLE[len(FILTER_TABLE) - n_bands:] + [None]      # the widest n_bands rows: a 10 Hz Ricker has little below 4 Hz
@@ -186,5 +207,8 @@ if __name__ == "__main__":
     ap.add_argument("--inner", type=int, default=3, help="with --gauss-newton: conjugate-gradient iterations per step (cap)")
     ap.add_argument("--envelope", action="store_true", help="a first stage on the envelope misfit (parameter key if_envelope_misfit) before the band stages; prints the misfit per iteration")
     ap.add_argument("--w2", action="store_true", help="a first stage on the W2 misfit (parameter key if_w2_misfit) before the band stages; prints the misfit per iteration; not with --gauss-newton")
+    ap.add_argument("--robust", choices=["huber", "cauchy"], default=None, help="every stage on this robust misfit of its band (parameter key robust_misfit); needs --robust-delta")
+    ap.add_argument("--robust-delta", type=float, default=None, help="with --robust: the threshold in units of every observed trace's 0.9-quantile of |samples| (parameter key robust_delta; no default)")
+    ap.add_argument("--spikes", type=int, default=0, help="write this many spikes of 100 x the trace's peak into every observed trace")
     a = ap.parse_args()
-    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope, w2=a.w2)
+    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope, w2=a.w2, robust=a.robust, robust_delta=a.robust_delta, spikes=a.spikes)

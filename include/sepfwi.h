@@ -114,6 +114,25 @@ int sepfwi_device_count(void);
  *                composes with if_win and filter; with "conditioning": "reference" it is parsed and ignored.  Refused
  *                (SEPFWI_EINVAL): together with if_cross_misfit, if_envelope_misfit, if_src_update or weights other than (1, 0, 0);
  *                a w2_beta outside (0, 16].  Absent or false: every launch, allocation and bit as before.
+ *                "robust_misfit": "huber" | "cauchy", "robust_delta": c, "robust_quantile": q (an extension that no reference run pins) --
+ *                a robust misfit for data with spikes, dropouts and fading channels (Guitton & Symes 2003; Aravkin et al. 2011).  Per
+ *                trace, o = C obs, s = C syn, the n = nSteps - 1 live samples i = 1 ... nSteps - 1 (csrc/robust_misfit.hpp):
+ *                  A = the order statistic of index floor(q (n - 1)), from the smallest, of |o_i| -- exact, no interpolation
+ *                  (A == 0: a dead trace, misfit 0 and adjoint source 0);  delta = c A;  r = o - s;  u = r / delta;
+ *                  huber:  phi = delta^2 u^2 / 2 for |u| <= 1, else delta^2 (|u| - 1/2);  w = min(1, 1 / |u|)
+ *                  cauchy: phi = delta^2 / 2 log1p(u^2);  w = 1 / (1 + u^2)
+ *                  misfit = sum_shots sum_r sum_i phi;  adjoint source = -d misfit / d syn = C^T Z (r w).
+ *                The scale A comes from the observed trace alone: a constant under differentiation.  The Gauss-Newton products use the
+ *                IRLS form C^T Z diag(w) Z C with w at the background -- symmetric, non-negative, the L2 operator where |r| <= delta
+ *                (huber); not the true Hessian (0 on huber's outliers, indefinite for cauchy).  robust_delta is REQUIRED with the key
+ *                (finite, > 0; no default: it depends on the data's noise); robust_quantile in (0, 1], default 0.9 (spikes and dropouts
+ *                fill far less than a tenth of a trace, a windowed arrival normally more; a trace whose signal fills less needs if_win
+ *                or a larger value, else A falls to the noise floor and the trace is treated as L1).  ARITHMETIC: double from r onwards,
+ *                the adjoint source rounded to float32 once; no floating-point atomics, the same input gives the same bits.  A live
+ *                conditioning key: it composes with if_win and filter; with "conditioning": "reference" it is parsed, validated and
+ *                ignored.  Refused (SEPFWI_EINVAL): any other kind; the key without robust_delta; robust_delta or robust_quantile without
+ *                the key or out of range; together with if_cross_misfit, if_envelope_misfit, if_w2_misfit, if_src_update or weights
+ *                other than (1, 0, 0).  Absent: every launch, allocation and bit as before.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.
@@ -204,7 +223,9 @@ int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, perturbation, stf or para_fname; a bad shot list; the product
  * (hv_* set) under if_cross_misfit (a misfit that is not quadratic in the data), if_src_update (a matching filter that depends on the
  * synthetics) or if_w2_misfit (no least-squares Gauss-Newton form; the message names the key) -- the scattered gathers alone are still served then.  SEPFWI_ECOURANT applies to the
- * background model only.  The session's observed data, its misfit, sepfwi_get_misfit_parts and the pseudo-Hessian state are neither
+ * background model only.  Under robust_misfit the product is J^T C^T Z W Z C J v, W the IRLS weight at (C obs, C of the background gather):
+ * the call records the background gather as under if_envelope_misfit and READS the shot's observed gather from the session's store
+ * (sepfwi_set_observed or the files), released with the shot.  Otherwise the session's observed data, its misfit, sepfwi_get_misfit_parts and the pseudo-Hessian state are neither
  * read nor written; sepfwi_get_stats afterwards describes this call (fwd_ms: the Born time loops).
  * Schedule: one shot after the other on the call's stream (hip_stream, NULL: the session's own), synchronous; the batched multi-lane
  * schedule of sepfwi_cufd* is not used.  Option quiet_skip is ignored for this call.  The second field set (18 arrays) is allocated on
@@ -242,6 +263,9 @@ int sepfwi_born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, float 
  *   *misfit; the w mode is untouched and stays in raw data space (sepfwi_data_misfit / sepfwi_data_gn give the operators to compose).
  * W2 misfit (if_w2_misfit, as under sepfwi_cufd): the gradient mode returns the exact gradient on Omega of 1/2 sum_r w_r W_r and that value
  *   in *misfit; the w mode is untouched; the product (v set) is refused with SEPFWI_EINVAL, as sepfwi_born refuses it.
+ * Robust misfit (robust_misfit, as under sepfwi_cufd): the gradient mode returns the exact gradient on Omega of sum phi and that value in
+ *   *misfit; the product is g = P J^T C^T Z W Z C J P v with the IRLS weight W (v^T g = |W^1/2 Z C J P v|^2), which reads the observed
+ *   store as sepfwi_born does under the key; the w mode is untouched.
  * Refused with SEPFWI_EINVAL before anything is touched: a NULL model, stf, para_fname or output g_*; a partial v; both v and w; a bad
  * shot list; if_cross_misfit or if_src_update in any mode; a w component without a weight.  SEPFWI_ECOURANT applies to the background model.  The
  * gradient of the source time function is returned by sepfwi_adjoint_exact_src (below), not here.  The session's observed data, sepfwi_get_misfit_parts and the pseudo-Hessian state
@@ -302,12 +326,18 @@ int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, con
  *       under weights other than (1, 0, 0).
  *   sepfwi_data_gn       out = the Gauss-Newton operator of the misfit at syn applied to d:  C^T Z C d for the L2 misfit (syn is not
  *       read),  C^T D^T Z D C d under if_envelope_misfit, D at C syn.  Symmetric and non-negative.  SEPFWI_EINVAL under if_cross_misfit,
- *       if_src_update, if_w2_misfit (the transport misfit has no least-squares form in the data) and under weights other than (1, 0, 0).
+ *       if_src_update, if_w2_misfit (the transport misfit has no least-squares form in the data), under robust_misfit (the weight needs
+ *       the observed data: sepfwi_data_gn_obs) and under weights other than (1, 0, 0).
+ *   sepfwi_data_gn_obs   sepfwi_data_gn at (obs, syn).  Under robust_misfit out = C^T Z W Z C d, W = diag(w) the IRLS weight of
+ *       (C obs, C syn), 0 on dead traces: symmetric and non-negative; obs is required (SEPFWI_EINVAL if NULL).  Under every other file obs
+ *       is not read and may be NULL: the result is that of sepfwi_data_gn bit for bit, and so are the refusals.
  */
 int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int gpu_id, int group_size, const int *shot_ids,
                        const char *para_fname, void *hip_stream);
 int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids, const char *para_fname,
                    void *hip_stream);
+int sepfwi_data_gn_obs(float *out, const float *obs, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids,
+                       const char *para_fname, void *hip_stream);
 
 /* Drops cached observed data (e.g. after the Shot_*.bin files were rewritten by another tool). */
 void sepfwi_invalidate_observed(void);

@@ -216,7 +216,17 @@ int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int
         if (!para_fname) throw std::invalid_argument("para_fname is NULL");
         if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
         if (group_size > 0 && (!out || !syn || !d)) throw std::invalid_argument("data_gn: out, syn and d must not be NULL");
-        get_session(para_fname, gpu_id)->data_gn(out, syn, d, group_size, shot_ids, (hipStream_t)hip_stream);
+        get_session(para_fname, gpu_id)->data_gn(out, nullptr, syn, d, group_size, shot_ids, (hipStream_t)hip_stream, false);
+    });
+}
+
+int sepfwi_data_gn_obs(float *out, const float *obs, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids,
+                       const char *para_fname, void *hip_stream) {
+    return guarded([&] {
+        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        if (group_size > 0 && (!out || !syn || !d)) throw std::invalid_argument("data_gn_obs: out, syn and d must not be NULL");
+        get_session(para_fname, gpu_id)->data_gn(out, obs, syn, d, group_size, shot_ids, (hipStream_t)hip_stream, true);  // (obs: checked under the key)
     });
 }
 

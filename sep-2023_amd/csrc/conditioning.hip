@@ -18,6 +18,7 @@
 
 #include "conditioning.hpp"
 #include "device_alloc.hpp"
+#include "robust_misfit.hpp"
 #include "w2_misfit.hpp"
 
 namespace sepfwi {
@@ -482,6 +483,29 @@ void Conditioner::w2_residual(hipStream_t st, const float *obs, const float *syn
     launch_w2_trace(st, nt_, nrec, obs, syn, res, weights, src_weight, dt, beta, w2_.get(), (size_t)nt_ * cap_, w2_sum_.get());
     launches_++;
     launch(k_env_sum, dim3(1), st, nrec, w2_sum_.get(), acc);  // the traces in a fixed order
+}
+
+void Conditioner::ensure_robust_buffers() {
+    if (robust_scale_.get()) return;
+    robust_scale_ = DevBuf<float>(&bytes_, (size_t)cap_);
+    robust_sum_ = DevBuf<double>(&bytes_, (size_t)cap_);
+}
+
+void Conditioner::robust_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, int kind, double delta, double quantile,
+                                  double *acc) {
+    if (idle(nrec)) return;
+    ensure_robust_buffers();
+    launch_robust_trace(st, nt_, nrec, obs, syn, nullptr, res, kind, delta, robust_rank(nt_, quantile), 1.0f, robust_scale_.get(), robust_sum_.get());
+    launches_++;
+    launch(k_env_sum, dim3(1), st, nrec, robust_sum_.get(), acc);  // the traces in a fixed order
+}
+
+void Conditioner::robust_scattered(hipStream_t st, const float *obs, const float *syn_bg, const float *d, float *res, int nrec, int kind,
+                                   double delta, double quantile, float sign) {
+    if (idle(nrec)) return;
+    ensure_robust_buffers();
+    launch_robust_trace(st, nt_, nrec, obs, syn_bg, d, res, kind, delta, robust_rank(nt_, quantile), sign, robust_scale_.get(), robust_sum_.get());
+    launches_++;
 }
 
 void Conditioner::envelope_scattered(hipStream_t st, const float *syn, const float *d, float *res, int nrec, float sign) {

@@ -1,5 +1,5 @@
 // conditioning.hpp -- data-conditioning chain of the misfit (conditioning.hip): windows, band-pass (hipFFT), normalised
-// cross-correlation misfit, envelope misfit, trace-wise W2 misfit.  All gathers are [rec][nt] float32 device arrays.
+// cross-correlation misfit, envelope misfit, trace-wise W2 misfit, robust (Huber / Cauchy) misfits.  All gathers are [rec][nt] float32 device arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +50,16 @@ class Conditioner {
     // cross_residual).  Double from the densities onwards, res rounded once; no atomics.  obs, syn and res: three different gathers.
     void w2_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, const float *weights, float src_weight, float dt,
                      double beta, double *acc);
+    // ---- robust misfits (parameter keys robust_misfit / robust_delta / robust_quantile; robust_misfit.hpp holds the definition) ----
+    // kind: kRobustHuber or kRobustCauchy.  Per trace A = the order statistic floor(quantile (nt - 2)) of |obs| over samples 1 ... nt - 1 (an
+    // exact radix select), the threshold delta A; res = psi (sample 0 zeroed), the sign of l2_residual; *acc += 2 sum phi, the traces in a fixed
+    // order.  Double from the residual onwards, res rounded once; no floating-point atomics.  obs, syn and res: three different gathers.
+    void robust_residual(hipStream_t st, const float *obs, const float *syn, float *res, int nrec, int kind, double delta, double quantile,
+                         double *acc);
+    // The linearised twin: res = sign Z w Z d with the IRLS weight w of (obs, the background syn_bg), 0 on dead traces.  sign = -1: what
+    // robust_residual leaves, to first order in the weights' own terms, for observed data syn_bg - d (the Gauss-Newton product); no misfit.
+    void robust_scattered(hipStream_t st, const float *obs, const float *syn_bg, const float *d, float *res, int nrec, int kind, double delta,
+                          double quantile, float sign = -1.0f);
     // source_update (utilities.cu:1170-1281, cuda_spectrum_update :905-977): the source-signature update as a matching filter.
     // Both gathers zero-padded to 2 nt and end-tapered over the padded length (ratio 0.01); per frequency one coefficient
     // coef(f) = sum_r conj(C_r) O_r / (sum_r |C_r|^2 + 1e-6), kept for the adjoint step; the synthetic spectra are multiplied by
@@ -67,6 +77,8 @@ class Conditioner {
     void ensure_envelope_buffers();
     // five [cap][nt] double scratch planes (the CDFs, the densities, c) and the per-trace w_r W_r of the W2 misfit, allocated on first use
     void ensure_w2_buffers();
+    // the per-trace scale A and sums 2 sum phi of the robust misfits, allocated on first use
+    void ensure_robust_buffers();
     long long device_bytes() const { return bytes_; }  // what the buffers below hold
     // What the methods above have issued so far: one per kernel launch and one per hipFFT exec (a plan's creation is none).  Per gather
     // with channels:
@@ -78,6 +90,8 @@ class Conditioner {
     //   envelope_residual                        19   difference, 2 hilbert, residual, sum, hilbert, combination
     //   envelope_scattered                       17   2 hilbert, linearised residual, hilbert, combination
     //   w2_residual                               2   the traces (one block each), their sum
+    //   robust_residual                           2   the traces (one block each: select, then residual), their sum
+    //   robust_scattered                          1   the traces (select, then the weighted product)
     long long launches() const { return launches_; }
 
   private:
@@ -110,6 +124,8 @@ class Conditioner {
     DevBuf<float> env_;            // envelope misfit: 3 x [cap][nt]
     DevBuf<double> env_sum_;       // ... and sum rho^2 per trace
     DevBuf<double> w2_, w2_sum_;   // W2 misfit: kW2Planes x [cap][nt], and w_r W_r per trace
+    DevBuf<float> robust_scale_;   // robust misfits: A per trace
+    DevBuf<double> robust_sum_;    // ... and 2 sum phi per trace
     std::map<int, Plans> plans_;  // by number of traces
 };
 

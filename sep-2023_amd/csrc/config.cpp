@@ -49,6 +49,23 @@ Params parse_params(const std::string &text) {
         if (!(std::isfinite(p.w2_beta) && p.w2_beta > 0.0 && p.w2_beta <= 16.0))
             throw std::invalid_argument("parameter file: w2_beta must be finite, above 0 and at most 16");
     }
+    if (j.has("robust_misfit")) {
+        const std::string k = j.at("robust_misfit").as_string("robust_misfit");
+        if (k != "huber" && k != "cauchy") throw std::invalid_argument("parameter file: robust_misfit must be \"huber\" or \"cauchy\"");
+        p.robust_misfit = k == "huber" ? 1 : 2;
+        // no default: the right threshold depends on the data's noise, and nothing here can derive one
+        if (!j.has("robust_delta")) throw std::invalid_argument("parameter file: robust_misfit needs robust_delta (finite, above 0; there is no default)");
+    } else if (j.has("robust_delta") || j.has("robust_quantile")) {
+        throw std::invalid_argument(std::string("parameter file: ") + (j.has("robust_delta") ? "robust_delta" : "robust_quantile") + " without robust_misfit");
+    }
+    if (j.has("robust_delta")) {
+        p.robust_delta = j.at("robust_delta").as_number("robust_delta");
+        if (!(std::isfinite(p.robust_delta) && p.robust_delta > 0.0)) throw std::invalid_argument("parameter file: robust_delta must be finite and above 0");
+    }
+    if (j.has("robust_quantile")) {
+        p.robust_quantile = j.at("robust_quantile").as_number("robust_quantile");
+        if (!(p.robust_quantile > 0.0 && p.robust_quantile <= 1.0)) throw std::invalid_argument("parameter file: robust_quantile must be above 0 and at most 1");
+    }
     p.has_filter = j.has("filter");
     if (p.has_filter) {
         const JsonValue &f = j.at("filter");
@@ -63,6 +80,7 @@ Params parse_params(const std::string &text) {
         if (c == "reference") {
             p.conditioning_reference = true;
             p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = p.if_w2_misfit = false;
+            p.robust_misfit = 0;
         } else if (c != "live") {
             throw std::runtime_error("parameter JSON: conditioning must be \"live\" or \"reference\"");
         }
@@ -116,9 +134,14 @@ Params parse_params(const std::string &text) {
     if (p.if_w2_misfit && (p.if_cross_misfit || p.if_envelope_misfit || p.if_src_update))
         throw std::invalid_argument(std::string("parameter file: if_w2_misfit together with ") +
                                     (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : "if_src_update")) + " is not supported");
-    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit)) {
+    // a robust misfit is one misfit kind among four; a matching filter fitted to gathers with outliers is what the key is there to avoid
+    if (p.robust_misfit && (p.if_cross_misfit || p.if_envelope_misfit || p.if_w2_misfit || p.if_src_update))
+        throw std::invalid_argument(std::string("parameter file: robust_misfit together with ") +
+                                    (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : "if_src_update"))) +
+                                    " is not supported");
+    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit)) {
         const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
-        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : "if_w2_misfit"))));
+        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : "robust_misfit")))));
         throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
                                     " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
     }

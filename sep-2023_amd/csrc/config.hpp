@@ -30,6 +30,14 @@ struct Params {
     // if_src_update or joint weights.
     bool if_w2_misfit = false;
     double w2_beta = 3.0;
+    // optional keys "robust_misfit" ("huber" | "cauchy") / "robust_delta" / "robust_quantile" (no counterpart in the reference;
+    // robust_misfit.hpp): the misfit is the Huber or Cauchy penalty of the conditioned residual with the threshold robust_delta A per trace,
+    // A the order statistic floor(robust_quantile (n - 1)) of the n live samples |C obs|.  robust_delta is REQUIRED with the key (finite,
+    // above 0; no default: it depends on the data's noise); robust_quantile in (0, 1], default 0.9.  robust_delta or robust_quantile without
+    // robust_misfit is refused.  A live conditioning key like those above; refused together with if_cross_misfit, if_envelope_misfit,
+    // if_w2_misfit, if_src_update or joint weights.
+    int robust_misfit = 0;  // RobustKind: 0 none, 1 huber, 2 cauchy
+    double robust_delta = 0.0, robust_quantile = 0.9;
     // optional key "conditioning": "live" (default) -- the keys above switch their stage on; "reference" -- they are parsed
     // and validated like the reference does and then IGNORED like its driver does (every call site commented out,
     // libCUFD.cu:353-457): results are those of a file without them.  if_win_key keeps what the file said, because the survey

@@ -72,7 +72,8 @@ class Session {
     // The misfit of the parameter file in data space (sepfwi_data_misfit, sepfwi_data_gn; session_data.cpp): raw gathers laid out like
     // born()'s d_ett, host or device.  Neither the observed store nor the misfit, misfit parts or statistics of the last call are touched.
     void data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int group_size, const int *shot_ids, hipStream_t ext_stream);
-    void data_gn(float *out, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream);
+    // obs: the observed gathers (sepfwi_data_gn_obs: obs_entry), needed under robust_misfit alone and not read otherwise; may be null then
+    void data_gn(float *out, const float *obs, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream, bool obs_entry);
     // test hook: wavefield `which` (0..4 vz, vx, szz, sxx, sxz; 5..9 their adjoint twins) of forward lane `lane` as left
     // by the last call, dense (nz - nPad, nx) row-major, host or device pointer; 10..14: the scattered fields of the last Born call
     void copy_field(int lane, int which, float *out);
@@ -97,12 +98,13 @@ class Session {
     //   misfit_chain  obs_c: the shot's CONDITIONED observed gather, only read.  syn: the raw synthetic gather, conditioned (under
     //                 if_src_update also updated) in place.  out: the raw-space adjoint source.  The misfit's sum is added to *acc.
     //   gn_chain      d: the raw gather, conditioned in place.  bg: the raw background gather, conditioned in place, under
-    //                 if_envelope_misfit; else null.  out = sign C^T Z C d, or sign C^T D^T Z D C d.
-    //                 The misfit kind is the file's: L2, if_cross_misfit, if_envelope_misfit or if_w2_misfit.
+    //                 if_envelope_misfit and robust_misfit; else null.  obs_c: C obs, read under robust_misfit alone.  out = sign C^T Z C d,
+    //                 sign C^T D^T Z D C d, or sign C^T Z W Z C d with the IRLS weight W of (obs_c, C bg).
+    //                 The misfit kind is the file's: L2, if_cross_misfit, if_envelope_misfit, if_w2_misfit or robust_misfit.
     // ALIASING: the gathers of one call are all different (the envelope and W2 kernels read the other two while they write out).  The callers
     // pass the session's scratch gathers xpose_, xpose2_, xpose3_.
     void misfit_chain(hipStream_t st, const float *obs_c, float *syn, float *out, int shot_id, int nrec, double *acc);
-    void gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign);
+    void gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign, const float *obs_c = nullptr);
     void ensure_data_scratch();  // xpose3_ / data_acc_
     // prologue and shot loop of condition / data_misfit / data_gn: this device and the caller's stream, or the session's own ordered after
     // the null stream; f(shot id, nrec, offset in the caller's arrays, length) for every shot with channels
@@ -199,7 +201,7 @@ class Session {
     void forward_init(const ShotCtx &x);
     void forward_step(const Call &c, const ShotCtx &x, int it, bool inl);
     void record_column(const ShotCtx &x, int column);
-    void record_background(const ShotCtx &x, int column);  // session_born.cpp (if_envelope_misfit)
+    void record_background(const ShotCtx &x, int column);  // session_born.cpp (if_envelope_misfit, robust_misfit)
     const GaugeDev &gauge_taps(const ShotCtx &x);  // a gauge shot's taps on the device, built on first use (das_gauge.hpp)
     void residual(const ShotCtx &x);
     GeoResShot geo_res_shot(const ShotCtx &x) const;  // joint misfit: what the residual kernel needs of one shot (geophone.hpp)

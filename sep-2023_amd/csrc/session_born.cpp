@@ -12,9 +12,11 @@
 //                       / filter (C = band-pass . window) the buffer gets -C^T Z C dsyn instead (Session::adjoint_source_conditioned):
 //                       the product is J^T C^T Z C J v; the gathers handed out stay the raw ones.  Under if_envelope_misfit the product is
 //                       J^T C^T D^T Z D C J v, D the derivative of the squared envelope at C of the BACKGROUND gather: one more sampler
-//                       launch per step records that gather (record_background), only under the key
-// and after the last shot the gradient finalisation writes hv.  The session's observed data, misfit, misfit parts and pseudo-Hessian
-// state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
+//                       launch per step records that gather (record_background), only under the key.  Under robust_misfit
+//                       the product is J^T C^T Z W Z C J v, W the IRLS weight psi / r of (C obs, C of the background gather): the same
+//                       recording, and the shot's conditioned observed gather is acquired from the store and released with the shot
+// and after the last shot the gradient finalisation writes hv.  The session's observed data (but for the read under robust_misfit), misfit,
+// misfit parts and pseudo-Hessian state are neither read nor written.  Option quiet_skip is ignored for this call (the scattered field has no quiet maps).
 // exact = true (sepfwi_adjoint_exact with v set): v is masked to Omega, the backward half is Session::backward_exact and the
 // finalisation the exact one on Omega (exact_adjoint.hpp) -- the product P J^T W J P v, symmetric and non-negative.
 // dStf (sepfwi_born_src, sepfwi_adjoint_exact_src): the scattered field takes a source term of its own (born.hpp, "Source block"), so the
@@ -62,7 +64,8 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     check_shot_ids(group_size, shot_ids);  // (begin_call checks them where run does: after it has touched the statistics)
     Call c = begin_call(ext_stream, group_size, shot_ids);
     c.opt.quiet_skip = 0;
-    c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files; the observed store is not touched)
+    c.with_adj = want_hv;  // (if_res, to_store stay false: no observed data, no misfit, no files; the observed store is not touched --
+                           // but for the product under robust_misfit, whose weight needs the shot's conditioned observed gather: below)
     hipStream_t st = c.st;
     last_batched_ = false;
     cs_.exact = exact && want_hv;
@@ -104,9 +107,12 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     int comps = (d_ett ? 8 : 0) | (d_vx ? 2 : 0) | (d_vz ? 4 : 0);
     if (want_hv) comps |= active_comps();
     // envelope misfit: the product linearises the envelope at the BACKGROUND gather, which the samplers record into a buffer of its own
-    const bool bg = want_hv && par_.if_envelope_misfit;
+    // robust misfit: the IRLS weight is taken at the background gather too, and at the shot's conditioned OBSERVED gather from the store
+    const bool robust = want_hv && par_.robust_misfit != 0;
+    const bool bg = want_hv && (par_.if_envelope_misfit || robust);
     if (bg && !born_bg_) born_bg_ = dev<float>(data_len_);
     if (bg) ensure_data_scratch();
+    if (robust) obs_begin(c);
     float *out[4] = {nullptr, d_vx, d_vz, d_ett};
     size_t out_off = 0;
     const BornArgs args{state_, dstate, media_, dmedia, pc_.a_z, n};
@@ -114,6 +120,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         ShotCtx x = make_ctx(c, is, stream_lane(0, st), false);
         x.scratch = false;
         x.comps = comps;
+        if (robust) x.d_obs = x.obs_c[3] = obs_->acquire(x.id, x.nrec, st, 3);  // held until the shot's adjoint source is formed
         ShotCtx xd = x;  // the samplers' view: the scattered fields
         xd.fld = fields_at(dstate, n);
 
@@ -144,6 +151,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
         out_off += cnt;
         if (want_hv && cond_on_) {  // if_win / filter: -C^T Z C J v (the weights are (1, 0, 0): the axial strain alone)
             adjoint_source_conditioned(c, x);
+            if (robust) obs_->release_all();
         } else if (want_hv && x.nrec > 0) {
             AdjSource q{{}, {}, 1, (size_t)x.nrec, x.res, x.nrec, geo_ncomp_};  // the time-major gathers of J v, by the weights
             for_active([&](int comp, int b) {

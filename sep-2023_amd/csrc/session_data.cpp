@@ -12,10 +12,12 @@
 //   condition     sepfwi_condition: C or C^T in place
 //   data_misfit   the file's misfit of (obs, syn) and the raw-space adjoint source a = -d misfit / d syn: C^T Z (C obs - C syn) under an L2
 //                 file, the adjoint source of the normalised cross-correlation under if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under
-//                 if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (w2_misfit.hpp).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
+//                 if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (w2_misfit.hpp), C^T psi under robust_misfit (robust_misfit.hpp).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
 //                 as a gradient call computes it; the misfit is that of the updated synthetics and a is taken with the filter held fixed
 //                 (nothing is carried from one shot or call to the next).
-//   data_gn       the Gauss-Newton operator of the misfit in data space at syn: C^T Z C d, or C^T D^T Z D C d under if_envelope_misfit.
+//   data_gn       the Gauss-Newton operator of the misfit in data space at syn: C^T Z C d, or C^T D^T Z D C d under if_envelope_misfit, or
+//                 (sepfwi_data_gn_obs alone: the weight needs the observed data) C^T Z W Z C d under robust_misfit, W the IRLS weight of
+//                 (C obs, C syn) (robust_misfit.hpp).
 //                 Refused under if_cross_misfit, if_src_update and if_w2_misfit (not a least-squares misfit of the data), as the products are.
 // A file without a live conditioning key has C = 1 and no conditioner: its misfit runs through the residual kernel of its gradient calls
 // (time-major, lane 0's gather and residual buffers), its operator is Z.  A joint misfit (misfit_w_*) is refused: it is not one of axial
@@ -60,6 +62,8 @@ void Session::misfit_chain(hipStream_t st, const float *obs_c, float *syn, float
         cond_->cross_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
     else if (par_.if_envelope_misfit)
         cond_->envelope_residual(st, obs_c, syn, out, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
+    else if (par_.robust_misfit)  // psi of the Huber / Cauchy penalty, the threshold from the conditioned observed trace (robust_misfit.hpp)
+        cond_->robust_residual(st, obs_c, syn, out, nrec, par_.robust_misfit, par_.robust_delta, par_.robust_quantile, acc);
     else if (par_.if_w2_misfit)  // the trace weights are explicit (the window's amplitude cancels in the densities): the rule of cross_residual
         cond_->w2_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, par_.dt, par_.w2_beta, acc);
     else
@@ -68,11 +72,14 @@ void Session::misfit_chain(hipStream_t st, const float *obs_c, float *syn, float
     condition_gather_t(st, out, shot_id, nrec);
 }
 
-void Session::gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign) {
+void Session::gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign, const float *obs_c) {
     condition_gather(st, d, shot_id, nrec);
     if (par_.if_envelope_misfit) {
         condition_gather(st, bg, shot_id, nrec);
         cond_->envelope_scattered(st, bg, d, out, nrec, sign);
+    } else if (par_.robust_misfit) {  // W = psi / r at the background: the IRLS weight of (C obs, C bg)
+        condition_gather(st, bg, shot_id, nrec);
+        cond_->robust_scattered(st, obs_c, bg, d, out, nrec, par_.robust_misfit, par_.robust_delta, par_.robust_quantile, sign);
     } else {
         cond_->scattered_residual(st, d, out, nrec, sign);
     }
@@ -96,15 +103,16 @@ void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
 // residual_conditioned leaves for observed data syn - J v, and the sign k_adjoint_source leaves.  Z (sample 0 zeroed) and the sign
 // are one kernel, in the place of the residual kernel; no misfit, no observed data.
 // Under if_envelope_misfit the buffer gets -C^T D^T Z D C d, D the derivative of the squared envelope at C of the shot's BACKGROUND
-// gather, which Session::born recorded time-major in born_bg_.
+// gather, which Session::born recorded time-major in born_bg_.  Under robust_misfit it gets -C^T Z W Z C d, W the IRLS weight of the
+// shot's conditioned observed gather (x.d_obs, which Session::born acquired from the store) and C of the same recorded background gather.
 void Session::adjoint_source_conditioned(const Call &c, const ShotCtx &x) {
     if (x.nrec <= 0) return;
     hipStream_t st = c.st;
-    const bool env = par_.if_envelope_misfit;
+    const bool env = par_.if_envelope_misfit || par_.robust_misfit;  // the kinds that linearise at the background gather
     const long long before = cond_->launches();
     if (env) launch_transpose(st, born_bg_.get(), xpose3_.get(), par_.nSteps, x.nrec);
     launch_transpose(st, syn_of(x, 3), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
-    gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, x.id, x.nrec, -1.0f);
+    gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, x.id, x.nrec, -1.0f, x.d_obs);
     launch_transpose(st, xpose2_, x.res, x.nrec, par_.nSteps);  // [rec][it] -> [it][rec]
     cs_.launches += (env ? 3 : 2) + (cond_->launches() - before);
 }
@@ -189,22 +197,32 @@ void Session::data_misfit(float *misfit, float *adj, const float *obs, const flo
     if (misfit) HIP_OK(hipMemcpy(misfit, &mf, sizeof(float), hipMemcpyDefault));
 }
 
-void Session::data_gn(float *out, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream) {
+void Session::data_gn(float *out, const float *obs, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream,
+                      bool obs_entry) {
     std::lock_guard<std::mutex> lock(mu_);
+    const bool robust = par_.robust_misfit != 0;
+    if (robust && !obs_entry)
+        throw std::invalid_argument("data_gn: under robust_misfit the operator's weight needs the observed data; call sepfwi_data_gn_obs(out, obs, syn, d, ...)");
+    if (robust && !obs && group_size > 0) throw std::invalid_argument("data_gn_obs: obs must not be NULL under robust_misfit (the weight is formed from C obs - C syn)");
     if (par_.if_cross_misfit || par_.if_src_update || par_.if_w2_misfit)
         throw std::invalid_argument(std::string("data_gn: not defined under ") + (par_.if_cross_misfit ? "if_cross_misfit" : (par_.if_src_update ? "if_src_update" : "if_w2_misfit")) +
                                     " (not a least-squares misfit of the data); if_win, filter and if_envelope_misfit are served");
     if (joint_) throw std::invalid_argument("data_gn: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);
     hipStream_t st = data_stream(ext_stream);
-    const bool env = par_.if_envelope_misfit;
+    const bool env = par_.if_envelope_misfit || robust;  // the kinds whose operator depends on syn
     if (env) ensure_data_scratch();
+    float *obs_c = robust ? syn_ : nullptr;  // a fourth [rec][it] gather: lane 0's gather buffers, as data_misfit borrows them under a plain file
     for_each_gather(group_size, shot_ids, [&](int id, int nrec, size_t off, size_t cnt) {
         const size_t bytes = cnt * sizeof(float);
         HIP_OK(hipMemcpyAsync(xpose_, d + off, bytes, hipMemcpyDefault, st));
         if (cond_on_) {
             if (env) HIP_OK(hipMemcpyAsync(xpose3_.get(), syn + off, bytes, hipMemcpyDefault, st));
-            gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, id, nrec, 1.0f);
+            if (robust) {
+                HIP_OK(hipMemcpyAsync(obs_c, obs + off, bytes, hipMemcpyDefault, st));
+                condition_gather(st, obs_c, id, nrec);
+            }
+            gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, id, nrec, 1.0f, obs_c);
             HIP_OK(hipMemcpyAsync(out + off, xpose2_, bytes, hipMemcpyDefault, st));
         } else {  // Z alone: sample 0 of every trace zeroed
             HIP_OK(hipMemset2DAsync(xpose_, (size_t)par_.nSteps * sizeof(float), 0, sizeof(float), (size_t)nrec, st));

@@ -22,8 +22,8 @@ PROBES_LIB_PATH = os.path.join(_ROOT, "libsepfwi_probes.so")
 FAULT_LIB_PATH = os.path.join(_ROOT, "libsepfwi_fault.so")
 VARIANTS = {"default": (LIB_PATH, []), "probes": (PROBES_LIB_PATH, ["-DSEPFWI_PROBES"]), "fault": (FAULT_LIB_PATH, ["-DSEPFWI_PK_FAULT=17"])}
 PUBLIC_OPTIONS = ("bwd_fuse", "batch", "img_every", "quiet_skip", "obs_cache_mb", "probe")
-SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "w2_misfit.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
-HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "w2_misfit.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
+SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "w2_misfit.hip", "robust_misfit.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
+HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "w2_misfit.hpp", "robust_misfit.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
            os.path.join("..", "..", "include", "sepfwi.h")]
 
 _libs = {}
@@ -120,10 +120,11 @@ def lib():
     L.sepfwi_condition.argtypes = [fp, C.c_int, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
     L.sepfwi_data_misfit.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
     L.sepfwi_data_gn.argtypes = [fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
+    L.sepfwi_data_gn_obs.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
     for f in ("sepfwi_cufd", "sepfwi_cufd_stream", "sepfwi_cpml_profiles", "sepfwi_stf_taper", "sepfwi_shot_split",
               "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes", "sepfwi_set_observed",
               "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact", "sepfwi_born_src",
-              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply", "sepfwi_version", "sepfwi_device_count"):
+              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_data_gn_obs", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply", "sepfwi_version", "sepfwi_device_count"):
         getattr(L, f).restype = C.c_int
     L.sepfwi_release_all.restype = None
     L.sepfwi_invalidate_observed.restype = None
@@ -135,7 +136,7 @@ EXPORTS = ["sepfwi_last_error", "sepfwi_version", "sepfwi_device_count", "sepfwi
            "sepfwi_release_all", "sepfwi_invalidate_observed", "sepfwi_cpml_profiles", "sepfwi_stf_taper",
            "sepfwi_shot_split", "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes",
            "sepfwi_set_observed", "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact",
-           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply"]
+           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_data_gn_obs", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply"]
 
 
 def ptr(t):

@@ -112,7 +112,8 @@ class PyTorchObjective(object):
         obj.gauss_newton(v, shot_ids, exact=exact), and the entries of the parameters are packed as `jac` packs the gradient.
         Under a parameter file with if_envelope_misfit the product is the envelope misfit's own Gauss-Newton Hessian (include/sepfwi.h,
         sepfwi_born): nothing changes here.  Under if_w2_misfit the library refuses the product (SepFwiError, SEPFWI_EINVAL: the transport
-        misfit has no Gauss-Newton form here) and the error surfaces as it stands; L-BFGS-B needs `fun` / `jac` alone.  With `regularizer=` its exact Hessian-vector product regularizer.hvp(v) is added, field by
+        misfit has no Gauss-Newton form here) and the error surfaces as it stands; L-BFGS-B needs `fun` / `jac` alone.  Under robust_misfit the
+        product is the IRLS Gauss-Newton form J^T C^T Z W Z C J (W the Huber / Cauchy weight at the current model): positive semi-definite, nothing changes here.  With `regularizer=` its exact Hessian-vector product regularizer.hvp(v) is added, field by
         field, to the Gauss-Newton product: the Hessian of the model term that `loss` carries as `+ regularizer()`.  With `smoother=`
         x and p are in the smoothed variables y: the product is s S^T H (s S p), H the sum above at the model p_ref + s S x."""
         if self.shot_ids is None:
@@ -247,7 +248,7 @@ def gauss_newton_cg(hessvec, grad, damping=0.0, diag=None, maxiter=10, rtol=1e-2
 
     hessvec   callable: a tuple of tensors v -> the tuple H v (fwi_ops.gauss_newton at a fixed model; an extension without a
               counterpart in the reference).  The parameter file decides which misfit's product that is: J^T W J, J^T C^T Z C J under
-              if_win / filter, J^T C^T D^T Z D C J under if_envelope_misfit (under if_w2_misfit the library refuses it) -- symmetric and non-negative with exact=True in every case,
+              if_win / filter, J^T C^T D^T Z D C J under if_envelope_misfit, the IRLS form J^T C^T Z W Z C J under robust_misfit (under if_w2_misfit the library refuses it) -- symmetric and non-negative with exact=True in every case,
               which is all this solver needs.  A model term composes as `lambda v: add(H(v), reg.hvp(v))` (sepfwi.regularize)
     grad      the gradient g, a tuple of tensors shaped like v
     diag      optional tuple of non-negative tensors, e.g. the diagonal pseudo-Hessian: D in the damping term AND the Jacobi

@@ -231,7 +231,7 @@ class _FwiOps:
         (sepfwi_adjoint_exact_src), in Stf's shape with zero rows for shots not in Shot_ids.  One GPU, not together with
         pseudo_hessian.  Windowed / band-passed data (if_win, filter) are served: misfit and gradients are those of the conditioned
         misfit 1/2 |Z (C obs - C syn)|^2, under if_envelope_misfit of the envelope misfit 1/2 |Z (e(C obs) - e(C syn))|^2, under
-        if_w2_misfit of the trace-wise W2 misfit 1/2 sum_r w_r W_r (include/sepfwi.h, sepfwi_cufd);
+        if_w2_misfit of the trace-wise W2 misfit 1/2 sum_r w_r W_r, under robust_misfit of the Huber / Cauchy misfit sum phi (include/sepfwi.h, sepfwi_cufd);
         if_cross_misfit and if_src_update are refused (SepFwiError).
         Extension `pseudo_hessian=k` > 0 (include/sepfwi.h, sepfwi_pseudo_hessian_arm): the diagonal pseudo-Hessian of the call's
         shots, accumulated on every k-th forward step -> the five plus [hLambda, hMu, hDen] ((nz, nx) each, summed over devices
@@ -375,7 +375,9 @@ class _FwiOps:
         misfit: the product is J^T C^T Z C J v (C: `condition`; Z: time sample 0 zeroed).  Under if_envelope_misfit it is the
         Gauss-Newton product of the envelope misfit, J^T C^T D^T Z D C J v with D the derivative of the squared envelope at C of the
         background gather (`data_gn` is its data-space part).  Refused (SepFwiError, SEPFWI_EINVAL) under if_cross_misfit,
-        if_src_update or if_w2_misfit (the transport misfit has no least-squares Gauss-Newton form here).  One GPU only, as born.
+        if_src_update or if_w2_misfit (the transport misfit has no least-squares Gauss-Newton form here).  Under robust_misfit it is the IRLS
+        form J^T C^T Z W Z C J v, W = psi / r at the background (symmetric, non-negative; not the true Hessian): the call reads the shots'
+        observed gathers from the session's store (`data_gn(..., obs=)` is its data-space part).  One GPU only, as born.
         exact=True (include/sepfwi.h, sepfwi_adjoint_exact): J^T is the exact transpose of J instead of the reference's backward pass,
         and the product is P J^T W J P v with P the restriction to Omega (the physical interior without its first row and column; v is
         read there only, hv is 0 elsewhere) -- symmetric, v^T hv = |W^1/2 J P v|^2 to float32 rounding (windowed / band-passed data:
@@ -516,7 +518,7 @@ class _FwiOps:
         many elements, CPU or HIP).  -> (misfit, adj): the misfit as `forward` reports it (a Python float) and the raw-space adjoint source
         a = -d misfit / d syn in syn's shape and device -- C^T Z (C obs - C syn) under an L2 file, the cross-correlation's under
         if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (the
-        trace-wise quadratic Wasserstein distance W of include/sepfwi.h, sepfwi_cufd; double arithmetic, rounded once).  Under if_src_update the matching filter is computed
+        trace-wise quadratic Wasserstein distance W of include/sepfwi.h, sepfwi_cufd; double arithmetic, rounded once), C^T Z psi under robust_misfit (the Huber / Cauchy penalty with the per-trace quantile scale, csrc/robust_misfit.hpp).  Under if_src_update the matching filter is computed
         from the call's own (C obs, C syn), shot by shot; the misfit is that of the updated synthetics and a holds the filter fixed.
         With `born_adjoint` a caller composes a gradient pass: g = -J^T a."""
         (obs, syn), ids, dev, stream = self._data_args((obs, syn), ("obs", "syn"), Shot_ids, para_fname, gpu_id)
@@ -526,11 +528,20 @@ class _FwiOps:
                                                        C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
         return float(mis.value), adj
 
-    def data_gn(self, syn, d, Shot_ids, para_fname, gpu_id=0):
+    def data_gn(self, syn, d, Shot_ids, para_fname, gpu_id=0, obs=None):
         """The Gauss-Newton operator of the parameter file's misfit in data space, at syn, applied to d (sepfwi_data_gn): C^T Z C d under
         an L2 file, C^T D^T Z D C d under if_envelope_misfit (D the derivative of the squared envelope at C syn).  Layout as data_misfit;
         -> a new tensor like d.  Symmetric and non-negative; refused under if_cross_misfit, if_src_update and if_w2_misfit.  `born`, this and
-        `born_adjoint` compose the product J^T (.) J v."""
+        `born_adjoint` compose the product J^T (.) J v.
+        obs (the observed gathers, laid out like syn): the call goes to sepfwi_data_gn_obs, the operator at (obs, syn).  Under robust_misfit
+        it is C^T Z W Z C d with the IRLS weight W of (C obs, C syn) (csrc/robust_misfit.hpp) and obs is required -- without it the library
+        refuses (SepFwiError) and names that entry; under every other file the result is the one without obs, bit for bit."""
+        if obs is not None:
+            (obs, syn, d), ids, dev, stream = self._data_args((obs, syn, d), ("obs", "syn", "d"), Shot_ids, para_fname, gpu_id)
+            out = torch.empty_like(d)
+            _native.check(_native.lib().sepfwi_data_gn_obs(_native.ptr(out), _native.ptr(obs), _native.ptr(syn), _native.ptr(d), dev, int(ids.size),
+                                                           C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
+            return out
         (syn, d), ids, dev, stream = self._data_args((syn, d), ("syn", "d"), Shot_ids, para_fname, gpu_id)
         out = torch.empty_like(d)
         _native.check(_native.lib().sepfwi_data_gn(_native.ptr(out), _native.ptr(syn), _native.ptr(d), dev, int(ids.size), C.c_void_p(ids.ctypes.data),

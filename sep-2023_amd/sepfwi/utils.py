@@ -36,7 +36,7 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
             das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None,
-            if_envelope_misfit=False, if_w2_misfit=False, w2_beta=None):
+            if_envelope_misfit=False, if_w2_misfit=False, w2_beta=None, robust_misfit=None, robust_delta=None, robust_quantile=None):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
@@ -52,6 +52,12 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
     if_w2_misfit / w2_beta (extension): the misfit is the trace-wise quadratic Wasserstein distance between the softplus densities of the
     conditioned gathers, softplus(w2_beta x / max |observed trace|) (include/sepfwi.h, sepfwi_cufd); w2_beta in (0, 16], the library's
     default 3.  Refused by the library together with if_cross_misfit, if_envelope_misfit, if_src_update or misfit_weights.  Each key is
+    written only when set.
+    robust_misfit / robust_delta / robust_quantile (extension): robust_misfit "huber" or "cauchy" makes the misfit that penalty of the
+    conditioned residual, with the threshold robust_delta A per trace, A the order statistic floor(robust_quantile (n - 1)) of the n live
+    samples |C obs| (csrc/robust_misfit.hpp).  robust_delta is required with robust_misfit (finite, > 0; no default: it depends on the
+    data's noise), robust_quantile in (0, 1], the library's default 0.9; either without robust_misfit is refused, here as in the library.
+    Refused by the library together with if_cross_misfit, if_envelope_misfit, if_w2_misfit, if_src_update or misfit_weights.  Each key is
     written only when set."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
@@ -74,6 +80,22 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
         if not (np.isfinite(w2_beta) and 0 < w2_beta <= 16):
             raise ValueError("w2_beta must be in (0, 16]")
         para["w2_beta"] = float(w2_beta)
+    if robust_misfit is not None:
+        if robust_misfit not in ("huber", "cauchy"):
+            raise ValueError("robust_misfit must be 'huber' or 'cauchy'")
+        if robust_delta is None:
+            raise ValueError("robust_misfit needs robust_delta (finite, > 0; there is no default)")
+        para["robust_misfit"] = robust_misfit
+    elif robust_delta is not None or robust_quantile is not None:
+        raise ValueError("%s without robust_misfit" % ("robust_delta" if robust_delta is not None else "robust_quantile"))
+    if robust_delta is not None:
+        if not (np.isfinite(robust_delta) and robust_delta > 0):
+            raise ValueError("robust_delta must be finite and > 0")
+        para["robust_delta"] = float(robust_delta)
+    if robust_quantile is not None:
+        if not 0 < robust_quantile <= 1:
+            raise ValueError("robust_quantile must be in (0, 1]")
+        para["robust_quantile"] = float(robust_quantile)
     if das_fiber != "horizontal":
         if das_fiber != "vertical":
             raise ValueError("das_fiber must be 'horizontal' or 'vertical'")

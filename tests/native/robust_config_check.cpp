@@ -1,0 +1,118 @@
+// CPU-only check of the parameter keys "robust_misfit" / "robust_delta" / "robust_quantile" in the host-side parser of libsepfwi
+// (csrc/config.cpp): built with -fsanitize=address,undefined by tests/test_robust_config.py.  The keys parse, "conditioning": "reference"
+// ignores the misfit kind like the other conditioning keys, a missing or bad robust_delta, a robust_quantile outside (0, 1], a stray
+// robust_delta / robust_quantile and the combinations without a meaning are refused with std::invalid_argument -- the class that the C
+// ABI reports as SEPFWI_EINVAL (csrc/capi.cpp) -- in a message that names the keys.
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+
+#include "../../sep-2023_amd/csrc/config.hpp"
+
+using namespace sepfwi;
+
+static const char *BASE =
+    "{\"nz\": 96, \"nx\": 80, \"dz\": 10.0, \"dx\": 10.0, \"nSteps\": 100, \"dt\": 0.001, \"f0\": 10.0, \"nPoints_pml\": 10, "
+    "\"nPad\": 12, \"survey_fname\": \"s.json\", \"data_dir_name\": \"D\"";
+
+static std::string doc(const std::string &more) { return std::string(BASE) + more + "}"; }
+
+static int failures = 0;
+static void fail(const std::string &what) {
+    printf("FAIL: %s\n", what.c_str());
+    failures++;
+}
+
+// -> 0 accepted, 1 std::invalid_argument naming both keys, 2 std::invalid_argument with another message, 3 any other exception
+static int refusal(const std::string &more, const char *key_a, const char *key_b) {
+    try {
+        (void)parse_params(doc(more));
+    } catch (const std::invalid_argument &e) {
+        const std::string w = e.what();
+        return (w.find(key_a) != std::string::npos && w.find(key_b) != std::string::npos) ? 1 : 2;
+    } catch (const std::exception &) {
+        return 3;
+    }
+    return 0;
+}
+
+int main() {
+    const std::string H = ", \"robust_misfit\": \"huber\", \"robust_delta\": 1.5", C = ", \"robust_misfit\": \"cauchy\", \"robust_delta\": 0.25";
+    // absent: off, and the default of robust_quantile
+    {
+        const Params p = parse_params(doc(""));
+        if (p.robust_misfit != 0 || p.robust_quantile != 0.9) fail("absent key reads as set, or the default of robust_quantile is not 0.9");
+    }
+    {
+        const Params p = parse_params(doc(H));
+        if (p.robust_misfit != 1 || p.robust_delta != 1.5 || p.robust_quantile != 0.9 || p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update ||
+            p.if_envelope_misfit || p.if_w2_misfit || p.joint())
+            fail("huber alone mis-parsed");
+        const Params q = parse_params(doc(C));
+        if (q.robust_misfit != 2 || q.robust_delta != 0.25) fail("cauchy alone mis-parsed");
+    }
+    {   // it composes with if_win and filter; the numbers are read as doubles; the closed end of the quantile's range
+        const Params p = parse_params(doc(H + ", \"robust_quantile\": 0.75, \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0]"));
+        if (p.robust_misfit != 1 || p.robust_quantile != 0.75 || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with if_win and filter mis-parsed");
+        if (parse_params(doc(H + ", \"robust_quantile\": 1")).robust_quantile != 1.0) fail("robust_quantile = 1 refused or mis-read");
+        if (parse_params(doc(H + ", \"robust_quantile\": 1e-9")).robust_quantile != 1e-9) fail("a small positive robust_quantile refused or mis-read");
+        if (parse_params(doc(", \"robust_misfit\": \"huber\", \"robust_delta\": 1e6")).robust_delta != 1e6) fail("a large robust_delta refused or mis-read");
+    }
+    // any other kind is refused, naming the key and the two kinds
+    for (const char *bad : {"\"l1\"", "\"Huber\"", "\"\"", "\"student\""})
+        if (refusal(std::string(", \"robust_misfit\": ") + bad + ", \"robust_delta\": 1.0", "robust_misfit", "cauchy") != 1) fail(std::string("robust_misfit = ") + bad);
+    {   // a value that is no string: the reader's own error (not std::invalid_argument)
+        bool threw = false;
+        try { (void)parse_params(doc(", \"robust_misfit\": true, \"robust_delta\": 1.0")); } catch (const std::invalid_argument &) {} catch (const std::exception &) { threw = true; }
+        if (!threw) fail("a boolean value of robust_misfit accepted or misreported");
+    }
+    // robust_delta is required with the key: no default
+    if (refusal(", \"robust_misfit\": \"huber\"", "robust_misfit", "robust_delta") != 1) fail("huber without robust_delta");
+    if (refusal(", \"robust_misfit\": \"cauchy\", \"robust_quantile\": 0.5", "robust_misfit", "robust_delta") != 1) fail("cauchy without robust_delta");
+    // ... finite and above 0 (1e999 reads as infinity; NaN is no JSON number: the reader's own error)
+    for (const char *bad : {"0", "0.0", "-1", "1e999", "-1e999"})
+        if (refusal(std::string(", \"robust_misfit\": \"huber\", \"robust_delta\": ") + bad, "robust_delta", "above 0") != 1) fail(std::string("robust_delta = ") + bad);
+    if (refusal(", \"robust_misfit\": \"huber\", \"robust_delta\": NaN", "", "") != 3) fail("robust_delta = NaN accepted, or not the reader's error");
+    // robust_quantile in (0, 1]
+    for (const char *bad : {"0", "-0.5", "1.000001", "2", "1e999"})
+        if (refusal(H + ", \"robust_quantile\": " + bad, "robust_quantile", "at most 1") != 1) fail(std::string("robust_quantile = ") + bad);
+    // robust_delta or robust_quantile without robust_misfit
+    if (refusal(", \"robust_delta\": 1.0", "robust_delta", "without robust_misfit") != 1) fail("a stray robust_delta");
+    if (refusal(", \"robust_quantile\": 0.5", "robust_quantile", "without robust_misfit") != 1) fail("a stray robust_quantile");
+    {   // reference mode: parsed and validated, then ignored like the other keys -- also in the combinations that a live file refuses
+        const Params p = parse_params(doc(H + ", \"if_cross_misfit\": true, \"if_win\": true, \"conditioning\": \"reference\""));
+        if (!p.conditioning_reference || p.robust_misfit != 0 || p.if_cross_misfit || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
+        const Params q = parse_params(doc(H + ", \"misfit_w_vx\": 0.5, \"conditioning\": \"reference\""));
+        if (q.robust_misfit != 0 || !q.joint()) fail("reference mode with joint weights mis-parsed");
+        const Params r = parse_params(doc(C + ", \"conditioning\": \"live\""));
+        if (r.robust_misfit != 2) fail("conditioning = live drops the key");
+        if (refusal(", \"robust_misfit\": \"huber\", \"conditioning\": \"reference\"", "robust_misfit", "robust_delta") != 1) fail("reference mode does not validate the key");
+    }
+    // the refused pairs, each naming both keys, as std::invalid_argument
+    for (const std::string &K : {H, C}) {
+        if (refusal(K + ", \"if_cross_misfit\": true", "robust_misfit", "if_cross_misfit") != 1) fail("if_cross_misfit pair");
+        if (refusal(K + ", \"if_envelope_misfit\": true", "robust_misfit", "if_envelope_misfit") != 1) fail("if_envelope_misfit pair");
+        if (refusal(K + ", \"if_w2_misfit\": true", "robust_misfit", "if_w2_misfit") != 1) fail("if_w2_misfit pair");
+        if (refusal(K + ", \"if_src_update\": true", "robust_misfit", "if_src_update") != 1) fail("if_src_update pair");
+        if (refusal(K + ", \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0], \"if_src_update\": true", "robust_misfit", "if_src_update") != 1)
+            fail("if_src_update pair on top of if_win and filter");
+        // joint weights other than (1, 0, 0) with the key as the only live conditioning key
+        if (refusal(K + ", \"misfit_w_vx\": 0.5", "misfit_w_vx", "robust_misfit") != 1) fail("joint weights (vx)");
+        if (refusal(K + ", \"misfit_w_vz\": 2.0", "misfit_w_vz", "robust_misfit") != 1) fail("joint weights (vz)");
+        if (refusal(K + ", \"misfit_w_ett\": 0.5", "misfit_w_ett", "robust_misfit") != 1) fail("joint weights (ett alone, not 1)");
+        // explicit default weights are no joint misfit: accepted
+        if (refusal(K + ", \"misfit_w_ett\": 1.0, \"misfit_w_vx\": 0.0", "", "") != 0) fail("default weights refused");
+    }
+    // ... and what the rules said before stays word for word
+    if (refusal(H + ", \"if_win\": true, \"misfit_w_vx\": 0.5", "misfit_w_vx", "if_win") != 1) fail("joint weights with if_win");
+    if (refusal(", \"if_w2_misfit\": true, \"misfit_w_vx\": 0.5", "misfit_w_vx", "if_w2_misfit") != 1) fail("joint weights with if_w2_misfit");
+    if (refusal(", \"if_w2_misfit\": true, \"if_envelope_misfit\": true", "if_w2_misfit", "if_envelope_misfit") != 1) fail("the W2 pair");
+    if (refusal(", \"if_envelope_misfit\": true, \"if_cross_misfit\": true", "if_envelope_misfit", "if_cross_misfit") != 1) fail("the envelope's pair");
+    // without the key the other keys are still accepted by the parser
+    if (refusal(", \"if_cross_misfit\": true", "", "") != 0 || refusal(", \"if_src_update\": true", "", "") != 0 || refusal(", \"if_envelope_misfit\": true", "", "") != 0 ||
+        refusal(", \"if_w2_misfit\": true", "", "") != 0)
+        fail("a file without the key refused");
+    if (failures) return 1;
+    printf("OK\n");
+    return 0;
+}
