@@ -6,7 +6,9 @@ the first 16 seeds' draws
 test_gpu_exact_adjoint_fuzz.py, whose docstrings say what they draw; draw_pseudo_hessian adds to it, and changes nothing, for
 tests/test_gpu_pseudo_hessian_fuzz.py; draw_conditioned puts draw_born's draw under live conditioning keys for
 tests/test_gpu_conditioned_gn_fuzz.py, its digest is in tests/test_conditioned_fuzz_reference.py; draw_envelope writes that draw once
-more with if_envelope_misfit for tests/test_gpu_envelope_fuzz.py, its digest is in tests/test_envelope_fuzz_reference.py)."""
+more with if_envelope_misfit for tests/test_gpu_envelope_fuzz.py, its digest is in tests/test_envelope_fuzz_reference.py; draw_robust writes
+it once more under robust_misfit / robust_delta / robust_quantile for tests/test_gpu_robust_fuzz.py, its digest is in
+tests/test_robust_fuzz_reference.py)."""
 import json
 import os
 
@@ -483,3 +485,51 @@ def draw_pseudo_hessian(d, seed):
     opts = PH_OPTION_SETS[int(rg.integers(0, len(PH_OPTION_SETS)))]
     fetch = ("ops", "capi")[int(rg.integers(0, 2))]
     return dict(every=every, entry=entry, opts=opts, fetch=fetch)
+
+
+# ---- the robust misfits (robust_misfit / robust_delta / robust_quantile) on the conditioned draw ------------------------------------
+ROB_SEED0 = 99411      # offset of the generator (how it was chosen: tests/test_robust_fuzz_reference.py)
+ROB_KINDS = ("huber", "cauchy")
+ROB_DELTAS = (0.1, 0.5)
+ROB_QUANTILES = (None, 0.99, 1.0)      # None: the key is absent from the file, the library's default 0.9
+ROB_STEPS = (0.9, 0.99, 1.0)           # where a quantile steps to when more than half of the call's traces are dead (draw_robust)
+ROB_KEYS = ("robust_misfit", "robust_delta", "robust_quantile")
+
+
+def robust_raw(seed):
+    """What draw_robust draws for a seed, every quantity for every seed: whether the keys stand alone (one draw in four), the penalty,
+    robust_delta, robust_quantile (None: absent from the file) and the seed of the spikes."""
+    rg = np.random.default_rng(ROB_SEED0 + seed)
+    return dict(alone=int(rg.integers(0, 4)) == 0, kind=ROB_KINDS[int(rg.integers(0, len(ROB_KINDS)))],
+                delta=ROB_DELTAS[int(rg.integers(0, len(ROB_DELTAS)))], quantile=ROB_QUANTILES[int(rg.integers(0, len(ROB_QUANTILES)))],
+                spike_seed=int(rg.integers(0, 2 ** 31)))
+
+
+def draw_robust(d, c, seed, steps=0):
+    """The conditioned draw (d: draw_problem, c: draw_conditioned) written a second time under the robust keys: the pair "rob" next to
+    the conditioned pair, same survey (windows, weights, src_weight), same keys plus robust_misfit, robust_delta and (unless the draw
+    left it to the default) robust_quantile -- or, in one draw of four, the keys ALONE: if_win and filter leave the file and C is the
+    plain end taper.  The pair "rob_twin" is the same file without the three keys, for the bit-identity checks.  draw_conditioned's own
+    pair stays what it is.  steps: how often the quantile has stepped up along ROB_STEPS (fuzz_sides.robust_oracle_side decides that
+    on the reference side, where more than half of the call's traces are dead); a stepped quantile is written into the file.
+    -> dict(mode (c's, or "alone"), alone, kind, delta, quantile (the value in force), drawn (the value drawn, None: default),
+    stepped, pb, twin (shallow copies of c["pb"] on the two pairs), spike_seed)."""
+    import cond_gn_ref as G
+    raw = robust_raw(seed)
+    cpb = c["pb"]
+    para = {k: v for k, v in cpb["para"].items() if k not in ("survey_fname", "data_dir_name")}
+    if raw["alone"]:
+        para = {k: v for k, v in para.items() if k not in COND_KEYS}
+    q0 = 0.9 if raw["quantile"] is None else raw["quantile"]
+    q = ROB_STEPS[min(ROB_STEPS.index(q0) + steps, len(ROB_STEPS) - 1)]
+    keys = {"robust_misfit": raw["kind"], "robust_delta": raw["delta"]}
+    if raw["quantile"] is not None or q != q0:
+        keys["robust_quantile"] = q
+    out = {}
+    for name, extra in (("pb", keys), ("twin", {})):
+        pb = dict(cpb)
+        pb["para_fname"], pb["para"] = G.write_files(d["pb"], "rob" if name == "pb" else "rob_twin", dict(para, **extra), cpb["survey"])
+        pb["survey_fname"], pb["data_dir"] = pb["para"]["survey_fname"], pb["para"]["data_dir_name"]
+        out[name] = pb
+    return dict(mode="alone" if raw["alone"] else c["mode"], alone=raw["alone"], kind=raw["kind"], delta=raw["delta"], quantile=q,
+                drawn=raw["quantile"], stepped=q != q0, spike_seed=raw["spike_seed"], **out)

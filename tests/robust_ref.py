@@ -160,3 +160,47 @@ def add_spikes(o, m, rng, q=QUANTILE, factor=100.0):
         out[r, idx] = (np.float32(factor) * peak * rng.choice([-1.0, 1.0], size=m)).astype(np.float32)
         where.append(idx)
     return out, where
+
+
+def spike_plan(co, seed, q=QUANTILE, m=5):
+    """Where add_spikes' spikes go when the misfit sees the gather through a chain C: co = C obs of ONE build (nrec, nt) -> [indices per
+    trace] and [signs per trace].  The samples are chosen on |C obs|, so inside the trace's window (outside it C obs is 0, never above
+    A): m samples above A where there are m, ONE where there are fewer -- a sample above A if there is one, else the trace's largest
+    (q = 1.0: A is the maximum and nothing lies above it) -- and none on a dead trace (A == 0).  seed: a sequence of integers; every
+    trace has a generator of its own, default_rng(seed + [trace]), so that one trace never shifts another's."""
+    where, signs = [], []
+    for r in range(co.shape[0]):
+        rng = np.random.default_rng(list(seed) + [r])
+        A = scale(co[r], q)
+        a = np.abs(np.asarray(co[r], np.float64)[1:])
+        above = 1 + np.flatnonzero(a > A)
+        if A == 0.0:
+            idx = np.zeros(0, int)
+        elif above.size >= m:
+            idx = np.sort(rng.choice(above, size=m, replace=False))
+        elif above.size:
+            idx = rng.choice(above, size=1)
+        else:
+            idx = np.array([1 + int(np.argmax(a))])
+        where.append(idx)
+        signs.append(rng.choice([-1.0, 1.0], size=idx.size))
+    return where, signs
+
+
+def put_spikes(o, where, signs, factor=100.0):
+    """a copy of the RAW gather o with +-factor x each trace's own peak at the planned samples (spike_plan): the other oracle build's
+    gather gets its spikes at the same samples with its own peak.
+
+    What this does to A.  Under the key alone C is the end taper (1 except over the record's last samples) and under if_win without a
+    filter it is a gain per sample: a sample that was above A stays above it (its |C obs| only grew), the samples up to rank k stay
+    what they were and A KEEPS ITS BITS -- as add_spikes on the raw gather under the key alone.  Two exceptions.  At q = 1.0 the one
+    spike replaces the maximum, so A becomes the spike's own value, 100 x the trace's peak through C, on both builds alike.  Under a
+    filter a spike is spread over the record by the band-pass, A is the order statistic of the filtered spiked trace and has nothing
+    in common with the clean trace's; it is still the same functional of the same installed gather for the library and for the
+    reference, and the two builds' A differ by what their band-passes differ by (fuzz_sides.robust_oracle_side holds that as a
+    yardstick)."""
+    out = np.array(o, np.float32)
+    for r, (idx, sg) in enumerate(zip(where, signs)):
+        if idx.size:
+            out[r, idx] = (np.float32(factor) * np.abs(out[r]).max() * sg).astype(np.float32)
+    return out
