@@ -8,7 +8,8 @@ tests/test_gpu_pseudo_hessian_fuzz.py; draw_conditioned puts draw_born's draw un
 tests/test_gpu_conditioned_gn_fuzz.py, its digest is in tests/test_conditioned_fuzz_reference.py; draw_envelope writes that draw once
 more with if_envelope_misfit for tests/test_gpu_envelope_fuzz.py, its digest is in tests/test_envelope_fuzz_reference.py; draw_robust writes
 it once more under robust_misfit / robust_delta / robust_quantile for tests/test_gpu_robust_fuzz.py, its digest is in
-tests/test_robust_fuzz_reference.py)."""
+tests/test_robust_fuzz_reference.py; draw_w2 writes it once more under if_w2_misfit / w2_beta for tests/test_gpu_w2_fuzz.py, its digest is
+in tests/test_w2_fuzz_reference.py)."""
 import json
 import os
 
@@ -533,3 +534,45 @@ def draw_robust(d, c, seed, steps=0):
         out[name] = pb
     return dict(mode="alone" if raw["alone"] else c["mode"], alone=raw["alone"], kind=raw["kind"], delta=raw["delta"], quantile=q,
                 drawn=raw["quantile"], stepped=q != q0, spike_seed=raw["spike_seed"], **out)
+
+
+# ---- the W2 misfit (if_w2_misfit / w2_beta) on the conditioned draw -------------------------------------------------------------------
+W2_SEED0 = 99826      # offset of the generator (how it was chosen: tests/test_w2_fuzz_reference.py)
+W2_BETAS = (None, 0.5, 8.0, 16.0)      # None: the key is absent from the file, the library's default 3.0
+W2_KEYS = ("if_w2_misfit", "w2_beta")
+
+
+def w2_raw(seed):
+    """What draw_w2 draws for a seed, every quantity for every seed: whether the key stands alone (one draw in four), w2_beta (None:
+    absent from the file), and whether one OBSERVED channel of the one-shot call's shot is silenced (one draw in two; dead_u: which)."""
+    rg = np.random.default_rng(W2_SEED0 + seed)
+    return dict(alone=int(rg.integers(0, 4)) == 0, beta=W2_BETAS[int(rg.integers(0, len(W2_BETAS)))], dead=bool(rg.integers(0, 2)),
+                dead_u=float(rg.uniform()))
+
+
+def draw_w2(d, c, seed):
+    """The conditioned draw (d: draw_problem, c: draw_conditioned) written a second time under if_w2_misfit: the pair "w2" next to the
+    conditioned pair, same survey (windows, weights, src_weight), same keys plus the key and (unless the draw left it to the default)
+    w2_beta -- or, in one draw of four, the key ALONE: if_win and filter leave the file and C is the plain end taper.  The pair
+    "w2_twin" is the same file without the two keys, for the bit-identity checks.  draw_conditioned's own pair stays what it is.
+    The files hold nothing of the silenced channel: it is a property of the observed DATA (exact zeros in one channel: a dead trace,
+    A == 0, beside live ones), applied by fuzz_sides.w2_oracle_side where the shot holds two channels or more.
+    -> dict(mode (c's, or "alone"), alone, beta (the value in force), drawn (the value drawn, None: default), dead, dead_u, pb, twin
+    (shallow copies of c["pb"] on the two pairs))."""
+    import cond_gn_ref as G
+    raw = w2_raw(seed)
+    cpb = c["pb"]
+    para = {k: v for k, v in cpb["para"].items() if k not in ("survey_fname", "data_dir_name")}
+    if raw["alone"]:
+        para = {k: v for k, v in para.items() if k not in COND_KEYS}
+    keys = {"if_w2_misfit": True}
+    if raw["beta"] is not None:
+        keys["w2_beta"] = raw["beta"]
+    out = {}
+    for name, extra in (("pb", keys), ("twin", {})):
+        pb = dict(cpb)
+        pb["para_fname"], pb["para"] = G.write_files(d["pb"], "w2" if name == "pb" else "w2_twin", dict(para, **extra), cpb["survey"])
+        pb["survey_fname"], pb["data_dir"] = pb["para"]["survey_fname"], pb["para"]["data_dir_name"]
+        out[name] = pb
+    return dict(mode="alone" if raw["alone"] else c["mode"], alone=raw["alone"], beta=3.0 if raw["beta"] is None else raw["beta"],
+                drawn=raw["beta"], dead=raw["dead"], dead_u=raw["dead_u"], **out)

@@ -25,11 +25,10 @@ import torch
 import cond_gn_ref as G
 import data_entry_common as DC
 import w2_ref as W
-from data_entry_common import flat, rel, traces, unflat
+from data_entry_common import flat, rel, traces
+from w2_held import EPS, call, on_identical_inputs
 
 pytestmark = pytest.mark.gpu
-EPS = 2.0 ** -24
-MISFIT_EPS, TRACE_EPS, L2_EPS = 8 * EPS, 8 * EPS, 16 * EPS
 ORACLE_TOL, YARD = 1e-4, 3.0
 NSTEPS = tuple(sorted(set(DC.NSTEPS) | {66, 258, 513, 1025}))
 LAYOUTS = {"one": (1,), "five": (5,), "ragged": (5, 3)}
@@ -42,38 +41,6 @@ def problem(tmp, nt, layout, keys, name, **more):
     return DC.problem(tmp, nt, nrec, dict(KEYSETS[keys], **more), name, misfit_key=W.KEY)
 
 
-def call(hip_ops, pb, obs, syn, ids=None):
-    f, a = hip_ops.data_misfit(flat(obs).cuda(), flat(syn).cuda(), pb["Shot_ids"] if ids is None else ids, pb["para_fname"])
-    return f, unflat(a, obs)
-
-
-def on_identical_inputs(oracle, hip_ops, pb, obs, syn, keys, what):
-    """the library against the reference on the library's own C obs, C syn; -> (f, a, f_ref, a_ref) for further use"""
-    ids, fn = pb["Shot_ids"], pb["para_fname"]
-    co = unflat(hip_ops.condition(flat(obs).cuda(), ids, fn), obs)
-    cs = unflat(hip_ops.condition(flat(syn).cuda(), ids, fn), obs)
-    f_ref, a64, _ = W.conditioned_misfit(oracle, pb, co, cs)
-    a_ref = unflat(hip_ops.condition(flat([x.astype(np.float32) for x in a64]).cuda(), ids, fn, transpose=True), obs)
-    f, a = call(hip_ops, pb, obs, syn)
-    gap_f = abs(f - f_ref) / f_ref if f_ref > 0 else abs(f)
-    worst = 0.0                          # per trace: max |a - a_ref| in units of max |a_ref|
-    for x, y in zip(a, a_ref):
-        for r in range(x.shape[0]):
-            top, d = float(np.abs(y[r]).max()), float(np.abs(x[r].astype(np.float64) - y[r]).max())
-            worst = max(worst, d / top if top > 0 else (0.0 if d == 0 else np.inf))
-    n_ref = G.norm(a_ref)
-    gap_l2 = G.norm([x.astype(np.float64) - y for x, y in zip(a, a_ref)]) / n_ref if n_ref > 0 else G.norm(a)
-    print("w2 data %s: misfit %.8e (reference %.8e, gap %.2f EPS), adj per-trace max gap %.2f EPS, rel-L2 %.2f EPS (|a| %.4e)"
-          % (what, f, f_ref, gap_f / EPS, worst / EPS, gap_l2 / EPS, n_ref))
-    assert np.isfinite(f) and all(np.isfinite(x).all() for x in a), what
-    assert abs(f - f_ref) <= MISFIT_EPS * f_ref, (what, f, f_ref)
-    if "filter" in KEYSETS[keys]:
-        assert gap_l2 <= L2_EPS, (what, gap_l2 / EPS)
-    else:
-        assert worst <= TRACE_EPS, (what, worst / EPS)
-    return f, a, f_ref, a_ref
-
-
 # ---- against the reference ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", list(LAYOUTS))
 @pytest.mark.parametrize("nt", NSTEPS)
@@ -83,7 +50,7 @@ def test_data_misfit_against_the_reference(oracle, oracle_nvfma, hip_ops, tmp_pa
         pb = problem(tmp_path / keys, nt, layout, keys, "w2")
         obs, syn = traces(pb, 1), traces(pb, 2)
         what = "nt %d %s %s" % (nt, layout, keys)
-        f, a, f_id, a_id = on_identical_inputs(oracle, hip_ops, pb, obs, syn, keys, what)
+        f, a, f_id, a_id = on_identical_inputs(oracle, hip_ops, pb, obs, syn, what)
         assert nt == 2 or (f_id > 0 and G.norm(a_id) > 0), what      # (one mass sample: both densities are that sample, W = 0)
         # the oracle's own C: float64 transforms, and under filter the distance of its two transform builds as the yardstick
         f_ref, a_ref, _ = W.data_misfit(oracle, pb, obs, syn)
@@ -105,7 +72,7 @@ def test_nearly_fitting_data_meet_the_same_bounds(oracle, hip_ops, tmp_path, nt,
     pb = problem(tmp_path, nt, "ragged", keys, "near")
     obs, noise = traces(pb, 1), traces(pb, 2)
     syn = [(o + np.float32(1e-4) * n).astype(np.float32) for o, n in zip(obs, noise)]
-    f, a, f_ref, a_ref = on_identical_inputs(oracle, hip_ops, pb, obs, syn, keys, "nearly fitting nt %d %s" % (nt, keys))
+    f, a, f_ref, a_ref = on_identical_inputs(oracle, hip_ops, pb, obs, syn, "nearly fitting nt %d %s" % (nt, keys))
     f_ind, _ = call(hip_ops, pb, obs, noise)
     print("w2 data nearly fitting nt %d %s: misfit %.4e, of the independent pair %.4e" % (nt, keys, f, f_ind))
     assert 0 < f < 1e-4 * f_ind
