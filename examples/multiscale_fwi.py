@@ -11,6 +11,7 @@ and the last one uses the unfiltered data.
     python examples/multiscale_fwi.py --envelope [--gauss-newton]
     python examples/multiscale_fwi.py --w2
     python examples/multiscale_fwi.py --robust {huber,cauchy} --robust-delta X [--spikes M] [--gauss-newton]
+    python examples/multiscale_fwi.py --fk P1 P2 P3 P4 [--fk-reject] [--gauss-newton]
 
 --gauss-newton (off by default; without it every printed line is what it was): every stage runs --niter truncated Gauss-Newton steps in
 the Lame parameters instead of L-BFGS-B -- the band's own parameter file serves the conditioned misfit, its exact gradient
@@ -36,6 +37,12 @@ conditioned residual with the threshold X times the 0.9-quantile of every observ
 the library: it depends on the data's noise.  With --gauss-newton the steps use the misfit's IRLS Gauss-Newton product.  --spikes M writes M
 spikes of 100 x the trace's peak into every observed trace after the data are modelled (interrogator spikes: what the robust misfit is for),
 with or without --robust: the pair of runs shows what the spikes do to the L2 inversion and what is left of that under the robust one.
+
+--fk P1 P2 P3 P4 [--fk-reject] (off by default; without it every printed line is what it was): EVERY stage conditions observed and synthetic
+gathers with the apparent-slowness (f-k) fan filter across the fibre's channels as well (parameter keys "fk_slowness" / "fk_mode"; the
+chain is C = FK . band-pass . window): the trapezoid P1 < P2 <= P3 < P4 in s/m is kept, or with --fk-reject removed; p > 0 is an event
+that arrives later at higher channel indices (here: to the right).  The fibre of this example is one straight line of channels 20 m
+apart, which is what the filter needs.  --fk 0.5e-4 1e-4 4e-4 6e-4 inverts the right-going wavefield alone.
 """
 import argparse
 import os
@@ -102,12 +109,12 @@ def gauss_newton_stage(m, Mask, Stf, Shot_ids, para_fname, outer, inner, damping
 
 
 def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_newton=False, inner=3, envelope=False, w2=False, robust=None,
-        robust_delta=None, spikes=0):
+        robust_delta=None, spikes=0, fk=None, fk_reject=False):
     """-> [(band or None, misfit at the start of the stage, misfit at its end)], (vp, vs, rho) after the last stage.
     gauss_newton: every stage is `niter` truncated Gauss-Newton steps (at most `inner` conjugate-gradient iterations each) on the stage's
     own parameter file instead of L-BFGS-B (gauss_newton_stage).  envelope: a first stage on the envelope misfit, band = ENVELOPE in the log; w2: a first stage on
     the W2 misfit, band = W2 (L-BFGS-B only).  robust ("huber" | "cauchy") with robust_delta: every band stage on that robust misfit; spikes: that many
-    spikes of 100 x the trace's peak in every observed trace."""
+    spikes of 100 x the trace's peak in every observed trace.  fk = [p1, p2, p3, p4]: the fan filter in every stage's chain (fk_reject: its reject mode)."""
     if robust and robust_delta is None:
         raise ValueError("--robust needs --robust-delta (there is no default: the threshold depends on the data's noise)")
     if w2 and gauss_newton:
@@ -136,12 +143,13 @@ def run(niter=4, n_bands=3, workdir=None, device="cuda", verbose=True, gauss_new
 
     def para_for(tag, band):
         fn = os.path.join(work, "para_%s.json" % tag)
+        fan = dict(fk_slowness=list(fk), fk_mode="reject" if fk_reject else None) if (fk is not None and tag != "obs") else {}
         if band == ENVELOPE:
-            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_envelope_misfit=True)
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_envelope_misfit=True, **fan)
         elif band == W2:
-            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_w2_misfit=True)
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, if_w2_misfit=True, **fan)
         else:
-            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band,
+            ft.paraGen(nz_pad, nx_pad, dz, dx, nt, dt, f0, nPml, nPad, fn, survey_fname, data_dir, filter_para=band, **fan,
                        robust_misfit=robust if tag != "obs" else None, robust_delta=robust_delta if (robust and tag != "obs") else None)
         return fn
 
@@ -210,5 +218,7 @@ if __name__ == "__main__":
     ap.add_argument("--robust", choices=["huber", "cauchy"], default=None, help="every stage on this robust misfit of its band (parameter key robust_misfit); needs --robust-delta")
     ap.add_argument("--robust-delta", type=float, default=None, help="with --robust: the threshold in units of every observed trace's 0.9-quantile of |samples| (parameter key robust_delta; no default)")
     ap.add_argument("--spikes", type=int, default=0, help="write this many spikes of 100 x the trace's peak into every observed trace")
+    ap.add_argument("--fk", type=float, nargs=4, default=None, metavar=("P1", "P2", "P3", "P4"), help="every stage with the apparent-slowness fan filter across the channels: the trapezoid in s/m (parameter key fk_slowness)")
+    ap.add_argument("--fk-reject", action="store_true", help="with --fk: remove the band instead of keeping it (parameter key fk_mode)")
     a = ap.parse_args()
-    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope, w2=a.w2, robust=a.robust, robust_delta=a.robust_delta, spikes=a.spikes)
+    run(a.niter, a.bands, a.workdir, gauss_newton=a.gauss_newton, inner=a.inner, envelope=a.envelope, w2=a.w2, robust=a.robust, robust_delta=a.robust_delta, spikes=a.spikes, fk=a.fk, fk_reject=a.fk_reject)

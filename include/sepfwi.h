@@ -137,6 +137,23 @@ int sepfwi_device_count(void);
  *                ignored.  Refused (SEPFWI_EINVAL): any other kind; the key without robust_delta; robust_delta or robust_quantile without
  *                the key or out of range; together with if_cross_misfit, if_envelope_misfit, if_w2_misfit, if_src_update or weights
  *                other than (1, 0, 0).  Absent: every launch, allocation and bit as before.
+ *                "fk_slowness": [p1, p2, p3, p4] (s/m), "fk_mode": "pass" | "reject" (default "pass") (an extension that no reference run
+ *                pins) -- the apparent-slowness (f-k) fan filter across the channels of a shot, the third stage of the conditioning
+ *                chain: C = FK . band-pass . window, C^T = window . band-pass . FK (sepfwi_condition below).  On a shot's [nrec][nSteps]
+ *                gather: zero-pad to [P][2 nSteps], P the smallest power of two >= 2 nrec; forward DFT along both axes; every bin
+ *                times the real gain G of its slowness p = -k / f (p > 0: an event that arrives later at higher channel indices; at
+ *                f = 0: p = 0 for k = 0, infinite otherwise); inverse transforms, crop.  G = T (pass) or 1 - T (reject), T(p) = 0 outside
+ *                (p1, p4), 1 on [p2, p3], sin^2 / cos^2 ramps between; on the time-Nyquist row and the wavenumber-Nyquist column
+ *                (T(p) + T(-p)) / 2, which makes the operator exactly symmetric.  The channel spacing comes from the survey: every
+ *                shot's channels must lie on one straight, equally spaced line in channel order ((z_rec, x_rec) steps all equal and
+ *                not (0, 0); spacing sqrt((sz dz)^2 + (sx dx)^2), shot by shot); a shot without channels is idle.  float32
+ *                transforms, the gain in double, no atomics: the same input gives the same bits.  A live conditioning key: alone it
+ *                switches the window stage to its end taper; it composes with if_win, filter and every misfit kind (they see C obs
+ *                and C syn alone); with "conditioning": "reference" it is parsed, validated and ignored.  Refused (SEPFWI_EINVAL):
+ *                fk_slowness that is not four finite numbers p1 < p2 <= p3 < p4; another fk_mode; fk_mode without fk_slowness;
+ *                together with weights other than (1, 0, 0); at session creation a shot with exactly one channel, a channel step
+ *                that changes or a zero step (the message names the shot and the channel).  Absent: every launch, allocation and
+ *                bit as before.
  *
  * Unlike the reference, device state (fields, PML profiles, boundary buffers, observed data) is kept
  * in a per-(para_fname, gpu_id) session between calls; sepfwi_release_all() frees it.
@@ -311,7 +328,8 @@ int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float 
 /* C (transpose = 0) or C^T (transpose != 0) of the parameter file, in place, on gathers laid out like sepfwi_born's d_ett:
    [nrec_i][nSteps] shot after shot in the order of shot_ids; host or device.  C is what the session applies to a synthetic
    axial-strain gather before the residual: per-channel windows with weights (if_win) or the end taper, then the band-pass
-   (filter); the identity when no conditioning key is live.  C^T: the band-pass, then the window.  Defined under every key
+   (filter), then the apparent-slowness fan filter across the shot's channels (fk_slowness / fk_mode); the identity when no conditioning
+   key is live.  C^T: the fan filter, the band-pass, then the window.  Defined under every key
    (if_cross_misfit and if_src_update select a misfit, not C).  Creates the session as sepfwi_set_observed does; touches no observed
    data, misfit or statistics; synchronous. */
 int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream);

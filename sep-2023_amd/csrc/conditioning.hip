@@ -1,5 +1,5 @@
 // conditioning.hip -- the data-conditioning chain of the misfit: time windows with trace weights, zero-phase band-pass
-// (hipFFT), normalised zero-lag cross-correlation misfit and its adjoint source.
+// (hipFFT), apparent-slowness (f-k) fan filter across the channels, normalised zero-lag cross-correlation misfit and its adjoint source.
 //
 // In the reference these are utilities.cu:733-1111 (kernels) and :1115-1166 (bp_filter1d, cuFFT); every call site in the
 // driver is commented out (libCUFD.cu:353-457), so the chain is DORMANT there: the parameter keys are parsed and nothing
@@ -265,14 +265,86 @@ __global__ void k_env_combine(int nt, int nrec, float *__restrict__ a, const flo
     a[i] = sign * (2.0f * (a[i] - hb[i]));
 }
 
+// ---- apparent-slowness (f-k) fan filter (parameter keys fk_slowness / fk_mode; no counterpart in the reference) ----------------------------
+// The two transpositions between the time-axis and the channel-axis transforms.  Tiles of 32 x 32 float2 in LDS, 256 threads as 32 x 8: the
+// global reads and writes both run along the contiguous index of their array (a row of 32 float2 is 256 B), and the tile's pitch of 33
+// float2 puts the 32 lanes of a column read (ds_read_b64: banks (a / 4) mod 64 per half wave) on addresses 66 dwords apart, i.e. on 32
+// different bank pairs.
+//   to channels: spec [nrec][nf] -> specT [nf][P], the rows nrec ... P - 1 of the channel padding written as zeros
+//   to traces:   specT [nf][P] -> spec [nrec][nf], the padding rows dropped
+constexpr int kFkTile = 32;
+__global__ void k_fk_to_channels(int nf, int nrec, int P, const float2 *__restrict__ spec, float2 *__restrict__ specT) {
+    __shared__ float2 tile[kFkTile][kFkTile + 1];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int j0 = blockIdx.x * kFkTile, m0 = blockIdx.y * kFkTile;
+    for (int i = ty; i < kFkTile; i += 8) {
+        const int r = m0 + i, j = j0 + tx;
+        tile[i][tx] = (r < nrec && j < nf) ? spec[(size_t)r * nf + j] : make_float2(0.0f, 0.0f);
+    }
+    __syncthreads();
+    for (int i = ty; i < kFkTile; i += 8) {
+        const int j = j0 + i, m = m0 + tx;
+        if (j < nf && m < P) specT[(size_t)j * P + m] = tile[tx][i];
+    }
+}
+__global__ void k_fk_to_traces(int nf, int nrec, int P, const float2 *__restrict__ specT, float2 *__restrict__ spec) {
+    __shared__ float2 tile[kFkTile][kFkTile + 1];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int j0 = blockIdx.x * kFkTile, m0 = blockIdx.y * kFkTile;
+    for (int i = ty; i < kFkTile; i += 8) {
+        const int j = j0 + i, m = m0 + tx;
+        tile[i][tx] = (j < nf && m < P) ? specT[(size_t)j * P + m] : make_float2(0.0f, 0.0f);
+    }
+    __syncthreads();
+    for (int i = ty; i < kFkTile; i += 8) {
+        const int r = m0 + i, j = j0 + tx;
+        if (r < nrec && j < nf) spec[(size_t)r * nf + j] = tile[tx][i];
+    }
+}
+
+// the trapezoid T(p): 0 outside (p1, p4) (also at p = +-infinity), 1 on [p2, p3], sin^2 / cos^2 ramps between
+__device__ __forceinline__ double fk_trapezoid(double p, double p1, double p2, double p3, double p4) {
+    if (!(p > p1 && p < p4)) return 0.0;
+    if (p < p2) {
+        const double s = sin(kPi / 2.0 * (p - p1) / (p2 - p1));
+        return s * s;
+    }
+    if (p <= p3) return 1.0;
+    const double c = cos(kPi / 2.0 * (p - p3) / (p4 - p3));
+    return c * c;
+}
+
+// One thread per bin (j, m) of specT [nt + 1][P]: times the gain of the bin's apparent slowness p = -k_m / f_j = -ms slope / j, ms the signed
+// wavenumber index and slope = 2 nt dt / (P delta).  Row j = 0: p = 0 at m = 0, infinite elsewhere.  Time-Nyquist row j = nt and
+// wavenumber-Nyquist column m = P / 2: (T(p) + T(-p)) / 2.  Double throughout, the gain rounded once.
+__global__ void k_fk_gain(int nt, int P, double slope, double p1, double p2, double p3, double p4, int reject, float2 *__restrict__ specT) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ((size_t)nt + 1) * (size_t)P) return;
+    const int j = (int)(i / (size_t)P), m = (int)(i % (size_t)P);
+    const int ms = m <= P / 2 ? m : m - P;
+    double T;
+    if (j == 0) {
+        T = ms == 0 ? fk_trapezoid(0.0, p1, p2, p3, p4) : 0.0;
+    } else {
+        const double p = -(double)ms * slope / (double)j;
+        T = fk_trapezoid(p, p1, p2, p3, p4);
+        if (j == nt || m == P / 2) T = 0.5 * (T + fk_trapezoid(-p, p1, p2, p3, p4));
+    }
+    const float g = (float)(reject ? 1.0 - T : T);
+    float2 &c = specT[i];
+    c.x *= g;
+    c.y *= g;
+}
+
 // hipFFT is only needed by a parameter file with a band-pass or a source-signature update, so libsepfwi.so does not link it:
-// the five entry points are resolved with dlopen when the first plan is made, and a ROCm image without hipFFT still loads and
+// the entry points are resolved with dlopen when the first plan is made, and a ROCm image without hipFFT still loads and
 // runs the propagator (a parameter file that asks for a filter then fails with a message that names the library).
 struct FftApi {
     hipfftResult (*Plan1d)(hipfftHandle *, int, hipfftType, int);
     hipfftResult (*SetStream)(hipfftHandle, hipStream_t);
     hipfftResult (*ExecR2C)(hipfftHandle, hipfftReal *, hipfftComplex *);
     hipfftResult (*ExecC2R)(hipfftHandle, hipfftComplex *, hipfftReal *);
+    hipfftResult (*ExecC2C)(hipfftHandle, hipfftComplex *, hipfftComplex *, int);
     hipfftResult (*Destroy)(hipfftHandle);
 };
 const FftApi &fft() {
@@ -280,7 +352,7 @@ const FftApi &fft() {
         void *h = nullptr;
         for (const char *name : {"libhipfft.so.0", "libhipfft.so", "/opt/rocm/lib/libhipfft.so.0"})
             if ((h = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
-        if (!h) throw std::runtime_error("data conditioning (filter / if_src_update / if_envelope_misfit) needs hipFFT, and libhipfft.so could not be opened");
+        if (!h) throw std::runtime_error("data conditioning (filter / if_src_update / if_envelope_misfit / fk_slowness) needs hipFFT, and libhipfft.so could not be opened");
         FftApi a{};
         auto sym = [&](const char *n) {
             void *p = dlsym(h, n);
@@ -291,6 +363,7 @@ const FftApi &fft() {
         a.SetStream = (decltype(a.SetStream))sym("hipfftSetStream");
         a.ExecR2C = (decltype(a.ExecR2C))sym("hipfftExecR2C");
         a.ExecC2R = (decltype(a.ExecC2R))sym("hipfftExecC2R");
+        a.ExecC2C = (decltype(a.ExecC2C))sym("hipfftExecC2C");
         a.Destroy = (decltype(a.Destroy))sym("hipfftDestroy");
         return a;
     }();
@@ -315,6 +388,7 @@ Conditioner::~Conditioner() {
         (void)fft().Destroy((hipfftHandle)kv.second.fwd);
         (void)fft().Destroy((hipfftHandle)kv.second.inv);
     }
+    for (auto &kv : fk_plans_) (void)fft().Destroy((hipfftHandle)kv.second);
 }
 
 // Every kernel of the chain runs in blocks of 256 threads and is counted as one launch (launches())
@@ -384,6 +458,53 @@ void Conditioner::bandpass(hipStream_t st, float *data, int nrec, float dt, cons
 void Conditioner::hilbert(hipStream_t st, const float *in, float *out, int nrec) {
     if (idle(nrec)) return;
     round_trip(st, in, out, nrec, [&](dim3 grid, float2 *spec) { launch(k_hilbert_mult, grid, st, nt_ + 1, nrec, spec); });
+}
+
+// ---- the fan filter (conditioning.hpp) ----
+namespace {
+int fk_padded(int nrec) {  // the smallest power of two >= 2 nrec
+    int P = 1;
+    while (P < 2 * nrec) P *= 2;
+    return P;
+}
+}  // namespace
+
+void Conditioner::ensure_fk_buffers() {
+    if (fk_.get()) return;
+    fk_ = DevBuf<float2>(&bytes_, ((size_t)nt_ + 1) * (size_t)fk_padded(cap_));
+}
+
+void *Conditioner::fk_plan_for(int P, hipStream_t st) {
+    auto it = fk_plans_.find(P);
+    if (it == fk_plans_.end()) {
+        hipfftHandle h;
+        fft_ok(fft().Plan1d(&h, P, HIPFFT_C2C, nt_ + 1), "hipfftPlan1d(C2C)");
+        // as in plans_for: plan creation is not stream-ordered
+        if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("conditioning: hipDeviceSynchronize failed");
+        it = fk_plans_.emplace(P, (void *)h).first;
+    }
+    fft_ok(fft().SetStream((hipfftHandle)it->second, st), "hipfftSetStream");
+    return it->second;
+}
+
+void Conditioner::fk_filter(hipStream_t st, float *data, int nrec, float dt, double delta, const double p[4], bool reject) {
+    if (idle(nrec)) return;
+    if (!(delta > 0.0)) throw std::invalid_argument("conditioning: the fan filter needs a positive channel spacing");
+    ensure_fk_buffers();
+    const int nf = nt_ + 1, P = fk_padded(nrec);
+    const size_t bins = (size_t)nf * (size_t)P;
+    const Plans &pl = plans_for(nrec, st);
+    hipfftHandle cc = (hipfftHandle)fk_plan_for(P, st);
+    float2 *specT = fk_.get();
+    embed(st, data, pad_.get(), nrec);
+    forward(pl, pad_.get(), spec_.get());
+    launch(k_fk_to_channels, dim3((nf + kFkTile - 1) / kFkTile, (P + kFkTile - 1) / kFkTile), st, nf, nrec, P, spec_.get(), specT);
+    fft_ok(fft().ExecC2C(cc, specT, specT, HIPFFT_FORWARD), "hipfftExecC2C"), launches_++;
+    launch(k_fk_gain, dim3((unsigned)((bins + 255) / 256)), st, nt_, P, 2.0 * (double)nt_ * (double)dt / ((double)P * delta), p[0], p[1], p[2], p[3], reject ? 1 : 0, specT);
+    fft_ok(fft().ExecC2C(cc, specT, specT, HIPFFT_BACKWARD), "hipfftExecC2C"), launches_++;
+    launch(k_fk_to_traces, dim3((nf + kFkTile - 1) / kFkTile, (nrec + kFkTile - 1) / kFkTile), st, nf, nrec, P, specT, spec_.get());
+    inverse(pl, spec_.get(), pad_.get());
+    launch(k_crop, time_grid(nrec), st, nt_, nrec, data, pad_.get(), (float)(1.0 / (2.0 * (double)nt_ * (double)P)));
 }
 
 void Conditioner::ensure_source_buffers(hipStream_t st) {

@@ -1,5 +1,5 @@
 // conditioning.hpp -- data-conditioning chain of the misfit (conditioning.hip): windows, band-pass (hipFFT), normalised
-// cross-correlation misfit, envelope misfit, trace-wise W2 misfit, robust (Huber / Cauchy) misfits.  All gathers are [rec][nt] float32 device arrays.
+// cross-correlation misfit, envelope misfit, trace-wise W2 misfit, robust (Huber / Cauchy) misfits, f-k fan filter.  All gathers are [rec][nt] float32 device arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +60,22 @@ class Conditioner {
     // robust_residual leaves, to first order in the weights' own terms, for observed data syn_bg - d (the Gauss-Newton product); no misfit.
     void robust_scattered(hipStream_t st, const float *obs, const float *syn_bg, const float *d, float *res, int nrec, int kind, double delta,
                           double quantile, float sign = -1.0f);
+    // ---- apparent-slowness (f-k) fan filter across the channels of one shot (parameter keys fk_slowness / fk_mode) ----
+    // In place on the [nrec][nt] gather: zero-pad to [P][2 nt], P the smallest power of two >= 2 nrec; forward DFT along both axes (e^{-i...}:
+    // the R2C of bandpass along time, rows j = 0 ... nt, f_j = j / (2 nt dt); a C2C of length P along the channels, k_m = m / (P delta) for
+    // m <= P / 2, else (m - P) / (P delta)); every bin times the real gain G of its apparent slowness p = -k / f (p > 0: an event that arrives
+    // later at higher channel indices; at f = 0: p = 0 for k = 0, G's value at infinity otherwise); both inverse transforms, 1 / (2 nt P), crop.
+    // G = T in pass mode, 1 - T with `reject`; T(p) = 0 outside (p[0], p[3]), 1 on [p[1], p[2]], sin^2 / cos^2 ramps between.  On the time-Nyquist
+    // row j = nt and the wavenumber-Nyquist column m = P / 2 the gain is (T(p) + T(-p)) / 2: the half-spectrum computation then equals the
+    // full complex one and the operator is exactly symmetric (its own transpose), like bandpass.  delta: the channel spacing [m].
+    // The gain is evaluated in the kernel in double (no table); float32 transforms, no atomics: the same input gives the same bits.
+    // Between the time and channel transforms the spectrum is transposed ([nrec][nt + 1] <-> [nt + 1][P], LDS tiles), so that both run on
+    // contiguous batches; the rows nrec ... P - 1 of the padding are written by the transposition and never transformed along time.
+    void fk_filter(hipStream_t st, float *data, int nrec, float dt, double delta, const double p[4], bool reject);
+    // the transposed spectrum [nt + 1][Pcap] float2, Pcap the smallest power of two >= 2 cap, allocated on first use: a session whose file does
+    // not set the key never holds it.  8 (nt + 1) Pcap bytes: 131 MB at 1980 channels x 4000 samples (Pcap = 4096), beside the 127 MB of the
+    // padded gather and its spectrum that bandpass holds anyway (hipFFT's own work areas are not counted).
+    void ensure_fk_buffers();
     // source_update (utilities.cu:1170-1281, cuda_spectrum_update :905-977): the source-signature update as a matching filter.
     // Both gathers zero-padded to 2 nt and end-tapered over the padded length (ratio 0.01); per frequency one coefficient
     // coef(f) = sum_r conj(C_r) O_r / (sum_r |C_r|^2 + 1e-6), kept for the adjoint step; the synthetic spectra are multiplied by
@@ -92,6 +108,7 @@ class Conditioner {
     //   w2_residual                               2   the traces (one block each), their sum
     //   robust_residual                           2   the traces (one block each: select, then residual), their sum
     //   robust_scattered                          1   the traces (select, then the weighted product)
+    //   fk_filter                                 9   embed, R2C, transposition, C2C, the gain, C2C, transposition, C2R, crop
     long long launches() const { return launches_; }
 
   private:
@@ -99,6 +116,7 @@ class Conditioner {
         void *fwd, *inv;  // hipfftHandle
     };
     Plans &plans_for(int nrec, hipStream_t st);
+    void *fk_plan_for(int P, hipStream_t st);  // the C2C plan of nt + 1 contiguous transforms of length P, made as plans_for makes its plans
     // true: no traces, nothing to do.  Throws for a gather of more traces than the work space holds.
     bool idle(int nrec) const;
     template <class K, class... A> void launch(K kernel, dim3 grid, hipStream_t st, A... args);
@@ -126,7 +144,9 @@ class Conditioner {
     DevBuf<double> w2_, w2_sum_;   // W2 misfit: kW2Planes x [cap][nt], and w_r W_r per trace
     DevBuf<float> robust_scale_;   // robust misfits: A per trace
     DevBuf<double> robust_sum_;    // ... and 2 sum phi per trace
+    DevBuf<float2> fk_;            // fan filter: the transposed spectrum [nt + 1][Pcap]
     std::map<int, Plans> plans_;  // by number of traces
+    std::map<int, void *> fk_plans_;  // by padded channel count P
 };
 
 }  // namespace sepfwi

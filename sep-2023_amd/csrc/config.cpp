@@ -74,12 +74,30 @@ Params parse_params(const std::string &text) {
         if (!(p.filter[0] <= p.filter[1] && p.filter[1] <= p.filter[2] && p.filter[2] <= p.filter[3]))
             throw std::runtime_error("parameter JSON: filter corners must be ascending");
     }
+    if (j.has("fk_slowness")) {
+        const JsonValue &f = j.at("fk_slowness");
+        bool ok = f.kind == JsonValue::Array && f.arr.size() == 4;
+        for (int k = 0; ok && k < 4; k++) {
+            ok = f.arr[k].kind == JsonValue::Number && std::isfinite(f.arr[k].num);
+            if (ok) p.fk_slowness[k] = f.arr[k].num;
+        }
+        if (!ok) throw std::invalid_argument("parameter file: fk_slowness must be four finite numbers [p1, p2, p3, p4] in s/m");
+        if (!(p.fk_slowness[0] < p.fk_slowness[1] && p.fk_slowness[1] <= p.fk_slowness[2] && p.fk_slowness[2] < p.fk_slowness[3]))
+            throw std::invalid_argument("parameter file: fk_slowness needs p1 < p2 <= p3 < p4");
+        p.has_fk = true;
+    }
+    if (j.has("fk_mode")) {
+        const JsonValue &m = j.at("fk_mode");
+        if (m.kind != JsonValue::String || (m.str != "pass" && m.str != "reject")) throw std::invalid_argument("parameter file: fk_mode must be \"pass\" or \"reject\"");
+        if (!p.has_fk) throw std::invalid_argument("parameter file: fk_mode without fk_slowness");
+        p.fk_reject = m.str == "reject";
+    }
     p.if_win_key = p.if_win;
     if (j.has("conditioning")) {
         const std::string c = j.at("conditioning").as_string("conditioning");
         if (c == "reference") {
             p.conditioning_reference = true;
-            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = p.if_w2_misfit = false;
+            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = p.if_w2_misfit = p.has_fk = p.fk_reject = false;
             p.robust_misfit = 0;
         } else if (c != "live") {
             throw std::runtime_error("parameter JSON: conditioning must be \"live\" or \"reference\"");
@@ -139,9 +157,9 @@ Params parse_params(const std::string &text) {
         throw std::invalid_argument(std::string("parameter file: robust_misfit together with ") +
                                     (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : "if_src_update"))) +
                                     " is not supported");
-    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit)) {
+    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit || p.has_fk)) {
         const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
-        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : "robust_misfit")))));
+        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : (p.robust_misfit ? "robust_misfit" : "fk_slowness"))))));
         throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
                                     " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
     }

@@ -38,6 +38,14 @@ struct Params {
     // if_w2_misfit, if_src_update or joint weights.
     int robust_misfit = 0;  // RobustKind: 0 none, 1 huber, 2 cauchy
     double robust_delta = 0.0, robust_quantile = 0.9;
+    // optional keys "fk_slowness" [p1, p2, p3, p4] (s/m) / "fk_mode" ("pass" | "reject", default "pass") (no counterpart in the reference;
+    // conditioning.hpp, fk_filter): the apparent-slowness fan filter across a shot's channels, the third stage of the chain,
+    // C = FK . band-pass . window.  Four finite numbers p1 < p2 <= p3 < p4 (negative ones allowed: p > 0 is an event that arrives later at
+    // higher channel indices); fk_mode without fk_slowness is refused.  A live conditioning key like those above; refused together with
+    // joint weights.  The channel spacing comes from the survey: every shot's channels must lie on one straight, equally spaced line
+    // (host_checks.hpp: fk_channel_spacing; refused at session creation otherwise).
+    bool has_fk = false, fk_reject = false;
+    double fk_slowness[4] = {0, 0, 0, 0};
     // optional key "conditioning": "live" (default) -- the keys above switch their stage on; "reference" -- they are parsed
     // and validated like the reference does and then IGNORED like its driver does (every call site commented out,
     // libCUFD.cu:353-457): results are those of a file without them.  if_win_key keeps what the file said, because the survey

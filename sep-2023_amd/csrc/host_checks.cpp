@@ -1,6 +1,7 @@
 // host_checks.cpp -- see host_checks.hpp.
 #include "host_checks.hpp"
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -66,6 +67,26 @@ void receiver_cells(const Params &par, const Survey &survey, int nzc, int nx, in
                 throw std::runtime_error("survey: receiver " + std::to_string(r) + " of shot " + std::to_string(i) + " lies outside the grid");
             (*idx)[(size_t)(*rec_off)[i] + r] = sh.z_rec[r] * pitch + sh.x_rec[r];
         }
+    }
+}
+
+void fk_channel_spacing(const Params &par, const Survey &survey, std::vector<double> *delta) {
+    const int ns = (int)survey.shots.size();
+    delta->assign(ns, 0.0);
+    for (int i = 0; i < ns; i++) {
+        const Shot &sh = survey.shots[i];
+        if (!sh.present || sh.nrec <= 0) continue;
+        const std::string who = "fk_slowness: shot " + std::to_string(i);
+        if ((int)sh.z_rec.size() < sh.nrec || (int)sh.x_rec.size() < sh.nrec) throw std::invalid_argument(who + " lists fewer receiver coordinates than nrec");
+        if (sh.nrec == 1) throw std::invalid_argument(who + " has exactly one channel (channel 0): no channel spacing can be derived from it");
+        const long long sz = (long long)sh.z_rec[1] - sh.z_rec[0], sx = (long long)sh.x_rec[1] - sh.x_rec[0];
+        if (sz == 0 && sx == 0) throw std::invalid_argument(who + ": channel 1 lies on channel 0 (a zero step along the fibre)");
+        for (int r = 2; r < sh.nrec; r++)
+            if ((long long)sh.z_rec[r] - sh.z_rec[r - 1] != sz || (long long)sh.x_rec[r] - sh.x_rec[r - 1] != sx)
+                throw std::invalid_argument(who + ": the step to channel " + std::to_string(r) + " differs from the step (" + std::to_string(sz) + ", " + std::to_string(sx) +
+                                            ") of the channels before it (the fan filter needs one straight, equally spaced line of channels)");
+        const double az = (double)sz * (double)par.dz, ax = (double)sx * (double)par.dx;
+        (*delta)[i] = std::sqrt(az * az + ax * ax);
     }
 }
 

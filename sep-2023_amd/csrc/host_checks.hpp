@@ -28,4 +28,11 @@ void read_pack_index(const std::string &fname, int nSteps, long long file_size, 
 // channels) inside the stored rows / columns.  Throws std::runtime_error naming the shot and receiver.
 void receiver_cells(const Params &par, const Survey &survey, int nzc, int nx, int pitch, std::vector<int> *rec_off, std::vector<int> *idx);
 
+// Parameter key fk_slowness: the channel spacing [m] of every shot along its fibre, (*delta)[i] for shot i (0 for a shot that is absent or has
+// no channels: idle).  A shot's channels must lie on one straight, equally spaced line in channel order: (z_rec[r + 1] - z_rec[r],
+// x_rec[r + 1] - x_rec[r]) = (sz, sx) is the same for every r and not (0, 0); then the spacing is sqrt((sz dz)^2 + (sx dx)^2).  A shot with
+// exactly one channel, a step that changes and a zero step are refused: std::invalid_argument naming the key, the shot and the first
+// offending channel.
+void fk_channel_spacing(const Params &par, const Survey &survey, std::vector<double> *delta);
+
 }  // namespace sepfwi

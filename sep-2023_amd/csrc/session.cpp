@@ -165,7 +165,8 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     // commented lines take the trace norms of the cross-correlation misfit BEFORE the source update and use them after it.
     if (par.if_src_update && par.if_cross_misfit)
         throw std::invalid_argument("parameter file: if_src_update together with if_cross_misfit is not supported");
-    cond_on_ = par.if_win || par.has_filter || par.if_cross_misfit || par.if_src_update || par.if_envelope_misfit || par.if_w2_misfit || par.robust_misfit != 0;
+    cond_on_ = par.if_win || par.has_filter || par.if_cross_misfit || par.if_src_update || par.if_envelope_misfit || par.if_w2_misfit || par.robust_misfit != 0 || par.has_fk;
+    if (par.has_fk) fk_channel_spacing(par_, survey_, &fk_delta_);  // refuses a survey whose channels are no straight, equally spaced line: before anything is allocated
     joint_ = par.joint();
     geo_ncomp_ = geo_blocks(par, geo_block_);
     HIP_OK(hipSetDevice(gpu_id_));
@@ -192,6 +193,7 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
         if (par.if_envelope_misfit) cond_->ensure_envelope_buffers();
         if (par.if_w2_misfit) cond_->ensure_w2_buffers();
         if (par.robust_misfit) cond_->ensure_robust_buffers();
+        if (par.has_fk) cond_->ensure_fk_buffers();
     }
     h_io_.ensure(dlen);
     {

@@ -90,7 +90,7 @@ class Session {
     void order_after_null_stream(hipStream_t st);
     // ---- the data-conditioning chain (session_data.cpp), on [rec][it] gathers of one shot ---------------------------------------
     // C of the parameter file on one gather in place: window (if_win: per channel, with weights; else the end taper), then band-pass
-    // (filter); and C^T: band-pass, then window
+    // (filter), then the fan filter across the channels (fk_slowness); and C^T: fan filter, band-pass, then window
     void window_gather(hipStream_t st, float *gather, int shot_id, int nrec);
     void condition_gather(hipStream_t st, float *gather, int shot_id, int nrec);
     void condition_gather_t(hipStream_t st, float *gather, int shot_id, int nrec);
@@ -381,6 +381,7 @@ class Session {
     bool cond_on_ = false;
     float *win_ = nullptr, *xpose2_ = nullptr;
     std::vector<int> rec_off_;
+    std::vector<double> fk_delta_;  // parameter key fk_slowness: the channel spacing [m] of every shot (host_checks.hpp), filled at creation
     Fields fld_{}, adj_{};
     PmlMem mem_{};
     Media md_{};

@@ -2,7 +2,8 @@
 //
 // The Conditioner (conditioning.hip) owns the kernels, the FFT work space and the count of what it issues; the session owns the [rec][it]
 // scratch gathers xpose_, xpose2_, xpose3_ (one shot each: the chain runs on the call's MAIN stream, shot after shot) and the order of the
-// stages, that of the reference's commented lines (libCUFD.cu:353-457): C = band-pass . window (condition_gather), C^T
+// stages, that of the reference's commented lines (libCUFD.cu:353-457) with the apparent-slowness fan filter across a shot's channels
+// (fk_slowness / fk_mode, conditioning.hpp: fk_filter) as the third: C = FK . band-pass . window (condition_gather), C^T = window . band-pass . FK
 // (condition_gather_t), and the two middles misfit_chain and gn_chain (session.hpp).  Inside a call the middles run between two
 // transpositions of the shot's time-major gathers: residual_conditioned (run, adjoint_exact) and adjoint_source_conditioned (born); these
 // charge their transpositions and what the Conditioner counted across the chain to sepfwi_stats.launches.  (The observed store conditions a
@@ -40,15 +41,18 @@ void Session::window_gather(hipStream_t st, float *gather, int shot_id, int nrec
 }
 
 // Window and band-pass one [rec][it] gather in place, as the commented driver lines apply them to observed and synthetic
-// data alike (libCUFD.cu:353-374)
+// data alike (libCUFD.cu:353-374); then the fan filter across the shot's channels (fk_slowness; no counterpart in the reference) at the
+// shot's own channel spacing.  The stages are composed, not fused: band-pass and fan filter do not commute exactly (the crop between them).
 void Session::condition_gather(hipStream_t st, float *gather, int shot_id, int nrec) {
     window_gather(st, gather, shot_id, nrec);
     if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
+    if (par_.has_fk) cond_->fk_filter(st, gather, nrec, par_.dt, fk_delta_[shot_id], par_.fk_slowness, par_.fk_reject);
 }
 
-// Its transpose, as the commented lines apply it to the residual (libCUFD.cu:436-457): the (zero-phase, symmetric) filter, then the
-// (pointwise) window.
+// Its transpose, as the commented lines apply it to the residual (libCUFD.cu:436-457): the (symmetric) fan filter first, the (zero-phase,
+// symmetric) filter, then the (pointwise) window.
 void Session::condition_gather_t(hipStream_t st, float *gather, int shot_id, int nrec) {
+    if (par_.has_fk) cond_->fk_filter(st, gather, nrec, par_.dt, fk_delta_[shot_id], par_.fk_slowness, par_.fk_reject);
     if (par_.has_filter) cond_->bandpass(st, gather, nrec, par_.dt, par_.filter);
     window_gather(st, gather, shot_id, nrec);
 }

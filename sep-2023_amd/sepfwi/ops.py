@@ -455,8 +455,9 @@ class _FwiOps:
     # -- the conditioning operator of a parameter file (sepfwi_condition) -----------------------------
     def condition(self, d, Shot_ids, para_fname, transpose=False, gpu_id=0):
         """C d (or C^T d with transpose=True) of the parameter file: what the session applies to a synthetic axial-strain gather before
-        the residual -- per-channel windows with weights (if_win) or the end taper, then the band-pass (filter); C^T: the band-pass, then
-        the window; the identity when no conditioning key is live.  d: the per-shot dict list that `born` returns (every component of
+        the residual -- per-channel windows with weights (if_win) or the end taper, then the band-pass (filter), then the apparent-slowness
+        (f-k) fan filter across each shot's channels (fk_slowness / fk_mode: include/sepfwi.h, sepfwi_cufd); C^T: the fan filter, the
+        band-pass, then the window; the identity when no conditioning key is live.  d: the per-shot dict list that `born` returns (every component of
         every dict is conditioned; a new list comes back), or ONE float32 tensor holding the gathers [nrec_i][nSteps] shot after shot in
         the order of Shot_ids (any shape with that many elements; a new tensor of the same shape and device comes back).  The input
         is never changed.  With it a caller composes J^T C^T Z C J from `born` and `born_adjoint`, which stay in raw data space."""
@@ -520,6 +521,7 @@ class _FwiOps:
         if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (the
         trace-wise quadratic Wasserstein distance W of include/sepfwi.h, sepfwi_cufd; double arithmetic, rounded once), C^T Z psi under robust_misfit (the Huber / Cauchy penalty with the per-trace quantile scale, csrc/robust_misfit.hpp).  Under if_src_update the matching filter is computed
         from the call's own (C obs, C syn), shot by shot; the misfit is that of the updated synthetics and a holds the filter fixed.
+        C includes the fan filter across each shot's channels under fk_slowness / fk_mode (C = FK . band-pass . window), under every kind.
         With `born_adjoint` a caller composes a gradient pass: g = -J^T a."""
         (obs, syn), ids, dev, stream = self._data_args((obs, syn), ("obs", "syn"), Shot_ids, para_fname, gpu_id)
         adj = torch.empty_like(syn)
@@ -531,7 +533,8 @@ class _FwiOps:
     def data_gn(self, syn, d, Shot_ids, para_fname, gpu_id=0, obs=None):
         """The Gauss-Newton operator of the parameter file's misfit in data space, at syn, applied to d (sepfwi_data_gn): C^T Z C d under
         an L2 file, C^T D^T Z D C d under if_envelope_misfit (D the derivative of the squared envelope at C syn).  Layout as data_misfit;
-        -> a new tensor like d.  Symmetric and non-negative; refused under if_cross_misfit, if_src_update and if_w2_misfit.  `born`, this and
+        -> a new tensor like d.  C includes the fan filter under fk_slowness / fk_mode, as in `condition`.  Symmetric and non-negative;
+        refused under if_cross_misfit, if_src_update and if_w2_misfit.  `born`, this and
         `born_adjoint` compose the product J^T (.) J v.
         obs (the observed gathers, laid out like syn): the call goes to sepfwi_data_gn_obs, the operator at (obs, syn).  Under robust_misfit
         it is C^T Z W Z C d with the IRLS weight W of (C obs, C syn) (csrc/robust_misfit.hpp) and obs is required -- without it the library

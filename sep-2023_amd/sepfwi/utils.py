@@ -36,7 +36,8 @@ def padding(cp, cs, den, nz_orig, nx_orig, nz, nx, nPml, nPad):
 def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname, data_dir_name,
             if_win=False, filter_para=None, if_src_update=False, scratch_dir_name="", if_cross_misfit=False,
             das_fiber="horizontal", obs_pack_fname=None, conditioning=None, obs_cache_mb=None, das_gauge_length=None, misfit_weights=None,
-            if_envelope_misfit=False, if_w2_misfit=False, w2_beta=None, robust_misfit=None, robust_delta=None, robust_quantile=None):
+            if_envelope_misfit=False, if_w2_misfit=False, w2_beta=None, robust_misfit=None, robust_delta=None, robust_quantile=None,
+            fk_slowness=None, fk_mode=None):
     """Write the one-line parameter JSON (schema of fwi_utils.py:46-83; nz, nx are the PADDED sizes).
     das_fiber (extension): "horizontal" = axial strain exx = vx(x) - vx(x-1), the reference's live
     choice; "vertical" = ezz = vz(z) - vz(z-1) (recording_ezz / res_injection_ezz, Src/utilities.cu:620-641, which the
@@ -58,6 +59,12 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
     samples |C obs| (csrc/robust_misfit.hpp).  robust_delta is required with robust_misfit (finite, > 0; no default: it depends on the
     data's noise), robust_quantile in (0, 1], the library's default 0.9; either without robust_misfit is refused, here as in the library.
     Refused by the library together with if_cross_misfit, if_envelope_misfit, if_w2_misfit, if_src_update or misfit_weights.  Each key is
+    written only when set.
+    fk_slowness / fk_mode (extension): fk_slowness [p1, p2, p3, p4] in s/m switches on the apparent-slowness (f-k) fan filter across every
+    shot's channels, the third stage of the conditioning chain (C = FK . band-pass . window; csrc/conditioning.hpp, fk_filter): four finite
+    numbers p1 < p2 <= p3 < p4, p > 0 an event that arrives later at higher channel indices; fk_mode "pass" (the library's default) keeps the
+    band, "reject" removes it; fk_mode without fk_slowness is refused, here as in the library.  The survey's channels must lie on one
+    straight, equally spaced line per shot (the library refuses the session otherwise); refused together with misfit_weights.  Each key is
     written only when set."""
     para = {"nz": int(nz), "nx": int(nx), "dz": dz, "dx": dx, "nSteps": int(nSteps), "dt": float(dt),
             "f0": f0, "nPoints_pml": int(nPml), "nPad": int(nPad)}
@@ -96,6 +103,17 @@ def paraGen(nz, nx, dz, dx, nSteps, dt, f0, nPml, nPad, para_fname, survey_fname
         if not 0 < robust_quantile <= 1:
             raise ValueError("robust_quantile must be in (0, 1]")
         para["robust_quantile"] = float(robust_quantile)
+    if fk_slowness is not None:
+        p = [float(v) for v in fk_slowness]
+        if len(p) != 4 or not all(np.isfinite(v) for v in p) or not (p[0] < p[1] <= p[2] < p[3]):
+            raise ValueError("fk_slowness must be four finite numbers p1 < p2 <= p3 < p4")
+        para["fk_slowness"] = p
+    if fk_mode is not None:
+        if fk_mode not in ("pass", "reject"):
+            raise ValueError("fk_mode must be 'pass' or 'reject'")
+        if fk_slowness is None:
+            raise ValueError("fk_mode without fk_slowness")
+        para["fk_mode"] = fk_mode
     if das_fiber != "horizontal":
         if das_fiber != "vertical":
             raise ValueError("das_fiber must be 'horizontal' or 'vertical'")

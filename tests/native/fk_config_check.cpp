@@ -1,0 +1,167 @@
+// CPU-only check of the parameter keys "fk_slowness" / "fk_mode" in the host-side parser of libsepfwi (csrc/config.cpp) and of the channel
+// spacing that the session derives from the survey under the key (csrc/host_checks.cpp: fk_channel_spacing): built with
+// -fsanitize=address,undefined by tests/test_fk_config.py.  The keys parse, "conditioning": "reference" validates and then ignores them like
+// the other conditioning keys, every refusal is a std::invalid_argument -- the class that the C ABI reports as SEPFWI_EINVAL (csrc/capi.cpp)
+// -- in a message that names its keys, and the geometry refusals name the shot and the first offending channel.
+#include <cmath>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../sep-2023_amd/csrc/config.hpp"
+#include "../../sep-2023_amd/csrc/host_checks.hpp"
+
+using namespace sepfwi;
+
+static const char *BASE =
+    "{\"nz\": 96, \"nx\": 80, \"dz\": 5.0, \"dx\": 10.0, \"nSteps\": 100, \"dt\": 0.001, \"f0\": 10.0, \"nPoints_pml\": 10, "
+    "\"nPad\": 12, \"survey_fname\": \"s.json\", \"data_dir_name\": \"D\"";
+static const char *FK = ", \"fk_slowness\": [-0.0002, 0.0001, 0.0006, 0.0009]";
+
+static std::string doc(const std::string &more) { return std::string(BASE) + more + "}"; }
+
+static int failures = 0;
+static void fail(const char *what) {
+    printf("FAIL: %s\n", what);
+    failures++;
+}
+
+// -> 0 accepted, 1 std::invalid_argument naming both keys, 2 std::invalid_argument with another message, 3 any other exception
+static int refusal(const std::string &more, const char *key_a, const char *key_b) {
+    try {
+        (void)parse_params(doc(more));
+    } catch (const std::invalid_argument &e) {
+        const std::string w = e.what();
+        return (w.find(key_a) != std::string::npos && w.find(key_b) != std::string::npos) ? 1 : 2;
+    } catch (const std::exception &) {
+        return 3;
+    }
+    return 0;
+}
+
+// a survey of one shot per (z, x) list, already shifted like parse_survey's
+static Survey survey_of(const std::vector<std::pair<std::vector<int>, std::vector<int>>> &shots) {
+    Survey s;
+    s.nShots = (int)shots.size();
+    for (const auto &zx : shots) {
+        Shot sh;
+        sh.present = true;
+        sh.z_rec = zx.first;
+        sh.x_rec = zx.second;
+        sh.nrec = (int)zx.first.size();
+        if (sh.nrec > s.max_nrec) s.max_nrec = sh.nrec;
+        s.shots.push_back(sh);
+    }
+    return s;
+}
+
+// -> 0 accepted, 1 std::invalid_argument naming the key, "shot <shot>" and "channel <channel>", 2 another message, 3 another exception
+static int geometry_refusal(const Params &p, const Survey &s, int shot, int channel) {
+    std::vector<double> d;
+    try {
+        fk_channel_spacing(p, s, &d);
+    } catch (const std::invalid_argument &e) {
+        const std::string w = e.what();
+        return (w.find("fk_slowness") != std::string::npos && w.find("shot " + std::to_string(shot)) != std::string::npos &&
+                w.find("channel " + std::to_string(channel)) != std::string::npos) ? 1 : 2;
+    } catch (const std::exception &) {
+        return 3;
+    }
+    return 0;
+}
+
+int main() {
+    // ---- the parser ----
+    {
+        const Params p = parse_params(doc(""));
+        if (p.has_fk || p.fk_reject) fail("absent keys read as set");
+    }
+    {
+        const Params p = parse_params(doc(FK));
+        if (!p.has_fk || p.fk_reject || p.fk_slowness[0] != -0.0002 || p.fk_slowness[1] != 0.0001 || p.fk_slowness[2] != 0.0006 || p.fk_slowness[3] != 0.0009)
+            fail("fk_slowness alone mis-parsed");
+        if (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit || p.joint()) fail("fk_slowness switches another key on");
+    }
+    if (!parse_params(doc(std::string(FK) + ", \"fk_mode\": \"reject\"")).fk_reject) fail("fk_mode reject not read");
+    if (parse_params(doc(std::string(FK) + ", \"fk_mode\": \"pass\"")).fk_reject) fail("fk_mode pass reads as reject");
+    if (!parse_params(doc(", \"fk_slowness\": [0.0001, 0.0003, 0.0003, 0.0007]")).has_fk) fail("p2 == p3 refused");
+    {   // it composes with every other live conditioning key
+        const Params p = parse_params(doc(std::string(FK) + ", \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0], \"if_envelope_misfit\": true"));
+        if (!p.has_fk || !p.if_win || !p.has_filter || !p.if_envelope_misfit) fail("fk with if_win, filter and if_envelope_misfit mis-parsed");
+        for (const char *k : {", \"if_cross_misfit\": true", ", \"if_src_update\": true", ", \"if_w2_misfit\": true", ", \"robust_misfit\": \"huber\", \"robust_delta\": 1.5"})
+            if (refusal(std::string(FK) + k, "", "") != 0) fail("fk with another misfit kind refused");
+    }
+    // the refusals of the values, each a std::invalid_argument naming the key
+    for (const char *v : {"[0.0001, 0.0002, 0.0003]", "[0.0001, 0.0002, 0.0003, 0.0004, 0.0005]", "0.0001", "\"pass\"", "[0.0001, 0.0002, \"x\", 0.0004]", "[0.0001, 0.0002, 0.0003, 1e999]",
+                          "[0.0002, 0.0002, 0.0003, 0.0004]", "[0.0001, 0.0003, 0.0002, 0.0004]", "[0.0001, 0.0002, 0.0004, 0.0004]", "[0.0004, 0.0003, 0.0002, 0.0001]", "[]"})
+        if (refusal(std::string(", \"fk_slowness\": ") + v, "fk_slowness", "fk_slowness") != 1) {
+            printf("value %s\n", v);
+            fail("a bad fk_slowness accepted or misreported");
+        }
+    for (const char *v : {"\"keep\"", "true", "1", "\"\""})
+        if (refusal(std::string(FK) + ", \"fk_mode\": " + v, "fk_mode", "fk_mode") != 1) fail("a bad fk_mode accepted or misreported");
+    if (refusal(", \"fk_mode\": \"reject\"", "fk_mode", "fk_slowness") != 1) fail("fk_mode without fk_slowness");
+    if (refusal(", \"fk_mode\": \"pass\", \"filter\": [1.0, 2.0, 8.0, 10.0]", "fk_mode", "fk_slowness") != 1) fail("fk_mode without fk_slowness, beside filter");
+    // joint weights other than (1, 0, 0): the existing rule and message, the key the last of its order
+    if (refusal(std::string(FK) + ", \"misfit_w_vx\": 0.5", "misfit_w_vx", "fk_slowness") != 1) fail("joint weights (vx)");
+    if (refusal(std::string(FK) + ", \"misfit_w_vz\": 2.0", "misfit_w_vz", "fk_slowness") != 1) fail("joint weights (vz)");
+    if (refusal(std::string(FK) + ", \"misfit_w_ett\": 0.5", "misfit_w_ett", "fk_slowness") != 1) fail("joint weights (ett alone, not 1)");
+    if (refusal(std::string(FK) + ", \"if_win\": true, \"misfit_w_vx\": 0.5", "misfit_w_vx", "if_win") != 1) fail("joint weights with if_win: the first live key of the old order is named");
+    if (refusal(std::string(FK) + ", \"robust_misfit\": \"cauchy\", \"robust_delta\": 2.0, \"misfit_w_vx\": 0.5", "misfit_w_vx", "robust_misfit") != 1) fail("joint weights with robust_misfit");
+    if (refusal(std::string(FK) + ", \"misfit_w_ett\": 1.0, \"misfit_w_vx\": 0.0", "", "") != 0) fail("default weights refused");
+    {   // reference mode: parsed, validated, ignored -- also with joint weights
+        const Params p = parse_params(doc(std::string(FK) + ", \"fk_mode\": \"reject\", \"filter\": [1.0, 2.0, 8.0, 10.0], \"conditioning\": \"reference\""));
+        if (!p.conditioning_reference || p.has_fk || p.fk_reject || p.has_filter) fail("reference mode does not ignore the keys");
+        const Params q = parse_params(doc(std::string(FK) + ", \"misfit_w_vx\": 0.5, \"conditioning\": \"reference\""));
+        if (q.has_fk || !q.joint()) fail("reference mode with joint weights mis-parsed");
+        if (refusal(", \"fk_slowness\": [0.0002, 0.0001, 0.0003, 0.0004], \"conditioning\": \"reference\"", "fk_slowness", "fk_slowness") != 1) fail("reference mode does not validate fk_slowness");
+        if (refusal(", \"fk_mode\": \"reject\", \"conditioning\": \"reference\"", "fk_mode", "fk_slowness") != 1) fail("reference mode does not validate fk_mode");
+        if (!parse_params(doc(std::string(FK) + ", \"conditioning\": \"live\"")).has_fk) fail("conditioning = live drops the key");
+    }
+    // what the parser accepted and refused before, it still does
+    if (refusal("", "", "") != 0 || refusal(", \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0]", "", "") != 0 || refusal(", \"if_cross_misfit\": true", "", "") != 0 ||
+        refusal(", \"robust_misfit\": \"huber\", \"robust_delta\": 1.5, \"robust_quantile\": 0.5", "", "") != 0 || refusal(", \"if_w2_misfit\": true, \"w2_beta\": 4.0", "", "") != 0)
+        fail("a file without the keys refused");
+    if (refusal(", \"if_envelope_misfit\": true, \"if_cross_misfit\": true", "if_envelope_misfit", "if_cross_misfit") != 1) fail("envelope / cross pair");
+    if (refusal(", \"if_cross_misfit\": true, \"misfit_w_vx\": 0.5", "misfit_w_vx", "if_cross_misfit") != 1) fail("joint weights with if_cross_misfit");
+    if (refusal(", \"robust_misfit\": \"huber\", \"robust_delta\": 1.5, \"misfit_w_vx\": 0.5", "misfit_w_vx", "robust_misfit") != 1) fail("joint weights with robust_misfit alone");
+    if (refusal(", \"robust_delta\": 1.5", "robust_delta", "robust_misfit") != 1) fail("robust_delta without robust_misfit");
+    if (refusal(", \"filter\": [3.0, 2.0, 8.0, 10.0]", "", "") != 3) fail("descending filter corners: the reader's own error class");
+
+    // ---- the channel spacing: dz = 5, dx = 10 ----
+    const Params par = parse_params(doc(FK));
+    {
+        const Survey s = survey_of({{{30, 30, 30, 30}, {14, 15, 16, 17}},      // horizontal
+                                    {{14, 15, 16}, {40, 40, 40}},              // vertical
+                                    {{30, 30, 30}, {14, 17, 20}},              // strided
+                                    {{20, 22, 24, 26, 28}, {50, 49, 48, 47, 46}},      // diagonal, x descending
+                                    {{}, {}},                                  // no channels: idle
+                                    {{33, 30}, {20, 20}}});                    // two channels, upwards
+        std::vector<double> d;
+        fk_channel_spacing(par, s, &d);
+        const double want[6] = {10.0, 5.0, 30.0, std::sqrt(10.0 * 10.0 + 10.0 * 10.0), 0.0, 15.0};
+        if (d.size() != 6) fail("one spacing per shot");
+        for (size_t i = 0; i < d.size() && i < 6; i++)
+            if (std::fabs(d[i] - want[i]) > 1e-12) {
+                printf("shot %zu: %.17g, want %.17g\n", i, d[i], want[i]);
+                fail("channel spacing");
+            }
+        Survey absent = s;
+        absent.shots[1].present = false;
+        absent.shots[1].z_rec = {1};      // nothing of an absent shot is read
+        absent.shots[1].nrec = 7;
+        fk_channel_spacing(par, absent, &d);
+        if (d[1] != 0.0 || d[0] != 10.0) fail("an absent shot");
+    }
+    if (geometry_refusal(par, survey_of({{{30, 30}, {14, 15}}, {{30}, {14}}}), 1, 0) != 1) fail("a shot with one channel");
+    if (geometry_refusal(par, survey_of({{{30, 30, 30, 30}, {14, 15, 17, 18}}}), 0, 2) != 1) fail("a step that changes");
+    if (geometry_refusal(par, survey_of({{{30, 30}, {14, 15}}, {{30, 30}, {14, 15}}, {{30, 30, 31, 31}, {14, 15, 16, 17}}}), 2, 2) != 1) fail("a bend");
+    if (geometry_refusal(par, survey_of({{{30, 30, 30}, {14, 14, 14}}}), 0, 1) != 1) fail("a zero step");
+    if (geometry_refusal(par, survey_of({{{30, 30, 30}, {14, 15, 15}}}), 0, 2) != 1) fail("a zero step later on the line");
+    if (geometry_refusal(par, survey_of({{{30, 31, 30, 31}, {14, 15, 16, 17}}}), 0, 2) != 1) fail("a zig-zag");
+    if (geometry_refusal(par, survey_of({{{30, 30, 30}, {16, 15, 14}}}), 0, 0) != 0) fail("a descending line refused");
+    if (failures) return 1;
+    printf("OK\n");
+    return 0;
+}
