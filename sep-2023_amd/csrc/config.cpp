@@ -41,9 +41,9 @@ Params parse_params(const std::string &text) {
     }
     if (j.has("if_win")) p.if_win = j.at("if_win").as_bool("if_win");
     if (j.has("if_src_update")) p.if_src_update = j.at("if_src_update").as_bool("if_src_update");
-    if (j.has("if_cross_misfit")) p.if_cross_misfit = j.at("if_cross_misfit").as_bool("if_cross_misfit");
-    if (j.has("if_envelope_misfit")) p.if_envelope_misfit = j.at("if_envelope_misfit").as_bool("if_envelope_misfit");
-    if (j.has("if_w2_misfit")) p.if_w2_misfit = j.at("if_w2_misfit").as_bool("if_w2_misfit");
+    bool kind_set[kMisfitKinds] = {};  // the kind keys the file sets: more than one may be, until the rule below has refused the pair
+    for (Misfit m : {Misfit::Cross, Misfit::Envelope, Misfit::W2})
+        if (j.has(traits(m).key)) kind_set[(int)m] = j.at(traits(m).key).as_bool(traits(m).key);
     if (j.has("w2_beta")) {
         p.w2_beta = j.at("w2_beta").as_number("w2_beta");
         if (!(std::isfinite(p.w2_beta) && p.w2_beta > 0.0 && p.w2_beta <= 16.0))
@@ -52,7 +52,8 @@ Params parse_params(const std::string &text) {
     if (j.has("robust_misfit")) {
         const std::string k = j.at("robust_misfit").as_string("robust_misfit");
         if (k != "huber" && k != "cauchy") throw std::invalid_argument("parameter file: robust_misfit must be \"huber\" or \"cauchy\"");
-        p.robust_misfit = k == "huber" ? 1 : 2;
+        kind_set[(int)Misfit::Robust] = true;
+        p.robust_kind = k == "huber" ? 1 : 2;
         // no default: the right threshold depends on the data's noise, and nothing here can derive one
         if (!j.has("robust_delta")) throw std::invalid_argument("parameter file: robust_misfit needs robust_delta (finite, above 0; there is no default)");
     } else if (j.has("robust_delta") || j.has("robust_quantile")) {
@@ -97,8 +98,8 @@ Params parse_params(const std::string &text) {
         const std::string c = j.at("conditioning").as_string("conditioning");
         if (c == "reference") {
             p.conditioning_reference = true;
-            p.if_win = p.if_src_update = p.if_cross_misfit = p.has_filter = p.if_envelope_misfit = p.if_w2_misfit = p.has_fk = p.fk_reject = false;
-            p.robust_misfit = 0;
+            p.if_win = p.if_src_update = p.has_filter = p.has_fk = p.fk_reject = false;
+            p.robust_kind = 0;  // (and the kind keys resolve to no kind below: misfit stays L2)
         } else if (c != "live") {
             throw std::runtime_error("parameter JSON: conditioning must be \"live\" or \"reference\"");
         }
@@ -142,28 +143,32 @@ Params parse_params(const std::string &text) {
         if (!p.obs_pack_fname.empty())
             throw std::invalid_argument(std::string("parameter file: ") + key + " > 0 together with obs_pack_fname is not supported (the packed file holds axial strain only)");
     }
-    // the envelope misfit is neither a correlation of the traces nor linear in them: the trace norms of the cross-correlation misfit and the
-    // matching filter of the source update have no meaning on envelopes
-    if (p.if_envelope_misfit && (p.if_cross_misfit || p.if_src_update))
-        throw std::invalid_argument(std::string("parameter file: if_envelope_misfit together with ") + (p.if_cross_misfit ? "if_cross_misfit" : "if_src_update") +
-                                    " is not supported");
-    // the W2 misfit is one misfit kind among three, and its densities are normalised trace by trace: a matching filter fitted to the
-    // gathers has no meaning for it either
-    if (p.if_w2_misfit && (p.if_cross_misfit || p.if_envelope_misfit || p.if_src_update))
-        throw std::invalid_argument(std::string("parameter file: if_w2_misfit together with ") +
-                                    (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : "if_src_update")) + " is not supported");
-    // a robust misfit is one misfit kind among four; a matching filter fitted to gathers with outliers is what the key is there to avoid
-    if (p.robust_misfit && (p.if_cross_misfit || p.if_envelope_misfit || p.if_w2_misfit || p.if_src_update))
-        throw std::invalid_argument(std::string("parameter file: robust_misfit together with ") +
-                                    (p.if_cross_misfit ? "if_cross_misfit" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : "if_src_update"))) +
-                                    " is not supported");
-    if (p.joint() && (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit || p.has_fk)) {
+    // A file has one misfit kind: each kind key it sets is refused with the first kind key before it in the table's order that is set
+    // too.  Then with if_src_update, where the kind's row says so: the matching filter fitted to the gathers has no meaning on envelopes
+    // (not linear in the traces) or on densities normalised trace by trace (W2), and is what a robust misfit is there to avoid.
+    for (int k = 1; k < kMisfitKinds; k++) {
+        if (!kind_set[k] || p.conditioning_reference) continue;
+        const char *partner = p.if_src_update && !kMisfitTraits[k].with_src_update ? "if_src_update" : nullptr;
+        for (int q = k - 1; q >= 1; q--)
+            if (kind_set[q]) partner = kMisfitTraits[q].key;
+        if (partner) throw std::invalid_argument(std::string("parameter file: ") + kMisfitTraits[k].key + " together with " + partner + " is not supported");
+        p.misfit = (Misfit)k;
+    }
+    if (p.joint() && p.first_live_key()) {
         const char *key = p.w_vx > 0.0f ? "misfit_w_vx" : (p.w_vz > 0.0f ? "misfit_w_vz" : "misfit_w_ett");
-        const char *cond = p.if_win ? "if_win" : (p.has_filter ? "filter" : (p.if_cross_misfit ? "if_cross_misfit" : (p.if_src_update ? "if_src_update" : (p.if_envelope_misfit ? "if_envelope_misfit" : (p.if_w2_misfit ? "if_w2_misfit" : (p.robust_misfit ? "robust_misfit" : "fk_slowness"))))));
-        throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + cond +
+        throw std::invalid_argument(std::string("parameter file: ") + key + " together with the live conditioning key " + p.first_live_key() +
                                     " is not supported (the conditioning chain acts on axial-strain gathers weighted 1)");
     }
     return p;
+}
+
+const char *Params::first_live_key() const {
+    if (if_win) return "if_win";
+    if (has_filter) return "filter";
+    if (misfit == Misfit::Cross) return traits(misfit).key;
+    if (if_src_update) return "if_src_update";
+    if (misfit != Misfit::L2) return traits(misfit).key;
+    return has_fk ? "fk_slowness" : nullptr;
 }
 
 Survey parse_survey(const std::string &text, int nPml, bool if_win) {

@@ -7,6 +7,30 @@
 
 namespace sepfwi {
 
+// The misfit kind of a parameter file, and per kind the facts that the parser and the session branch on.  A new kind is a new enumerator,
+// a new row and a new case in the switches over Params::misfit (none has a default: the compiler names the ones that miss it).
+enum class Misfit { L2, Cross, Envelope, W2, Robust };
+struct MisfitTraits {
+    const char *key;        // the JSON key that selects the kind (nullptr: L2, the absence of the others)
+    bool gauss_newton;      // a Gauss-Newton product exists: born's hv_*, the exact product, data_gn (the others are no least squares of the data)
+    bool at_background;     // ... and it linearises at the shot's BACKGROUND gather, which those calls record or take (syn)
+    bool needs_obs;         // ... and it needs the conditioned observed gather (the IRLS weight)
+    bool exact_adjoint;     // adjoint_exact serves the kind's gradient
+    bool trace_weights;     // the residual takes the survey's trace weights and src_weight explicitly (under if_win)
+    bool with_src_update;   // parse_params accepts if_src_update beside the key (Cross: Session's constructor refuses the pair, after the survey is read)
+};
+constexpr MisfitTraits kMisfitTraits[] = {
+    //                         key             gn     at_bg  obs    exact  trace_w  src_update
+    /* L2       */ {nullptr,               true,  false, false, true,  false, true},
+    /* Cross    */ {"if_cross_misfit",     false, false, false, false, true,  true},
+    /* Envelope */ {"if_envelope_misfit",  true,  true,  false, true,  false, false},
+    /* W2       */ {"if_w2_misfit",        false, false, false, true,  true,  false},
+    /* Robust   */ {"robust_misfit",       true,  true,  true,  true,  false, false},
+};
+constexpr int kMisfitKinds = (int)Misfit::Robust + 1;
+static_assert(sizeof(kMisfitTraits) / sizeof(kMisfitTraits[0]) == kMisfitKinds, "one row of kMisfitTraits per Misfit kind, in the enum's order");
+inline const MisfitTraits &traits(Misfit m) { return kMisfitTraits[(int)m]; }
+
 struct Params {
     int nz = 0, nx = 0;  // padded grid sizes
     float dz = 0, dx = 0, dt = 0, f0 = 0;
@@ -18,32 +42,24 @@ struct Params {
     // optional key "obs_cache_mb": HBM budget [MB] of the session's observed-data store; the least recently used gathers beyond it
     // wait in pinned host memory (obs_store.hpp).  0 / absent: no budget (option "obs_cache_mb" of sepfwi_set_option applies).
     int obs_cache_mb = 0;
-    // data-conditioning keys (dormant in the reference's driver, libCUFD.cu:353-457; live here, csrc/conditioning.hip)
-    bool if_win = false, if_src_update = false, if_cross_misfit = false, has_filter = false;
-    // optional key "if_envelope_misfit" (no counterpart in the reference; conditioning.hip): the misfit compares the squared envelopes
-    // e(x) = x^2 + (H x)^2 of the conditioned gathers instead of the gathers.  A live conditioning key like the four above; refused
-    // together with if_cross_misfit or if_src_update.
-    bool if_envelope_misfit = false;
-    // optional keys "if_w2_misfit" / "w2_beta" (no counterpart in the reference; w2_misfit.hpp): the misfit is the trace-wise quadratic
-    // Wasserstein distance between the softplus densities of the conditioned gathers, softplus(w2_beta x / max |obs trace|); w2_beta in
-    // (0, 16], default 3.  A live conditioning key like the five above; refused together with if_cross_misfit, if_envelope_misfit,
-    // if_src_update or joint weights.
-    bool if_w2_misfit = false;
+    // data-conditioning keys (dormant in the reference's driver, libCUFD.cu:353-457; live here, csrc/conditioning.hip).  if_src_update is a
+    // stage of the chain (the matching filter), not a misfit kind; kMisfitTraits says which kinds it may accompany.
+    bool if_win = false, if_src_update = false, has_filter = false;
+    // the file's misfit kind, from the keys "if_cross_misfit" / "if_envelope_misfit" / "if_w2_misfit" / "robust_misfit" ("huber" | "cauchy")
+    // (live conditioning keys like those above; at most one may be set).  What the kinds compute: include/sepfwi.h, sepfwi_cufd, and
+    // conditioning.hpp, w2_misfit.hpp, robust_misfit.hpp; what each serves and is refused with: kMisfitTraits, nowhere else.  Their numbers:
+    // w2_beta in (0, 16]; robust_delta REQUIRED with robust_misfit (finite, above 0; no default: it depends on the data's noise),
+    // robust_quantile in (0, 1]; robust_delta or robust_quantile without robust_misfit is refused.
+    Misfit misfit = Misfit::L2;
     double w2_beta = 3.0;
-    // optional keys "robust_misfit" ("huber" | "cauchy") / "robust_delta" / "robust_quantile" (no counterpart in the reference;
-    // robust_misfit.hpp): the misfit is the Huber or Cauchy penalty of the conditioned residual with the threshold robust_delta A per trace,
-    // A the order statistic floor(robust_quantile (n - 1)) of the n live samples |C obs|.  robust_delta is REQUIRED with the key (finite,
-    // above 0; no default: it depends on the data's noise); robust_quantile in (0, 1], default 0.9.  robust_delta or robust_quantile without
-    // robust_misfit is refused.  A live conditioning key like those above; refused together with if_cross_misfit, if_envelope_misfit,
-    // if_w2_misfit, if_src_update or joint weights.
-    int robust_misfit = 0;  // RobustKind: 0 none, 1 huber, 2 cauchy
+    int robust_kind = 0;  // RobustKind (robust_misfit.hpp): 1 huber, 2 cauchy; 0 unless misfit is Robust
     double robust_delta = 0.0, robust_quantile = 0.9;
     // optional keys "fk_slowness" [p1, p2, p3, p4] (s/m) / "fk_mode" ("pass" | "reject", default "pass") (no counterpart in the reference;
     // conditioning.hpp, fk_filter): the apparent-slowness fan filter across a shot's channels, the third stage of the chain,
     // C = FK . band-pass . window.  Four finite numbers p1 < p2 <= p3 < p4 (negative ones allowed: p > 0 is an event that arrives later at
-    // higher channel indices); fk_mode without fk_slowness is refused.  A live conditioning key like those above; refused together with
-    // joint weights.  The channel spacing comes from the survey: every shot's channels must lie on one straight, equally spaced line
-    // (host_checks.hpp: fk_channel_spacing; refused at session creation otherwise).
+    // higher channel indices); fk_mode without fk_slowness is refused.  A live conditioning key like those above.  The channel spacing
+    // comes from the survey: every shot's channels must lie on one straight, equally spaced line (host_checks.hpp: fk_channel_spacing;
+    // refused at session creation otherwise).
     bool has_fk = false, fk_reject = false;
     double fk_slowness[4] = {0, 0, 0, 0};
     // optional key "conditioning": "live" (default) -- the keys above switch their stage on; "reference" -- they are parsed
@@ -63,6 +79,9 @@ struct Params {
     float w_ett = 1.0f, w_vx = 0.0f, w_vz = 0.0f;
     bool joint() const { return !(w_ett == 1.0f && w_vx == 0.0f && w_vz == 0.0f); }  // the joint path (geophone.hip) serves the call
     float weight(int comp) const { return comp == 1 ? w_vx : (comp == 2 ? w_vz : (comp == 3 ? w_ett : 0.0f)); }  // comp: 1 vx, 2 vz, 3 ett
+    // The first live conditioning key in the order if_win, filter, if_cross_misfit, if_src_update, if_envelope_misfit, if_w2_misfit,
+    // robust_misfit, fk_slowness, or nullptr: a file without one has C = 1 and no conditioner.  Joint weights are refused with any.
+    const char *first_live_key() const;
 };
 
 struct Shot {

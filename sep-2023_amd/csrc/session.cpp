@@ -163,9 +163,9 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
     // line, source_update_adj at :430-433, acts on the pressure residual that is never injected).  Here a key switches its
     // stage on for the axial-strain gathers (conditioning.hip).  One combination has no defined meaning there either: the
     // commented lines take the trace norms of the cross-correlation misfit BEFORE the source update and use them after it.
-    if (par.if_src_update && par.if_cross_misfit)
+    if (par.if_src_update && par.misfit == Misfit::Cross)
         throw std::invalid_argument("parameter file: if_src_update together with if_cross_misfit is not supported");
-    cond_on_ = par.if_win || par.has_filter || par.if_cross_misfit || par.if_src_update || par.if_envelope_misfit || par.if_w2_misfit || par.robust_misfit != 0 || par.has_fk;
+    cond_on_ = par.first_live_key() != nullptr;
     if (par.has_fk) fk_channel_spacing(par_, survey_, &fk_delta_);  // refuses a survey whose channels are no straight, equally spaced line: before anything is allocated
     joint_ = par.joint();
     geo_ncomp_ = geo_blocks(par, geo_block_);
@@ -190,9 +190,12 @@ Session::Session(const std::string &para_fname, int gpu_id, const std::string &p
         xpose2_ = dalloc<float>(dlen);
         cond_.reset(new Conditioner(par.nSteps, std::max(1, survey_.max_nrec)));
         if (par.if_src_update) cond_->ensure_source_buffers(own_stream_);  // now: no shot pays an allocation inside its time loop
-        if (par.if_envelope_misfit) cond_->ensure_envelope_buffers();
-        if (par.if_w2_misfit) cond_->ensure_w2_buffers();
-        if (par.robust_misfit) cond_->ensure_robust_buffers();
+        switch (par.misfit) {
+            case Misfit::L2: case Misfit::Cross: break;
+            case Misfit::Envelope: cond_->ensure_envelope_buffers(); break;
+            case Misfit::W2: cond_->ensure_w2_buffers(); break;
+            case Misfit::Robust: cond_->ensure_robust_buffers(); break;
+        }
         if (par.has_fk) cond_->ensure_fk_buffers();
     }
     h_io_.ensure(dlen);

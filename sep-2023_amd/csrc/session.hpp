@@ -271,7 +271,7 @@ class Session {
         if (!v.empty()) HIP_OK(hipMemcpy(b.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return b;
     }
-    // data conditioning (parameter keys if_win / filter / if_cross_misfit): the hipFFT work space
+    // data conditioning (any live conditioning key, Params::first_live_key): the kernels' scratch and the hipFFT work space
     std::unique_ptr<Conditioner> cond_;
     Stream own_stream_;
     Event ev_order_;

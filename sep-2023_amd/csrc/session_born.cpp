@@ -55,12 +55,13 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     std::lock_guard<std::mutex> lock(mu_);
     const bool want_hv = hv_Lambda != nullptr, have_v = dLambda != nullptr;
     // refusals first: nothing is touched
-    if (want_hv && par_.if_w2_misfit)
-        throw std::invalid_argument("born: the Gauss-Newton product is not defined under if_w2_misfit (the transport misfit has no least-squares form in the data); "
-                                    "the scattered gathers alone are served (hv_* = NULL)");
-    if (want_hv && (par_.if_cross_misfit || par_.if_src_update))
-        throw std::invalid_argument("born: the Gauss-Newton product is not defined for a conditioned misfit with if_cross_misfit or if_src_update (not "
-                                    "quadratic in the data); if_win and filter are served; the scattered gathers alone are served under every key (hv_* = NULL)");
+    const MisfitTraits &kind = traits(par_.misfit);
+    if (want_hv && (!kind.gauss_newton || par_.if_src_update))
+        throw std::invalid_argument(par_.misfit == Misfit::W2
+            ? "born: the Gauss-Newton product is not defined under if_w2_misfit (the transport misfit has no least-squares form in the data); "
+              "the scattered gathers alone are served (hv_* = NULL)"
+            : "born: the Gauss-Newton product is not defined for a conditioned misfit with if_cross_misfit or if_src_update (not "
+              "quadratic in the data); if_win and filter are served; the scattered gathers alone are served under every key (hv_* = NULL)");
     check_shot_ids(group_size, shot_ids);  // (begin_call checks them where run does: after it has touched the statistics)
     Call c = begin_call(ext_stream, group_size, shot_ids);
     c.opt.quiet_skip = 0;
@@ -108,8 +109,7 @@ void Session::born(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, flo
     if (want_hv) comps |= active_comps();
     // envelope misfit: the product linearises the envelope at the BACKGROUND gather, which the samplers record into a buffer of its own
     // robust misfit: the IRLS weight is taken at the background gather too, and at the shot's conditioned OBSERVED gather from the store
-    const bool robust = want_hv && par_.robust_misfit != 0;
-    const bool bg = want_hv && (par_.if_envelope_misfit || robust);
+    const bool robust = want_hv && kind.needs_obs, bg = want_hv && kind.at_background;
     if (bg && !born_bg_) born_bg_ = dev<float>(data_len_);
     if (bg) ensure_data_scratch();
     if (robust) obs_begin(c);

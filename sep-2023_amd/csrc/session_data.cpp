@@ -13,13 +13,13 @@
 //   condition     sepfwi_condition: C or C^T in place
 //   data_misfit   the file's misfit of (obs, syn) and the raw-space adjoint source a = -d misfit / d syn: C^T Z (C obs - C syn) under an L2
 //                 file, the adjoint source of the normalised cross-correlation under if_cross_misfit, C^T D^T Z (e(C obs) - e(C syn)) under
-//                 if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (w2_misfit.hpp), C^T psi under robust_misfit (robust_misfit.hpp).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
+//                 if_envelope_misfit, -1/2 C^T w dW / d(C syn) under if_w2_misfit (w2_misfit.hpp), C^T psi under robust_misfit
+//                 (robust_misfit.hpp).  Under if_src_update the matching filter is computed from the call's own (C obs, C syn), shot by shot,
 //                 as a gradient call computes it; the misfit is that of the updated synthetics and a is taken with the filter held fixed
 //                 (nothing is carried from one shot or call to the next).
 //   data_gn       the Gauss-Newton operator of the misfit in data space at syn: C^T Z C d, or C^T D^T Z D C d under if_envelope_misfit, or
 //                 (sepfwi_data_gn_obs alone: the weight needs the observed data) C^T Z W Z C d under robust_misfit, W the IRLS weight of
-//                 (C obs, C syn) (robust_misfit.hpp).
-//                 Refused under if_cross_misfit, if_src_update and if_w2_misfit (not a least-squares misfit of the data), as the products are.
+//                 (C obs, C syn) (robust_misfit.hpp).  Refused where the products are: a kind without one (kMisfitTraits), if_src_update.
 // A file without a live conditioning key has C = 1 and no conditioner: its misfit runs through the residual kernel of its gradient calls
 // (time-major, lane 0's gather and residual buffers), its operator is Z.  A joint misfit (misfit_w_*) is refused: it is not one of axial
 // strain alone.  The session's observed store, misfit, misfit parts and call statistics are neither read nor written; the callers' inputs
@@ -60,32 +60,34 @@ void Session::condition_gather_t(hipStream_t st, float *gather, int shot_id, int
 void Session::misfit_chain(hipStream_t st, const float *obs_c, float *syn, float *out, int shot_id, int nrec, double *acc) {
     const size_t tot = (size_t)rec_off_.back() + 1, off = (size_t)rec_off_[shot_id];
     const Shot &sh = survey_.shots[shot_id];
+    // the trace weights of the kinds that take them explicitly (Cross; W2: the window's amplitude cancels in the densities).  They belong to
+    // if_win, as the window's do: without the key w_r = 1 (oracle.conditioned_residual)
+    const float *tw = traits(par_.misfit).trace_weights && par_.if_win ? win_ + 2 * tot + off : nullptr;
     condition_gather(st, syn, shot_id, nrec);
     if (par_.if_src_update) cond_->source_update(st, obs_c, syn, nrec, par_.dt);  // libCUFD.cu:383-390
-    if (par_.if_cross_misfit)  // the trace weights belong to if_win, as the window's do: without the key w_r = 1 (oracle.conditioned_residual)
-        cond_->cross_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, acc);
-    else if (par_.if_envelope_misfit)
-        cond_->envelope_residual(st, obs_c, syn, out, nrec, acc);  // rho = Z (e(C obs) - e(C syn)); D^T rho
-    else if (par_.robust_misfit)  // psi of the Huber / Cauchy penalty, the threshold from the conditioned observed trace (robust_misfit.hpp)
-        cond_->robust_residual(st, obs_c, syn, out, nrec, par_.robust_misfit, par_.robust_delta, par_.robust_quantile, acc);
-    else if (par_.if_w2_misfit)  // the trace weights are explicit (the window's amplitude cancels in the densities): the rule of cross_residual
-        cond_->w2_residual(st, obs_c, syn, out, nrec, par_.if_win ? win_ + 2 * tot + off : nullptr, sh.src_weight, par_.dt, par_.w2_beta, acc);
-    else
-        cond_->l2_residual(st, obs_c, syn, out, nrec, acc);
+    switch (par_.misfit) {
+        case Misfit::L2: cond_->l2_residual(st, obs_c, syn, out, nrec, acc); break;
+        case Misfit::Cross: cond_->cross_residual(st, obs_c, syn, out, nrec, tw, sh.src_weight, acc); break;
+        case Misfit::Envelope: cond_->envelope_residual(st, obs_c, syn, out, nrec, acc); break;  // rho = Z (e(C obs) - e(C syn)); D^T rho
+        case Misfit::W2: cond_->w2_residual(st, obs_c, syn, out, nrec, tw, sh.src_weight, par_.dt, par_.w2_beta, acc); break;
+        case Misfit::Robust:  // psi of the Huber / Cauchy penalty, the threshold from the conditioned observed trace (robust_misfit.hpp)
+            cond_->robust_residual(st, obs_c, syn, out, nrec, par_.robust_kind, par_.robust_delta, par_.robust_quantile, acc);
+            break;
+    }
     if (par_.if_src_update) cond_->source_update_adj(st, out, nrec, par_.dt);  // libCUFD.cu:430-433
     condition_gather_t(st, out, shot_id, nrec);
 }
 
 void Session::gn_chain(hipStream_t st, float *d, float *bg, float *out, int shot_id, int nrec, float sign, const float *obs_c) {
     condition_gather(st, d, shot_id, nrec);
-    if (par_.if_envelope_misfit) {
-        condition_gather(st, bg, shot_id, nrec);
-        cond_->envelope_scattered(st, bg, d, out, nrec, sign);
-    } else if (par_.robust_misfit) {  // W = psi / r at the background: the IRLS weight of (C obs, C bg)
-        condition_gather(st, bg, shot_id, nrec);
-        cond_->robust_scattered(st, obs_c, bg, d, out, nrec, par_.robust_misfit, par_.robust_delta, par_.robust_quantile, sign);
-    } else {
-        cond_->scattered_residual(st, d, out, nrec, sign);
+    if (traits(par_.misfit).at_background) condition_gather(st, bg, shot_id, nrec);
+    switch (par_.misfit) {
+        case Misfit::Cross: case Misfit::W2:  // (no Gauss-Newton product: every caller has refused)
+        case Misfit::L2: cond_->scattered_residual(st, d, out, nrec, sign); break;
+        case Misfit::Envelope: cond_->envelope_scattered(st, bg, d, out, nrec, sign); break;
+        case Misfit::Robust:  // W = psi / r at the background: the IRLS weight of (C obs, C bg)
+            cond_->robust_scattered(st, obs_c, bg, d, out, nrec, par_.robust_kind, par_.robust_delta, par_.robust_quantile, sign);
+            break;
     }
     condition_gather_t(st, out, shot_id, nrec);
 }
@@ -112,13 +114,13 @@ void Session::residual_conditioned(const Call &c, const ShotCtx &x) {
 void Session::adjoint_source_conditioned(const Call &c, const ShotCtx &x) {
     if (x.nrec <= 0) return;
     hipStream_t st = c.st;
-    const bool env = par_.if_envelope_misfit || par_.robust_misfit;  // the kinds that linearise at the background gather
+    const bool bg = traits(par_.misfit).at_background;
     const long long before = cond_->launches();
-    if (env) launch_transpose(st, born_bg_.get(), xpose3_.get(), par_.nSteps, x.nrec);
+    if (bg) launch_transpose(st, born_bg_.get(), xpose3_.get(), par_.nSteps, x.nrec);
     launch_transpose(st, syn_of(x, 3), xpose_, par_.nSteps, x.nrec);  // [it][rec] -> [rec][it]
-    gn_chain(st, xpose_, env ? xpose3_.get() : nullptr, xpose2_, x.id, x.nrec, -1.0f, x.d_obs);
+    gn_chain(st, xpose_, bg ? xpose3_.get() : nullptr, xpose2_, x.id, x.nrec, -1.0f, x.d_obs);
     launch_transpose(st, xpose2_, x.res, x.nrec, par_.nSteps);  // [rec][it] -> [it][rec]
-    cs_.launches += (env ? 3 : 2) + (cond_->launches() - before);
+    cs_.launches += (bg ? 3 : 2) + (cond_->launches() - before);
 }
 
 // the third [rec][it] scratch gather and the sum of the data-space entry points (and of the envelope product of Session::born)
@@ -204,17 +206,17 @@ void Session::data_misfit(float *misfit, float *adj, const float *obs, const flo
 void Session::data_gn(float *out, const float *obs, const float *syn, const float *d, int group_size, const int *shot_ids, hipStream_t ext_stream,
                       bool obs_entry) {
     std::lock_guard<std::mutex> lock(mu_);
-    const bool robust = par_.robust_misfit != 0;
+    const MisfitTraits &kind = traits(par_.misfit);
+    const bool robust = kind.needs_obs, env = kind.at_background;  // env: the kinds whose operator depends on syn
     if (robust && !obs_entry)
         throw std::invalid_argument("data_gn: under robust_misfit the operator's weight needs the observed data; call sepfwi_data_gn_obs(out, obs, syn, d, ...)");
     if (robust && !obs && group_size > 0) throw std::invalid_argument("data_gn_obs: obs must not be NULL under robust_misfit (the weight is formed from C obs - C syn)");
-    if (par_.if_cross_misfit || par_.if_src_update || par_.if_w2_misfit)
-        throw std::invalid_argument(std::string("data_gn: not defined under ") + (par_.if_cross_misfit ? "if_cross_misfit" : (par_.if_src_update ? "if_src_update" : "if_w2_misfit")) +
+    if (!kind.gauss_newton || par_.if_src_update)  // (if_src_update stands beside no kind without the product: parse_params, the constructor)
+        throw std::invalid_argument(std::string("data_gn: not defined under ") + (par_.if_src_update ? "if_src_update" : kind.key) +
                                     " (not a least-squares misfit of the data); if_win, filter and if_envelope_misfit are served");
     if (joint_) throw std::invalid_argument("data_gn: not defined for a joint misfit (misfit_w_*): it is a misfit of axial-strain gathers alone");
     check_shot_ids(group_size, shot_ids);
     hipStream_t st = data_stream(ext_stream);
-    const bool env = par_.if_envelope_misfit || robust;  // the kinds whose operator depends on syn
     if (env) ensure_data_scratch();
     float *obs_c = robust ? syn_ : nullptr;  // a fourth [rec][it] gather: lane 0's gather buffers, as data_misfit borrows them under a plain file
     for_each_gather(group_size, shot_ids, [&](int id, int nrec, size_t off, size_t cnt) {

@@ -94,7 +94,7 @@ void Session::adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *
     const float *w[4] = {nullptr, w_vx, w_vz, w_ett};  // by component id
     const bool have_w = w_ett || w_vx || w_vz;
     // refusals first: nothing is touched
-    if (par_.if_cross_misfit || par_.if_src_update)
+    if (!traits(par_.misfit).exact_adjoint || par_.if_src_update)
         throw std::invalid_argument("adjoint_exact: not defined for a conditioned misfit with if_cross_misfit or if_src_update (not quadratic in the "
                                     "data); if_win and filter are served");
     static const char *kName[4] = {"", "vx", "vz", "ett"};

@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
     // 1. the well-formed documents parse to the expected values
     Params p = parse_params(PARA);
     Survey s = parse_survey(SURVEY, p.nPml, p.if_win);
-    if (!p.if_src_update || p.obs_pack_fname != "D/pack.bin" || p.obs_cache_mb != 64 || p.if_cross_misfit || p.nz != 96 || p.nx != 80 || p.fiber != 1 || !p.if_win || !p.has_filter || s.nShots != 2 || s.shots[1].nrec != 2 ||
+    if (!p.if_src_update || p.obs_pack_fname != "D/pack.bin" || p.obs_cache_mb != 64 || p.misfit == Misfit::Cross || p.nz != 96 || p.nx != 80 || p.fiber != 1 || !p.if_win || !p.has_filter || s.nShots != 2 || s.shots[1].nrec != 2 ||
         s.shots[0].x_rec[2] != 3 + p.nPml || p.filter[3] != 2.5f || s.shots[0].win_end[2] != 0.07f || s.shots[0].weights[1] != 0.5f ||
         s.shots[0].src_weight != 1.5f || s.shots[0].sens[3 * 1 + 1] != 0.5f || s.shots[0].sens[3 * 1 + 2] != 0.1f || !s.shots[1].weights.empty()) {
         printf("FAIL: reference documents mis-parsed\n");
@@ -42,7 +42,7 @@ int main(int argc, char **argv) {
         std::string pr(PARA);
         pr.insert(pr.rfind('}'), ", \"conditioning\": \"reference\"");
         Params q = parse_params(pr);
-        if (!q.conditioning_reference || q.if_win || q.has_filter || q.if_src_update || q.if_cross_misfit || !q.if_win_key || q.nz != 96) {
+        if (!q.conditioning_reference || q.if_win || q.has_filter || q.if_src_update || q.misfit == Misfit::Cross || !q.if_win_key || q.nz != 96) {
             printf("FAIL: conditioning = reference mis-parsed\n");
             return 1;
         }

@@ -38,15 +38,15 @@ static int refusal(const std::string &more, const char *key_a, const char *key_b
 
 int main() {
     // the key parsed; absent or false: off
-    if (parse_params(doc("")).if_envelope_misfit) fail("absent key reads as set");
-    if (parse_params(doc(", \"if_envelope_misfit\": false")).if_envelope_misfit) fail("false reads as set");
+    if (parse_params(doc("")).misfit == Misfit::Envelope) fail("absent key reads as set");
+    if (parse_params(doc(", \"if_envelope_misfit\": false")).misfit == Misfit::Envelope) fail("false reads as set");
     {
         const Params p = parse_params(doc(", \"if_envelope_misfit\": true"));
-        if (!p.if_envelope_misfit || p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.joint()) fail("the key alone mis-parsed");
+        if (p.misfit != Misfit::Envelope || p.if_win || p.has_filter || p.misfit == Misfit::Cross || p.if_src_update || p.joint()) fail("the key alone mis-parsed");
     }
     {   // it composes with if_win and filter
         const Params p = parse_params(doc(", \"if_envelope_misfit\": true, \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0]"));
-        if (!p.if_envelope_misfit || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with if_win and filter mis-parsed");
+        if (p.misfit != Misfit::Envelope || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with if_win and filter mis-parsed");
     }
     {   // a value that is no boolean: the reader's own error (not std::invalid_argument)
         bool threw = false;
@@ -55,11 +55,11 @@ int main() {
     }
     {   // reference mode: parsed, then ignored like the other four -- also in the combinations that a live file refuses
         const Params p = parse_params(doc(", \"if_envelope_misfit\": true, \"if_cross_misfit\": true, \"if_win\": true, \"conditioning\": \"reference\""));
-        if (!p.conditioning_reference || p.if_envelope_misfit || p.if_cross_misfit || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
+        if (!p.conditioning_reference || p.misfit == Misfit::Envelope || p.misfit == Misfit::Cross || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
         const Params q = parse_params(doc(", \"if_envelope_misfit\": true, \"misfit_w_vx\": 0.5, \"conditioning\": \"reference\""));
-        if (q.if_envelope_misfit || !q.joint()) fail("reference mode with joint weights mis-parsed");
+        if (q.misfit == Misfit::Envelope || !q.joint()) fail("reference mode with joint weights mis-parsed");
         const Params r = parse_params(doc(", \"if_envelope_misfit\": true, \"conditioning\": \"live\""));
-        if (!r.if_envelope_misfit) fail("conditioning = live drops the key");
+        if (r.misfit != Misfit::Envelope) fail("conditioning = live drops the key");
     }
     // the refused pairs, each naming both keys, as std::invalid_argument
     if (refusal(", \"if_envelope_misfit\": true, \"if_cross_misfit\": true", "if_envelope_misfit", "if_cross_misfit") != 1) fail("if_cross_misfit pair");

@@ -81,14 +81,14 @@ int main() {
         const Params p = parse_params(doc(FK));
         if (!p.has_fk || p.fk_reject || p.fk_slowness[0] != -0.0002 || p.fk_slowness[1] != 0.0001 || p.fk_slowness[2] != 0.0006 || p.fk_slowness[3] != 0.0009)
             fail("fk_slowness alone mis-parsed");
-        if (p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.if_w2_misfit || p.robust_misfit || p.joint()) fail("fk_slowness switches another key on");
+        if (p.if_win || p.has_filter || p.misfit == Misfit::Cross || p.if_src_update || p.misfit == Misfit::Envelope || p.misfit == Misfit::W2 || p.misfit == Misfit::Robust || p.joint()) fail("fk_slowness switches another key on");
     }
     if (!parse_params(doc(std::string(FK) + ", \"fk_mode\": \"reject\"")).fk_reject) fail("fk_mode reject not read");
     if (parse_params(doc(std::string(FK) + ", \"fk_mode\": \"pass\"")).fk_reject) fail("fk_mode pass reads as reject");
     if (!parse_params(doc(", \"fk_slowness\": [0.0001, 0.0003, 0.0003, 0.0007]")).has_fk) fail("p2 == p3 refused");
     {   // it composes with every other live conditioning key
         const Params p = parse_params(doc(std::string(FK) + ", \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0], \"if_envelope_misfit\": true"));
-        if (!p.has_fk || !p.if_win || !p.has_filter || !p.if_envelope_misfit) fail("fk with if_win, filter and if_envelope_misfit mis-parsed");
+        if (!p.has_fk || !p.if_win || !p.has_filter || p.misfit != Misfit::Envelope) fail("fk with if_win, filter and if_envelope_misfit mis-parsed");
         for (const char *k : {", \"if_cross_misfit\": true", ", \"if_src_update\": true", ", \"if_w2_misfit\": true", ", \"robust_misfit\": \"huber\", \"robust_delta\": 1.5"})
             if (refusal(std::string(FK) + k, "", "") != 0) fail("fk with another misfit kind refused");
     }

@@ -41,19 +41,19 @@ int main() {
     // absent: off, and the default of robust_quantile
     {
         const Params p = parse_params(doc(""));
-        if (p.robust_misfit != 0 || p.robust_quantile != 0.9) fail("absent key reads as set, or the default of robust_quantile is not 0.9");
+        if ((p.misfit == Misfit::Robust || p.robust_kind != 0) || p.robust_quantile != 0.9) fail("absent key reads as set, or the default of robust_quantile is not 0.9");
     }
     {
         const Params p = parse_params(doc(H));
-        if (p.robust_misfit != 1 || p.robust_delta != 1.5 || p.robust_quantile != 0.9 || p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update ||
-            p.if_envelope_misfit || p.if_w2_misfit || p.joint())
+        if ((p.misfit != Misfit::Robust || p.robust_kind != 1) || p.robust_delta != 1.5 || p.robust_quantile != 0.9 || p.if_win || p.has_filter || p.misfit == Misfit::Cross || p.if_src_update ||
+            p.misfit == Misfit::Envelope || p.misfit == Misfit::W2 || p.joint())
             fail("huber alone mis-parsed");
         const Params q = parse_params(doc(C));
-        if (q.robust_misfit != 2 || q.robust_delta != 0.25) fail("cauchy alone mis-parsed");
+        if ((q.misfit != Misfit::Robust || q.robust_kind != 2) || q.robust_delta != 0.25) fail("cauchy alone mis-parsed");
     }
     {   // it composes with if_win and filter; the numbers are read as doubles; the closed end of the quantile's range
         const Params p = parse_params(doc(H + ", \"robust_quantile\": 0.75, \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0]"));
-        if (p.robust_misfit != 1 || p.robust_quantile != 0.75 || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with if_win and filter mis-parsed");
+        if ((p.misfit != Misfit::Robust || p.robust_kind != 1) || p.robust_quantile != 0.75 || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with if_win and filter mis-parsed");
         if (parse_params(doc(H + ", \"robust_quantile\": 1")).robust_quantile != 1.0) fail("robust_quantile = 1 refused or mis-read");
         if (parse_params(doc(H + ", \"robust_quantile\": 1e-9")).robust_quantile != 1e-9) fail("a small positive robust_quantile refused or mis-read");
         if (parse_params(doc(", \"robust_misfit\": \"huber\", \"robust_delta\": 1e6")).robust_delta != 1e6) fail("a large robust_delta refused or mis-read");
@@ -81,11 +81,11 @@ int main() {
     if (refusal(", \"robust_quantile\": 0.5", "robust_quantile", "without robust_misfit") != 1) fail("a stray robust_quantile");
     {   // reference mode: parsed and validated, then ignored like the other keys -- also in the combinations that a live file refuses
         const Params p = parse_params(doc(H + ", \"if_cross_misfit\": true, \"if_win\": true, \"conditioning\": \"reference\""));
-        if (!p.conditioning_reference || p.robust_misfit != 0 || p.if_cross_misfit || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
+        if (!p.conditioning_reference || (p.misfit == Misfit::Robust || p.robust_kind != 0) || p.misfit == Misfit::Cross || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
         const Params q = parse_params(doc(H + ", \"misfit_w_vx\": 0.5, \"conditioning\": \"reference\""));
-        if (q.robust_misfit != 0 || !q.joint()) fail("reference mode with joint weights mis-parsed");
+        if ((q.misfit == Misfit::Robust || q.robust_kind != 0) || !q.joint()) fail("reference mode with joint weights mis-parsed");
         const Params r = parse_params(doc(C + ", \"conditioning\": \"live\""));
-        if (r.robust_misfit != 2) fail("conditioning = live drops the key");
+        if (r.misfit != Misfit::Robust || r.robust_kind != 2) fail("conditioning = live drops the key");
         if (refusal(", \"robust_misfit\": \"huber\", \"conditioning\": \"reference\"", "robust_misfit", "robust_delta") != 1) fail("reference mode does not validate the key");
     }
     // the refused pairs, each naming both keys, as std::invalid_argument

@@ -38,17 +38,17 @@ static int refusal(const std::string &more, const char *key_a, const char *key_b
 int main() {
     const std::string K = ", \"if_w2_misfit\": true";
     // the flag parsed; absent or false: off; the default of w2_beta
-    if (parse_params(doc("")).if_w2_misfit) fail("absent key reads as set");
-    if (parse_params(doc(", \"if_w2_misfit\": false")).if_w2_misfit) fail("false reads as set");
+    if (parse_params(doc("")).misfit == Misfit::W2) fail("absent key reads as set");
+    if (parse_params(doc(", \"if_w2_misfit\": false")).misfit == Misfit::W2) fail("false reads as set");
     if (parse_params(doc("")).w2_beta != 3.0) fail("the default of w2_beta is not 3");
     {
         const Params p = parse_params(doc(K));
-        if (!p.if_w2_misfit || p.w2_beta != 3.0 || p.if_win || p.has_filter || p.if_cross_misfit || p.if_src_update || p.if_envelope_misfit || p.joint())
+        if (p.misfit != Misfit::W2 || p.w2_beta != 3.0 || p.if_win || p.has_filter || p.misfit == Misfit::Cross || p.if_src_update || p.misfit == Misfit::Envelope || p.joint())
             fail("the key alone mis-parsed");
     }
     {   // it composes with if_win and filter; w2_beta is read as a double
         const Params p = parse_params(doc(K + ", \"w2_beta\": 5.5, \"if_win\": true, \"filter\": [1.0, 2.0, 8.0, 10.0]"));
-        if (!p.if_w2_misfit || p.w2_beta != 5.5 || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with w2_beta, if_win and filter mis-parsed");
+        if (p.misfit != Misfit::W2 || p.w2_beta != 5.5 || !p.if_win || !p.has_filter || p.filter[2] != 8.0f) fail("the key with w2_beta, if_win and filter mis-parsed");
         if (parse_params(doc(K + ", \"w2_beta\": 16")).w2_beta != 16.0) fail("w2_beta = 16 (the closed end of the range) refused or mis-read");
         if (parse_params(doc(K + ", \"w2_beta\": 1e-3")).w2_beta != 1e-3) fail("a small positive w2_beta refused or mis-read");
     }
@@ -66,11 +66,11 @@ int main() {
         if (refusal(K + ", \"w2_beta\": " + bad, "", "") != 3) fail("w2_beta = NaN accepted, or not the reader's error");
     {   // reference mode: parsed, then ignored like the other keys -- also in the combinations that a live file refuses
         const Params p = parse_params(doc(K + ", \"if_cross_misfit\": true, \"if_win\": true, \"conditioning\": \"reference\""));
-        if (!p.conditioning_reference || p.if_w2_misfit || p.if_cross_misfit || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
+        if (!p.conditioning_reference || p.misfit == Misfit::W2 || p.misfit == Misfit::Cross || p.if_win || !p.if_win_key) fail("reference mode does not ignore the key");
         const Params q = parse_params(doc(K + ", \"misfit_w_vx\": 0.5, \"conditioning\": \"reference\""));
-        if (q.if_w2_misfit || !q.joint()) fail("reference mode with joint weights mis-parsed");
+        if (q.misfit == Misfit::W2 || !q.joint()) fail("reference mode with joint weights mis-parsed");
         const Params r = parse_params(doc(K + ", \"conditioning\": \"live\""));
-        if (!r.if_w2_misfit) fail("conditioning = live drops the key");
+        if (r.misfit != Misfit::W2) fail("conditioning = live drops the key");
     }
     // the refused pairs, each naming both keys, as std::invalid_argument
     if (refusal(K + ", \"if_cross_misfit\": true", "if_w2_misfit", "if_cross_misfit") != 1) fail("if_cross_misfit pair");
