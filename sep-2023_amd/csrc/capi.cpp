@@ -46,6 +46,19 @@ static int guarded(Fn &&fn) {
     }
 }
 
+// The argument checks the entry points share: a parameter file and a sane shot list (where another refusal comes between the two: called
+// without the list, then with it, so that the refusals keep their order).
+static void check_args(const char *para_fname, int group_size = 0, const int *shot_ids = nullptr) {
+    if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+    if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+}
+
+// The session of a status query: the one an earlier call made.
+static std::shared_ptr<Session> existing_session(const char *para_fname, int gpu_id) {
+    if (std::shared_ptr<Session> s = find_session(para_fname, gpu_id)) return s;
+    throw std::invalid_argument("no session for this parameter file / gpu");
+}
+
 extern "C" {
 
 const char *sepfwi_last_error(void) { return t_last_error.c_str(); }
@@ -65,9 +78,9 @@ int sepfwi_cufd_stream(float *misfit, float *grad_Lambda, float *grad_Mu, float 
                        int async) {
     return guarded([&] {
         if (calc_id < 0 || calc_id > 3) throw std::invalid_argument("Invalid calc_id " + std::to_string(calc_id));  // libCUFD.cu:43-46
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         if (calc_id == 1 && (!grad_Lambda || !grad_Mu || !grad_Den)) throw std::invalid_argument("gradient outputs must not be NULL for calc_id 1");
         std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
         s->run(misfit, grad_Lambda, grad_Mu, grad_Den, grad_stf, Lambda, Mu, Den, stf, calc_id, group_size, shot_ids,
@@ -89,14 +102,14 @@ void sepfwi_release_all(void) {
 
 int sepfwi_set_observed(const char *para_fname, int gpu_id, int shot_id, const float *ett, int nrec, int nSteps) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         get_session(para_fname, gpu_id)->set_observed(shot_id, ett, nrec, nSteps);
     });
 }
 
 int sepfwi_set_observed_component(const char *para_fname, int gpu_id, int shot_id, int comp, const float *data, int nrec, int nSteps) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         if (comp < 1 || comp > 3) throw std::invalid_argument("set_observed_component: comp must be 1 (vx), 2 (vz) or 3 (ett), got " + std::to_string(comp));
         get_session(para_fname, gpu_id)->set_observed(shot_id, data, nrec, nSteps, comp);
     });
@@ -105,16 +118,14 @@ int sepfwi_set_observed_component(const char *para_fname, int gpu_id, int shot_i
 int sepfwi_get_misfit_parts(const char *para_fname, int gpu_id, double parts[3]) {
     return guarded([&] {
         if (!para_fname || !parts) throw std::invalid_argument("bad arguments");
-        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
-        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
-        s->misfit_parts(parts);
+        existing_session(para_fname, gpu_id)->misfit_parts(parts);
     });
 }
 
 int sepfwi_pseudo_hessian_arm(const char *para_fname, int gpu_id, int every) {
     return guarded([&] {
         if (every < 0) throw std::invalid_argument("pseudo_hessian_arm: every must be >= 0, got " + std::to_string(every));
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         if (every == 0) {  // disarm: nothing to do without a session
             if (std::shared_ptr<Session> s = find_session(para_fname, gpu_id)) s->pseudo_hessian_arm(0);
             return;
@@ -125,10 +136,8 @@ int sepfwi_pseudo_hessian_arm(const char *para_fname, int gpu_id, int every) {
 
 int sepfwi_get_pseudo_hessian(const char *para_fname, int gpu_id, float *hLambda, float *hMu, float *hDen) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
-        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
-        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
-        s->pseudo_hessian_get(hLambda, hMu, hDen);
+        check_args(para_fname);
+        existing_session(para_fname, gpu_id)->pseudo_hessian_get(hLambda, hMu, hDen);
     });
 }
 
@@ -136,12 +145,12 @@ int sepfwi_born_src(float *d_ett, float *d_vx, float *d_vz, float *hv_Lambda, fl
                     const float *Den, const float *dLambda, const float *dMu, const float *dDen, const float *stf, int gpu_id, int group_size,
                     const int *shot_ids, const char *para_fname, void *hip_stream, const float *dStf) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
         const int n_v = (dLambda ? 1 : 0) + (dMu ? 1 : 0) + (dDen ? 1 : 0);
         if (!dStf && n_v != 3) throw std::invalid_argument("born: dLambda, dMu and dDen must not be NULL");
         if (dStf && n_v != 0 && n_v != 3) throw std::invalid_argument("born: with dStf, dLambda, dMu, dDen must be all NULL or all set");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         const int n_hv = (hv_Lambda ? 1 : 0) + (hv_Mu ? 1 : 0) + (hv_Den ? 1 : 0);
         if (n_hv != 0 && n_hv != 3) throw std::invalid_argument("born: hv_Lambda, hv_Mu, hv_Den must be all NULL (J v only) or all set");
         if (dStf && n_hv == 3)
@@ -165,7 +174,7 @@ int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float 
                              const float *stf, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream,
                              const float *dStf, float *g_stf) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
+        check_args(para_fname);
         if (!Lambda || !Mu || !Den || !stf) throw std::invalid_argument("Lambda, Mu, Den and stf must not be NULL");
         if (!g_Lambda || !g_Mu || !g_Den) throw std::invalid_argument("adjoint_exact: g_Lambda, g_Mu and g_Den must not be NULL");
         const int n_v = (dLambda ? 1 : 0) + (dMu ? 1 : 0) + (dDen ? 1 : 0);
@@ -173,7 +182,7 @@ int sepfwi_adjoint_exact_src(float *misfit, float *g_Lambda, float *g_Mu, float 
         const bool have_w = w_ett || w_vx || w_vz;
         if (n_v == 3 && have_w) throw std::invalid_argument("adjoint_exact: either v (the product) or w (J^T w), not both");
         if (dStf && have_w) throw std::invalid_argument("adjoint_exact: either dStf (the product) or w (J^T w), not both");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         std::shared_ptr<Session> s = get_session(para_fname, gpu_id);
         if (n_v == 3 || dStf)
             s->born(nullptr, nullptr, nullptr, g_Lambda, g_Mu, g_Den, Lambda, Mu, Den, dLambda, dMu, dDen, stf, group_size, shot_ids,
@@ -192,8 +201,7 @@ int sepfwi_adjoint_exact(float *misfit, float *g_Lambda, float *g_Mu, float *g_D
 
 int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, const int *shot_ids, const char *para_fname, void *hip_stream) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         if (group_size > 0 && !data) throw std::invalid_argument("condition: data must not be NULL");
         get_session(para_fname, gpu_id)->condition(data, transpose != 0, group_size, shot_ids, (hipStream_t)hip_stream);
     });
@@ -202,8 +210,7 @@ int sepfwi_condition(float *data, int transpose, int gpu_id, int group_size, con
 int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float *syn, int gpu_id, int group_size, const int *shot_ids,
                        const char *para_fname, void *hip_stream) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         if (!misfit) throw std::invalid_argument("data_misfit: misfit must not be NULL");
         if (group_size > 0 && (!obs || !syn)) throw std::invalid_argument("data_misfit: obs and syn must not be NULL");
         get_session(para_fname, gpu_id)->data_misfit(misfit, adj, obs, syn, group_size, shot_ids, (hipStream_t)hip_stream);
@@ -213,8 +220,7 @@ int sepfwi_data_misfit(float *misfit, float *adj, const float *obs, const float 
 int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids, const char *para_fname,
                    void *hip_stream) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         if (group_size > 0 && (!out || !syn || !d)) throw std::invalid_argument("data_gn: out, syn and d must not be NULL");
         get_session(para_fname, gpu_id)->data_gn(out, nullptr, syn, d, group_size, shot_ids, (hipStream_t)hip_stream, false);
     });
@@ -223,8 +229,7 @@ int sepfwi_data_gn(float *out, const float *syn, const float *d, int gpu_id, int
 int sepfwi_data_gn_obs(float *out, const float *obs, const float *syn, const float *d, int gpu_id, int group_size, const int *shot_ids,
                        const char *para_fname, void *hip_stream) {
     return guarded([&] {
-        if (!para_fname) throw std::invalid_argument("para_fname is NULL");
-        if (group_size < 0 || (group_size > 0 && !shot_ids)) throw std::invalid_argument("bad shot list");
+        check_args(para_fname, group_size, shot_ids);
         if (group_size > 0 && (!out || !syn || !d)) throw std::invalid_argument("data_gn_obs: out, syn and d must not be NULL");
         get_session(para_fname, gpu_id)->data_gn(out, obs, syn, d, group_size, shot_ids, (hipStream_t)hip_stream, true);  // (obs: checked under the key)
     });
@@ -260,18 +265,14 @@ int sepfwi_shot_split(int group_size, int ngpu, int *starts) {
 int sepfwi_get_stats(const char *para_fname, int gpu_id, sepfwi_stats *out) {
     return guarded([&] {
         if (!para_fname || !out) throw std::invalid_argument("bad arguments");
-        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
-        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
-        s->stats(out);
+        existing_session(para_fname, gpu_id)->stats(out);
     });
 }
 
 int sepfwi_loop_status(const char *para_fname, int gpu_id, char *why, int len) {
     return guarded([&] {
         if (!para_fname || !why || len < 1) throw std::invalid_argument("bad arguments");
-        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
-        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
-        const std::string w = s->loop_status();
+        const std::string w = existing_session(para_fname, gpu_id)->loop_status();
         std::snprintf(why, (size_t)len, "%s", w.c_str());
     });
 }
@@ -279,9 +280,7 @@ int sepfwi_loop_status(const char *para_fname, int gpu_id, char *why, int len) {
 int sepfwi_debug_field(const char *para_fname, int gpu_id, int lane, int which, float *out) {
     return guarded([&] {
         if (!para_fname || !out) throw std::invalid_argument("bad arguments");
-        std::shared_ptr<Session> s = find_session(para_fname, gpu_id);
-        if (!s) throw std::invalid_argument("no session for this parameter file / gpu");
-        s->copy_field(lane, which, out);
+        existing_session(para_fname, gpu_id)->copy_field(lane, which, out);
     });
 }
 

@@ -23,8 +23,7 @@ FAULT_LIB_PATH = os.path.join(_ROOT, "libsepfwi_fault.so")
 VARIANTS = {"default": (LIB_PATH, []), "probes": (PROBES_LIB_PATH, ["-DSEPFWI_PROBES"]), "fault": (FAULT_LIB_PATH, ["-DSEPFWI_PK_FAULT=17"])}
 PUBLIC_OPTIONS = ("bwd_fuse", "batch", "img_every", "quiet_skip", "obs_cache_mb", "probe")
 SOURCES = ["kernels.hip", "schedule.cpp", "model_call.cpp", "param_maps.hip", "regularizer.hip", "smoother.hip", "conditioning.hip", "w2_misfit.hip", "robust_misfit.hip", "session.cpp", "session_run.cpp", "session_data.cpp", "session_persist.cpp", "session_batched.cpp", "obs_store.cpp", "host_checks.cpp", "persist_plan.cpp", "inject_plan.cpp", "das_gauge.hip", "das_gauge.cpp", "geophone.hip", "geophone.cpp", "pseudo_hessian.hip", "born.hip", "session_born.cpp", "exact_adjoint.hip", "session_exact.cpp", "config.cpp", "capi.cpp"]
-HEADERS = ["kernels.hpp", "kernels_device.hpp", "kernels_bodies.hpp", "kernels_quiet.hpp", "kernels_step.hpp", "kernels_persist.hpp", "kernels_aux.hpp", "model_call.hpp", "param_maps.hpp", "regularizer.hpp", "smoother.hpp", "conditioning.hpp", "w2_misfit.hpp", "robust_misfit.hpp", "device_common.hpp", "device_alloc.hpp", "obs_store.hpp", "host_checks.hpp", "persist_plan.hpp", "inject_plan.hpp", "schedule.hpp", "das_gauge.hpp", "geophone.hpp", "pseudo_hessian.hpp", "born.hpp", "exact_adjoint.hpp", "errors.hpp", "hip_check.hpp", "session.hpp", "config.hpp", "fwi_types.hpp", "json_min.hpp",
-           os.path.join("..", "..", "include", "sepfwi.h")]
+HEADER = os.path.join(os.path.dirname(_ROOT), "include", "sepfwi.h")
 
 _libs = {}
 _active = os.environ.get("SEPFWI_LIB_VARIANT", "default")
@@ -39,12 +38,47 @@ class Stats(C.Structure):
                 ("obs_device_bytes", C.c_longlong), ("obs_host_bytes", C.c_longlong), ("obs_evictions", C.c_longlong), ("persist_steps", C.c_longlong), ("quiet_active", C.c_longlong), ("quiet_total", C.c_longlong)]
 
 
+_I, _F, _P, _S = C.c_int, C.c_float, C.c_void_p, C.c_char_p
+_SESSION = [_S, _I]                        # para_fname, gpu_id
+_SHOTS = [_I, _I, _P, _S, _P]              # gpu_id, group_size, shot_ids, para_fname, hip_stream
+_CUFD = [_P] * 9 + [_I, _I, _I, _P, _S]    # 5 outputs, 4 inputs, calc_id, gpu_id, group_size, shot_ids, para_fname
+_PARAM = [_I] * 5 + [_P] * 13 + [_P]       # kind and sizes, 7 fields, 3 inputs, 3 outputs, hip_stream
+_REG = [_I, _I, _F, _F] + [_P] * 7 + [_F, _P, _P, _P]
+# Every function of include/sepfwi.h: name -> (restype, argtypes).  lib() declares them from here and tests/test_host_logic.py holds
+# the table against the header's declarations, so a new entry point is one entry here (a line holds the functions that belong together).
+API = {
+    "sepfwi_last_error": (_S, []),
+    "sepfwi_version": (_I, []), "sepfwi_device_count": (_I, []),
+    "sepfwi_cufd": (_I, _CUFD), "sepfwi_cufd_stream": (_I, _CUFD + [_P, _I]),
+    "sepfwi_release_all": (None, []), "sepfwi_invalidate_observed": (None, []),
+    "sepfwi_cpml_profiles": (_I, [_P] * 6 + [_I, _I, _F, _F, _F]),
+    "sepfwi_stf_taper": (_I, [_P, _I, _F, _F]), "sepfwi_shot_split": (_I, [_I, _I, _P]),
+    "sepfwi_get_stats": (_I, _SESSION + [C.POINTER(Stats)]), "sepfwi_loop_status": (_I, _SESSION + [_S, _I]),
+    "sepfwi_set_option": (_I, [_S, _I]), "sepfwi_get_option": (_I, [_S]),
+    "sepfwi_debug_field": (_I, _SESSION + [_I, _I, _P]), "sepfwi_debug_live_bytes": (_I, [C.POINTER(C.c_longlong)] * 2),
+    "sepfwi_set_observed": (_I, _SESSION + [_I, _P, _I, _I]), "sepfwi_set_observed_component": (_I, _SESSION + [_I, _I, _P, _I, _I]),
+    "sepfwi_get_misfit_parts": (_I, _SESSION + [C.POINTER(C.c_double)]),
+    "sepfwi_pseudo_hessian_arm": (_I, _SESSION + [_I]), "sepfwi_get_pseudo_hessian": (_I, _SESSION + [_P] * 3),
+    "sepfwi_born": (_I, [_P] * 13 + _SHOTS), "sepfwi_born_src": (_I, [_P] * 13 + _SHOTS + [_P]),
+    "sepfwi_adjoint_exact": (_I, [_P] * 14 + _SHOTS), "sepfwi_adjoint_exact_src": (_I, [_P] * 14 + _SHOTS + [_P, _P]),
+    "sepfwi_condition": (_I, [_P, _I] + _SHOTS),
+    "sepfwi_data_misfit": (_I, [_P] * 4 + _SHOTS),
+    "sepfwi_data_gn": (_I, [_P] * 3 + _SHOTS), "sepfwi_data_gn_obs": (_I, [_P] * 4 + _SHOTS),
+    "sepfwi_param_forward": (_I, [_I] * 5 + [_P] * 10 + [_P]),
+    "sepfwi_param_backward": (_I, _PARAM), "sepfwi_param_jvp": (_I, _PARAM), "sepfwi_param_diag": (_I, _PARAM),
+    "sepfwi_regularizer": (_I, _REG), "sepfwi_regularizer_hvp": (_I, _REG),
+    "sepfwi_smooth_plan": (_I, [_I] * 4 + [_P] * 4 + [_P]), "sepfwi_smooth_apply": (_I, [_I] * 4 + [_P] * 4 + [_I, _P, _P, _P]),
+}
+EXPORTS = list(API)
+
+
 def needs_build(variant: str = "default") -> bool:
     path = VARIANTS[variant][0]
     if not os.path.exists(path):
         return True
     t = os.path.getmtime(path)
-    return any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in SOURCES + HEADERS)
+    # every file of csrc/ is a translation unit of the library or one of its headers: the directory is the list
+    return any(os.path.getmtime(f) > t for f in [os.path.join(CSRC, n) for n in os.listdir(CSRC)] + [HEADER])
 
 
 def build(force: bool = False, verbose: bool = False, variant: str = "all") -> str:
@@ -87,61 +121,26 @@ def lib():
             "%s is not built (%s missing). Run `python -c 'import __graft_entry__ as g; g.build()'`; "
             "there is no CPU fallback for the propagator." % (os.path.basename(path), path))
     L = C.CDLL(path)
-    fp, ip = C.c_void_p, C.c_void_p
-    L.sepfwi_last_error.restype = C.c_char_p
-    L.sepfwi_cufd.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, ip, C.c_char_p]
-    L.sepfwi_cufd_stream.argtypes = L.sepfwi_cufd.argtypes + [C.c_void_p, C.c_int]
-    L.sepfwi_cpml_profiles.argtypes = [fp] * 6 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
-    L.sepfwi_stf_taper.argtypes = [fp, C.c_int, C.c_float, C.c_float]
-    L.sepfwi_shot_split.argtypes = [C.c_int, C.c_int, ip]
-    L.sepfwi_get_stats.argtypes = [C.c_char_p, C.c_int, C.POINTER(Stats)]
-    L.sepfwi_set_option.argtypes = [C.c_char_p, C.c_int]
-    L.sepfwi_get_option.argtypes = [C.c_char_p]
-    L.sepfwi_param_forward.argtypes = [C.c_int] * 5 + [fp] * 10 + [C.c_void_p]
-    L.sepfwi_param_backward.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
-    L.sepfwi_param_jvp.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
-    L.sepfwi_param_diag.argtypes = [C.c_int] * 5 + [fp] * 13 + [C.c_void_p]
-    L.sepfwi_regularizer.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float] + [fp] * 7 + [C.c_float, fp, fp, C.c_void_p]
-    L.sepfwi_regularizer_hvp.argtypes = L.sepfwi_regularizer.argtypes
-    L.sepfwi_smooth_plan.argtypes = [C.c_int] * 4 + [fp] * 4 + [C.c_void_p]
-    L.sepfwi_smooth_apply.argtypes = [C.c_int] * 4 + [fp] * 4 + [C.c_int, fp, fp, C.c_void_p]
-    L.sepfwi_debug_field.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, fp]
-    L.sepfwi_debug_live_bytes.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-    L.sepfwi_loop_status.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int]
-    L.sepfwi_set_observed.argtypes = [C.c_char_p, C.c_int, C.c_int, fp, C.c_int, C.c_int]
-    L.sepfwi_set_observed_component.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int]
-    L.sepfwi_get_misfit_parts.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
-    L.sepfwi_pseudo_hessian_arm.argtypes = [C.c_char_p, C.c_int, C.c_int]
-    L.sepfwi_get_pseudo_hessian.argtypes = [C.c_char_p, C.c_int, fp, fp, fp]
-    L.sepfwi_born.argtypes = [fp] * 13 + [C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    L.sepfwi_adjoint_exact.argtypes = [fp] * 14 + [C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    L.sepfwi_born_src.argtypes = L.sepfwi_born.argtypes + [fp]
-    L.sepfwi_adjoint_exact_src.argtypes = L.sepfwi_adjoint_exact.argtypes + [fp, fp]
-    L.sepfwi_condition.argtypes = [fp, C.c_int, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    L.sepfwi_data_misfit.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    L.sepfwi_data_gn.argtypes = [fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    L.sepfwi_data_gn_obs.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, ip, C.c_char_p, C.c_void_p]
-    for f in ("sepfwi_cufd", "sepfwi_cufd_stream", "sepfwi_cpml_profiles", "sepfwi_stf_taper", "sepfwi_shot_split",
-              "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes", "sepfwi_set_observed",
-              "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact", "sepfwi_born_src",
-              "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_data_gn_obs", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply", "sepfwi_version", "sepfwi_device_count"):
-        getattr(L, f).restype = C.c_int
-    L.sepfwi_release_all.restype = None
-    L.sepfwi_invalidate_observed.restype = None
+    for name, (restype, argtypes) in API.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _libs[_active] = L
     return L
-
-
-EXPORTS = ["sepfwi_last_error", "sepfwi_version", "sepfwi_device_count", "sepfwi_cufd", "sepfwi_cufd_stream",
-           "sepfwi_release_all", "sepfwi_invalidate_observed", "sepfwi_cpml_profiles", "sepfwi_stf_taper",
-           "sepfwi_shot_split", "sepfwi_get_stats", "sepfwi_loop_status", "sepfwi_set_option", "sepfwi_get_option", "sepfwi_debug_field", "sepfwi_debug_live_bytes",
-           "sepfwi_set_observed", "sepfwi_set_observed_component", "sepfwi_get_misfit_parts", "sepfwi_pseudo_hessian_arm", "sepfwi_get_pseudo_hessian", "sepfwi_born", "sepfwi_adjoint_exact",
-           "sepfwi_born_src", "sepfwi_adjoint_exact_src", "sepfwi_condition", "sepfwi_data_misfit", "sepfwi_data_gn", "sepfwi_data_gn_obs", "sepfwi_param_forward", "sepfwi_param_backward", "sepfwi_param_jvp", "sepfwi_param_diag", "sepfwi_regularizer", "sepfwi_regularizer_hvp", "sepfwi_smooth_plan", "sepfwi_smooth_apply"]
 
 
 def ptr(t):
     """a tensor's data pointer as a C argument; None stays None (NULL)"""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def path_arg(fname):
+    """a parameter-file path as a C argument"""
+    return str(fname).encode()
+
+
+def ids_arg(ids):
+    """a contiguous int32 numpy array of shot ids as a C argument (the array must outlive the call)"""
+    return C.c_void_p(ids.ctypes.data)
 
 
 def triple(ts):

@@ -21,6 +21,7 @@ import torch
 
 from . import _native
 from . import dist as _dist
+from . import utils as _utils
 
 
 def split_shots(group_size: int, ngpu: int):
@@ -39,8 +40,6 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.detach().contiguous()
 
 
-_DIMS_CACHE = {}
-
 # An armed call is arm -> run -> collect -> disarm on ONE session: threads that share a session (single-process ngpu > 1 with the
 # device pinned) take turns, or one would collect the other's result.
 _PH_LOCKS = {}
@@ -53,24 +52,19 @@ def _ph_lock(para_fname, gpu_id):
 
 
 def _para_dims(para_fname):
-    """(nz, nx, nSteps) of the one-line parameter JSON (fwi_utils.py:46-83), cached by mtime.  The reference passes raw
+    """(nz, nx, nSteps) of the one-line parameter JSON (fwi_utils.py:46-83), cached (utils.read_para).  The reference passes raw
     data_ptr<float>()s with no size anywhere (Src/Torch_Fwi.cpp:55-58); here a tensor of the wrong shape is an error
     before the library reads or writes past it."""
-    import json
-    import os
     try:
-        key = (str(para_fname), os.stat(para_fname).st_mtime_ns)
-    except OSError:
-        return None          # the library reports the missing file (SEPFWI_EIO)
-    if key not in _DIMS_CACHE:
-        try:
-            with open(para_fname) as fp:
-                j = json.loads(fp.readline())
-            _DIMS_CACHE.clear()
-            _DIMS_CACHE[key] = (int(j["nz"]), int(j["nx"]), int(j["nSteps"]))
-        except (ValueError, KeyError, TypeError):
-            return None      # the library reports the malformed file (SEPFWI_EJSON)
-    return _DIMS_CACHE[key]
+        p = _utils.read_para(para_fname)
+        return int(p["nz"]), int(p["nx"]), int(p["nSteps"])
+    except (OSError, ValueError, KeyError, TypeError):
+        return None          # the library reports the missing (SEPFWI_EIO) or malformed (SEPFWI_EJSON) file
+
+
+def _shot_ids(shot_ids):
+    """Shot_ids as the library reads them: a tensor on any device, a list or an array -> a contiguous 1-D int32 numpy array"""
+    return np.ascontiguousarray(np.asarray(shot_ids.cpu() if torch.is_tensor(shot_ids) else shot_ids, dtype=np.int32)).reshape(-1)
 
 
 def _checked(Lambda, Mu, Den, Stf, shot_ids, para_fname, what, v=(), need_dims=True):
@@ -85,7 +79,7 @@ def _checked(Lambda, Mu, Den, Stf, shot_ids, para_fname, what, v=(), need_dims=T
         raise ValueError(names + " must be 2-D tensors of one shape (nz_pad, nx_pad)")
     if any(t.device != Lambda.device for t in [Mu, Den] + v):
         raise ValueError(names + " must live on one device")
-    ids = np.ascontiguousarray(np.asarray(shot_ids.cpu() if torch.is_tensor(shot_ids) else shot_ids, dtype=np.int32)).reshape(-1)
+    ids = _shot_ids(shot_ids)
     dims = _para_dims(para_fname)
     if dims is None:
         if need_dims:
@@ -107,34 +101,33 @@ def _gdev(Lambda, gpu_id):
     return torch.device("cuda", gpu_id) if Lambda.is_cuda else torch.device("cpu")
 
 
+def _stream_for(t, dev):
+    """The stream argument of a call that reads or writes t on the session of HIP device dev: torch's current stream when t lives
+    there; else None (the legacy default stream: the library orders itself behind it), after t's own GPU, if any, has finished."""
+    if t.is_cuda and t.device.index == dev:
+        return _native.stream_arg(t.device)
+    if t.is_cuda:
+        torch.cuda.synchronize(t.device)   # produced on another GPU: finished before it is staged
+    return None
+
+
 def _stream_or_sync(Lambda, Stf, gpu_id, sync_current=False):
-    """The stream argument of a call, after everything it reads has been queued: torch's current stream when the model lives on the
-    session's GPU, else NULL (the legacy default stream: the library orders itself behind it) after the model's device has finished."""
-    stream = None
-    if Lambda.is_cuda and Lambda.device.index == gpu_id:
-        stream = _native.stream_arg(Lambda.device)
-        if sync_current:
-            torch.cuda.current_stream(Lambda.device).synchronize()
-    elif Lambda.is_cuda:
-        torch.cuda.synchronize(Lambda.device)   # the model was produced on another GPU: finished before it is staged
+    """The stream argument of a call (_stream_for the model), after everything it reads has been queued."""
+    if sync_current and Lambda.is_cuda:         # (on another GPU than the session's, _stream_for waits for the whole device anyway)
+        torch.cuda.current_stream(Lambda.device).synchronize()
+    stream = _stream_for(Lambda, gpu_id)
     if Stf.is_cuda:
         torch.cuda.synchronize(Stf.device)      # read with a blocking copy inside the library
     return stream
 
 
 def _nrec_per_shot(para_fname, ids):
-    """Channels of every shot of ids, from the survey file the parameter file names."""
-    import json
-    with open(para_fname) as fp:
-        survey_fname = json.loads(fp.readline())["survey_fname"]
-    with open(survey_fname) as fp:
-        survey = json.loads(fp.readline())
-    nrec = []
+    """Channels of every shot of ids, from the survey file the parameter file names (cached: utils.read_survey_channels)."""
+    channels = _utils.read_survey_channels(para_fname)
     for i in ids:
-        if "shot%d" % int(i) not in survey:
+        if "shot%d" % int(i) not in channels:
             raise ValueError("shot id %d is not in the survey file" % int(i))
-        nrec.append(len(survey["shot%d" % int(i)]["z_rec"]))
-    return nrec
+    return [channels["shot%d" % int(i)] for i in ids]
 
 
 def _local_rows(dStf, Stf, ids, gdev):
@@ -186,14 +179,14 @@ class _FwiOps:
             misfit = fused[3 * n:3 * n + 1]
             gS = torch.zeros((int(ids.size), Stf.shape[1]), dtype=torch.float32)
         stream = _stream_or_sync(Lambda, Stf, gpu_id)
-        fn = str(para_fname).encode()
+        fn = _native.path_arg(para_fname)
         H = None
         with (_ph_lock(para_fname, gpu_id) if k > 0 else contextlib.nullcontext()):
             if k > 0:
                 _native.check(L.sepfwi_pseudo_hessian_arm(fn, gpu_id, k))
             try:
                 rc = L.sepfwi_cufd_stream(_native.ptr(misfit), _native.ptr(gL), _native.ptr(gM), _native.ptr(gD), _native.ptr(gS), _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den),
-                                          _native.ptr(Stf), int(calc_id), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), fn, stream, 0)
+                                          _native.ptr(Stf), int(calc_id), gpu_id, int(ids.size), _native.ids_arg(ids), fn, stream, 0)
                 _native.check(rc)
                 if k > 0:   # ONE buffer [hLambda | hMu | hDen], the unit of the all-reduce under torch.distributed
                     H = torch.empty((3,) + tuple(Lambda.shape), dtype=torch.float32, device=gdev)
@@ -223,6 +216,27 @@ class _FwiOps:
             return _dist.local_device_index()
         return i
 
+    def _session_dev(self, gpu_id) -> int:
+        """HIP device of the session an entry point with a `gpu_id` argument addresses: the pinned one, else gpu_id.  (stats and
+        loop_status read gpu_id literally: bench.py passes them the device itself.)"""
+        return int(gpu_id) if self.device_override is None else int(self.device_override)
+
+    def _split_cufd(self, calc_id, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, **kw):
+        """_cufd over the shot split -> the list of its results: this rank's block under torch.distributed, one call for ngpu == 1,
+        else one block and one host thread per GPU, every block's results on the model's device."""
+        ids = _shot_ids(Shot_ids)
+        if _dist.active():
+            lo, hi = _dist.my_block(int(ids.size))
+            return [self._cufd(calc_id, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids[lo:hi], para_fname, **kw)]
+        ngpu = int(ngpu)
+        bars = split_shots(int(ids.size), ngpu)
+        if ngpu == 1:
+            return [self._cufd(calc_id, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids, para_fname, **kw)]
+        with ThreadPoolExecutor(max_workers=ngpu) as ex:   # one host thread per GPU, ctypes drops the GIL
+            futs = [ex.submit(self._cufd, calc_id, self._device_for(Lambda, i, ngpu), Lambda, Mu, Den, Stf,
+                              ids[bars[i]:bars[i + 1]], para_fname, Lambda.device, **kw) for i in range(ngpu)]
+            return [f.result() for f in futs]
+
     # -- reference surface -------------------------------------------------------------------
     def backward(self, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, *, pseudo_hessian=0, exact_adjoint=False, source_gradient=False):
         """-> [misfit(1,), gLambda, gMu, gDen, gStf]   (fwi_backward, Src/Torch_Fwi.cpp:38-104).
@@ -246,11 +260,9 @@ class _FwiOps:
         if source_gradient:
             raise ValueError("source_gradient needs exact_adjoint=True (the reference's pass returns its own gStf)")
         kw = {"pseudo_hessian": k} if k else {}     # (not armed: _cufd is called exactly as the reference surface calls it)
-        ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
-        n = int(ids.numel())
+        parts = self._split_cufd(1, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname, **kw)
         if _dist.active():
-            lo, hi = _dist.my_block(n)
-            m, gL, gM, gD, gS_loc, *H = self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids[lo:hi], para_fname, **kw)
+            m, gL, gM, gD, gS_loc, *H = parts[0]
             m, gL, gM, gD = _dist.allreduce_gradients(m, gL, gM, gD)
             gS = torch.zeros_like(_f32c(Stf, "Stf").cpu())
             if _dist.rank() == 0:   # the reference returns GPU 0's buffer only (Torch_Fwi.cpp:102-103)
@@ -258,15 +270,6 @@ class _FwiOps:
             if k > 0:
                 return [m, gL, gM, gD, gS] + list(_dist.allreduce_sum(H[0]))
             return [m, gL, gM, gD, gS]
-        ngpu = int(ngpu)
-        bars = split_shots(n, ngpu)
-        if ngpu == 1:
-            parts = [self._cufd(1, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids, para_fname, **kw)]
-        else:
-            with ThreadPoolExecutor(max_workers=ngpu) as ex:   # one host thread per GPU, ctypes drops the GIL
-                futs = [ex.submit(self._cufd, 1, self._device_for(Lambda, i, ngpu), Lambda, Mu, Den, Stf,
-                                  ids[bars[i]:bars[i + 1]], para_fname, Lambda.device, **kw) for i in range(ngpu)]
-                parts = [f.result() for f in futs]
         if k > 0:   # the parts' pseudo-Hessians summed like the gradients
             H = parts[0][5]
             for p in parts[1:]:
@@ -288,9 +291,8 @@ class _FwiOps:
     def forward(self, Lambda, Mu, Den, Stf, gpu_id, Shot_ids, para_fname, *, pseudo_hessian=0):
         """-> [misfit(1,)]   (fwi_forward, Src/Torch_Fwi.cpp:12-36; calc_id 0 on device gpu_id).
         Extension `pseudo_hessian=k` > 0: -> [misfit, hLambda, hMu, hDen] (see backward; this call's device and shots only)."""
-        ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
-        m, *rest = self._cufd(0, int(gpu_id) if self.device_override is None else self.device_override,
-                              Lambda, Mu, Den, Stf, ids, para_fname, **({"pseudo_hessian": int(pseudo_hessian)} if pseudo_hessian else {}))
+        m, *rest = self._cufd(0, self._session_dev(gpu_id), Lambda, Mu, Den, Stf, _shot_ids(Shot_ids), para_fname,
+                              **({"pseudo_hessian": int(pseudo_hessian)} if pseudo_hessian else {}))
         if int(pseudo_hessian) > 0:
             return [m] + list(rest[4])
         return [m]
@@ -300,23 +302,9 @@ class _FwiOps:
         Extension `to_store=True` (SEPFWI_CALC_OBSERVE_TO_STORE): no files -- the axial-strain gather of every shot goes straight
         into the HBM store of observed data of the session that will later evaluate that shot (same device, same shot split as
         `backward` with the same ngpu / ranks), bit for bit what the file route leaves there."""
-        calc = 3 if to_store else 2
-        ids = torch.as_tensor(Shot_ids, dtype=torch.int32).cpu()
-        n = int(ids.numel())
+        self._split_cufd(3 if to_store else 2, Lambda, Mu, Den, Stf, ngpu, Shot_ids, para_fname)
         if _dist.active():
-            lo, hi = _dist.my_block(n)
-            self._cufd(calc, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids[lo:hi], para_fname)
             _dist.barrier()
-            return None
-        ngpu = int(ngpu)
-        bars = split_shots(n, ngpu)
-        if ngpu == 1:
-            self._cufd(calc, self._device_for(Lambda, 0), Lambda, Mu, Den, Stf, ids, para_fname)
-        else:
-            with ThreadPoolExecutor(max_workers=ngpu) as ex:
-                futs = [ex.submit(self._cufd, calc, self._device_for(Lambda, i, ngpu), Lambda, Mu, Den, Stf,
-                                  ids[bars[i]:bars[i + 1]], para_fname) for i in range(ngpu)]
-                [f.result() for f in futs]
         return None
 
     # -- Born modelling and the Gauss-Newton product (sepfwi_born) -------------------------------
@@ -350,7 +338,7 @@ class _FwiOps:
         stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=ds is not None)   # (ds: read with a blocking copy inside the library)
         args = (_native.ptr(bufs[2]), _native.ptr(bufs[0]), _native.ptr(bufs[1]), _native.ptr(hv[0]) if with_hv else None, _native.ptr(hv[1]) if with_hv else None,
                 _native.ptr(hv[2]) if with_hv else None, _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den), _native.ptr(dLambda), _native.ptr(dMu), _native.ptr(dDen), _native.ptr(Stf), gpu_id,
-                int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+                int(ids.size), _native.ids_arg(ids), _native.path_arg(para_fname), stream)
         rc = L.sepfwi_born(*args) if ds is None else L.sepfwi_born_src(*args, _native.ptr(ds))
         _native.check(rc)
         out, off = [], 0
@@ -435,7 +423,7 @@ class _FwiOps:
         stream = _stream_or_sync(Lambda, Stf, gpu_id, sync_current=True)   # (w was assembled on this stream; the library may run on its own)
         vp = [_native.ptr(t) for t in v] if v else [None, None, None]
         args = (_native.ptr(misfit), _native.ptr(g[0]), _native.ptr(g[1]), _native.ptr(g[2]), _native.ptr(wbuf["ett"]), _native.ptr(wbuf["vx"]), _native.ptr(wbuf["vz"]), *vp,
-                _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den), _native.ptr(Stf), gpu_id, int(ids.size), C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream)
+                _native.ptr(Lambda), _native.ptr(Mu), _native.ptr(Den), _native.ptr(Stf), gpu_id, int(ids.size), _native.ids_arg(ids), _native.path_arg(para_fname), stream)
         rc = L.sepfwi_adjoint_exact_src(*args, _native.ptr(ds), _native.ptr(g_loc)) if src else L.sepfwi_adjoint_exact(*args)
         _native.check(rc)
         g = g.to(Lambda.device)
@@ -461,10 +449,8 @@ class _FwiOps:
         every dict is conditioned; a new list comes back), or ONE float32 tensor holding the gathers [nrec_i][nSteps] shot after shot in
         the order of Shot_ids (any shape with that many elements; a new tensor of the same shape and device comes back).  The input
         is never changed.  With it a caller composes J^T C^T Z C J from `born` and `born_adjoint`, which stay in raw data space."""
-        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
         if not torch.is_tensor(d):
-            d = list(d)
+            d, ids = list(d), _shot_ids(Shot_ids)
             if len(d) != ids.size:
                 raise ValueError("d must hold one dict of gathers per shot of Shot_ids")
             comps = sorted({c for g in d for c in g})
@@ -478,25 +464,15 @@ class _FwiOps:
                     out[i][c] = flat[off:off + n].view(d[i][c].shape)
                     off += n
             return out
-        dims = _para_dims(para_fname)
-        if dims is not None and d.numel() != int(sum(_nrec_per_shot(para_fname, ids))) * dims[2]:
-            raise ValueError("d must hold (nrec_i, nSteps = %d) float32 per shot of Shot_ids, %d elements in all, got %d"
-                             % (dims[2], int(sum(_nrec_per_shot(para_fname, ids))) * dims[2], d.numel()))
-        out = _f32c(d, "d").clone()
-        stream = None
-        if out.is_cuda and out.device.index == dev:
-            stream = _native.stream_arg(out.device)
-        elif out.is_cuda:
-            torch.cuda.synchronize(out.device)
-        _native.check(_native.lib().sepfwi_condition(_native.ptr(out), int(bool(transpose)), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
-                                                     str(para_fname).encode(), stream))
+        (out,), ids, dev, stream = self._data_args((d.clone(),), ("d",), Shot_ids, para_fname, gpu_id)   # (the copy is queued before the stream rule)
+        _native.check(_native.lib().sepfwi_condition(_native.ptr(out), int(bool(transpose)), dev, int(ids.size), _native.ids_arg(ids),
+                                                     _native.path_arg(para_fname), stream))
         return out
 
     # -- the misfit of a parameter file in data space (sepfwi_data_misfit, sepfwi_data_gn) ----------------
     def _data_args(self, tensors, names, Shot_ids, para_fname, gpu_id):
         """float32 contiguous gathers of one size on one device, checked against the survey -> (tensors, ids, dev, stream)"""
-        ids = np.ascontiguousarray(np.asarray(Shot_ids.cpu() if torch.is_tensor(Shot_ids) else Shot_ids, dtype=np.int32)).reshape(-1)
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
+        ids, dev = _shot_ids(Shot_ids), self._session_dev(gpu_id)
         ts = [_f32c(t, n) for t, n in zip(tensors, names)]
         if any(t.numel() != ts[0].numel() or t.device != ts[0].device for t in ts):
             raise ValueError("%s must hold the same number of elements on one device" % " and ".join(names))
@@ -506,12 +482,7 @@ class _FwiOps:
             if ts[0].numel() != want:
                 raise ValueError("%s must hold (nrec_i, nSteps = %d) float32 per shot of Shot_ids, %d elements in all, got %d"
                                  % (names[0], dims[2], want, ts[0].numel()))
-        stream = None
-        if ts[0].is_cuda and ts[0].device.index == dev:
-            stream = _native.stream_arg(ts[0].device)
-        elif ts[0].is_cuda:
-            torch.cuda.synchronize(ts[0].device)
-        return ts, ids, dev, stream
+        return ts, ids, dev, _stream_for(ts[0], dev)
 
     def data_misfit(self, obs, syn, Shot_ids, para_fname, gpu_id=0):
         """The parameter file's misfit of RAW axial-strain gathers, with no wave propagation (include/sepfwi.h, sepfwi_data_misfit):
@@ -527,7 +498,7 @@ class _FwiOps:
         adj = torch.empty_like(syn)
         mis = C.c_float(0.0)
         _native.check(_native.lib().sepfwi_data_misfit(C.cast(C.byref(mis), C.c_void_p), _native.ptr(adj), _native.ptr(obs), _native.ptr(syn), dev, int(ids.size),
-                                                       C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
+                                                       _native.ids_arg(ids), _native.path_arg(para_fname), stream))
         return float(mis.value), adj
 
     def data_gn(self, syn, d, Shot_ids, para_fname, gpu_id=0, obs=None):
@@ -543,12 +514,12 @@ class _FwiOps:
             (obs, syn, d), ids, dev, stream = self._data_args((obs, syn, d), ("obs", "syn", "d"), Shot_ids, para_fname, gpu_id)
             out = torch.empty_like(d)
             _native.check(_native.lib().sepfwi_data_gn_obs(_native.ptr(out), _native.ptr(obs), _native.ptr(syn), _native.ptr(d), dev, int(ids.size),
-                                                           C.c_void_p(ids.ctypes.data), str(para_fname).encode(), stream))
+                                                           _native.ids_arg(ids), _native.path_arg(para_fname), stream))
             return out
         (syn, d), ids, dev, stream = self._data_args((syn, d), ("syn", "d"), Shot_ids, para_fname, gpu_id)
         out = torch.empty_like(d)
-        _native.check(_native.lib().sepfwi_data_gn(_native.ptr(out), _native.ptr(syn), _native.ptr(d), dev, int(ids.size), C.c_void_p(ids.ctypes.data),
-                                                   str(para_fname).encode(), stream))
+        _native.check(_native.lib().sepfwi_data_gn(_native.ptr(out), _native.ptr(syn), _native.ptr(d), dev, int(ids.size), _native.ids_arg(ids),
+                                                   _native.path_arg(para_fname), stream))
         return out
 
     # -- extras --------------------------------------------------------------------------------
@@ -560,8 +531,7 @@ class _FwiOps:
             raise ValueError("ett must be (nrec, nSteps)")
         if ett.is_cuda:     # the library copies on its own stream, ordered only behind the legacy default stream
             torch.cuda.current_stream(ett.device).synchronize()
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_set_observed(str(para_fname).encode(), dev, int(shot_id), _native.ptr(ett),
+        _native.check(_native.lib().sepfwi_set_observed(_native.path_arg(para_fname), self._session_dev(gpu_id), int(shot_id), _native.ptr(ett),
                                                         int(ett.shape[0]), int(ett.shape[1])))
 
     def set_observed_component(self, para_fname, shot_id, comp, data, gpu_id=0):
@@ -573,38 +543,33 @@ class _FwiOps:
             raise ValueError("data must be (nrec, nSteps)")
         if data.is_cuda:
             torch.cuda.current_stream(data.device).synchronize()
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_set_observed_component(str(para_fname).encode(), dev, int(shot_id), int(comp), _native.ptr(data),
+        _native.check(_native.lib().sepfwi_set_observed_component(_native.path_arg(para_fname), self._session_dev(gpu_id), int(shot_id), int(comp), _native.ptr(data),
                                                                   int(data.shape[0]), int(data.shape[1])))
 
     def misfit_parts(self, para_fname, gpu_id=0):
         """{"vx", "vz", "ett"}: the unweighted 0.5 sum r_c^2 of the session's last misfit or gradient call (sepfwi_get_misfit_parts;
         0 for a component with weight 0; this process's shots only)."""
         parts = (C.c_double * 3)()
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_get_misfit_parts(str(para_fname).encode(), dev, parts))
+        _native.check(_native.lib().sepfwi_get_misfit_parts(_native.path_arg(para_fname), self._session_dev(gpu_id), parts))
         return {"vx": parts[0], "vz": parts[1], "ett": parts[2]}
 
     def debug_field(self, para_fname, which, lane=0, gpu_id=0):
         """Test hook (sepfwi_debug_field): wavefield 0..4 (vz, vx, szz, sxx, sxz) / adjoint 5..9 of a forward lane as the
         last call left it, (nz - nPad, nx) float32."""
-        import json
-        with open(para_fname) as fp:
-            j = json.loads(fp.readline())
+        j = _utils.read_para(para_fname)
         out = torch.empty((int(j["nz"]) - int(j["nPad"]), int(j["nx"])), dtype=torch.float32)
-        dev = self.device_override if self.device_override is not None else int(gpu_id)
-        _native.check(_native.lib().sepfwi_debug_field(str(para_fname).encode(), dev, int(lane), int(which), _native.ptr(out)))
+        _native.check(_native.lib().sepfwi_debug_field(_native.path_arg(para_fname), self._session_dev(gpu_id), int(lane), int(which), _native.ptr(out)))
         return out
 
     def stats(self, para_fname, gpu_id=0):
         st = _native.Stats()
-        _native.check(_native.lib().sepfwi_get_stats(str(para_fname).encode(), int(gpu_id), C.byref(st)))
+        _native.check(_native.lib().sepfwi_get_stats(_native.path_arg(para_fname), int(gpu_id), C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
     def loop_status(self, para_fname, gpu_id=0):
         """"" while the session's backward passes run in the persistent loop, else why they do not (sepfwi_loop_status)."""
         buf = C.create_string_buffer(512)
-        _native.check(_native.lib().sepfwi_loop_status(str(para_fname).encode(), int(gpu_id), buf, 512))
+        _native.check(_native.lib().sepfwi_loop_status(_native.path_arg(para_fname), int(gpu_id), buf, 512))
         return buf.value.decode(errors="replace")
 
     def release(self):

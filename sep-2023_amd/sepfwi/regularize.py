@@ -24,11 +24,11 @@ knows of it.
 from __future__ import annotations
 
 import ctypes as C
-import json
 
 import torch
 
 from . import _native
+from . import utils as _utils
 
 USE_FUSED = True   # tests switch it off to compare the fused launches with the torch expressions
 
@@ -96,8 +96,7 @@ class Regularizer(object):
         ref = params[self.active[0]]
         self.weight = None if weight is None else weight.detach().to(device=ref.device, dtype=ref.dtype).contiguous()
         if dx is None or dz is None:
-            with open(module.para_fname) as f:
-                para = json.load(f)
+            para = _utils.read_para(module.para_fname)
             dx, dz = (para["dx"] if dx is None else dx), (para["dz"] if dz is None else dz)
         self.dx, self.dz = float(dx), float(dz)
         ok = lambda x: x == x and x not in (float("inf"), float("-inf"))

@@ -19,12 +19,12 @@ definition runs in torch.  The operator acts on the model only: under sepfwi.dis
 """
 from __future__ import annotations
 
-import json
 import math
 
 import torch
 
 from . import _native
+from . import utils as _utils
 
 MAX_RADIUS = 64
 
@@ -78,8 +78,7 @@ class Smoother(object):
         if unit == "m" and (dx is None or dz is None):
             if self.module is None or getattr(self.module, "para_fname", None) is None:
                 raise ValueError("Smoother: widths in metres need dx and dz (or a module with a parameter file)")
-            with open(self.module.para_fname) as f:
-                para = json.load(f)
+            para = _utils.read_para(self.module.para_fname)
             dx, dz = (para["dx"] if dx is None else dx), (para["dz"] if dz is None else dz)
         self.dx, self.dz = (1.0, 1.0) if unit == "cells" else (float(dx), float(dz))
         if not (self.dx > 0 and self.dz > 0 and math.isfinite(self.dx) and math.isfinite(self.dz)):

@@ -181,6 +181,33 @@ def surveyGen(z_src, x_src, z_rec, x_rec, survey_fname, Windows=None, Weights=No
         json.dump(survey, fp)
 
 
+_PARA_KEYS = ("nz", "nx", "nSteps", "nPad", "dx", "dz", "survey_fname")
+_FILE_CACHE = {}   # ONE entry per kind of file: "para" / "survey" -> ((path, st_mtime_ns, st_size), what the Python side needs of it)
+
+
+def _cached_line(kind, fname, digest):
+    """digest(the one JSON line of fname), read again only when the file's path, mtime or size has changed"""
+    st = os.stat(fname)
+    key = (str(fname), st.st_mtime_ns, st.st_size)
+    hit = _FILE_CACHE.get(kind)
+    if hit is None or hit[0] != key:
+        with open(fname) as fp:
+            hit = _FILE_CACHE[kind] = (key, digest(json.loads(fp.readline())))
+    return hit[1]
+
+
+def read_para(para_fname):
+    """What the Python side reads of a parameter file: those of nz, nx, nSteps, nPad, dx, dz, survey_fname that it holds, as a dict.
+    Raises what open / json raise on a missing or malformed file."""
+    return _cached_line("para", para_fname, lambda j: {k: j[k] for k in _PARA_KEYS if k in j})
+
+
+def read_survey_channels(para_fname):
+    """{"shot<id>": channel count} of the survey file that the parameter file names."""
+    return _cached_line("survey", read_para(para_fname)["survey_fname"],
+                        lambda j: {k: len(v["z_rec"]) for k, v in j.items() if isinstance(v, dict) and "z_rec" in v})
+
+
 def sourceGene(f, nStep, delta_t):
     """Ricker wavelet, delay 1.2/f, amplitude 1e7, float64 (fwi_utils.py:127-140)."""
     e = np.pi * np.pi * f * f

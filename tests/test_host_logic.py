@@ -569,3 +569,82 @@ def test_paragen_writes_the_conditioning_switch_only_when_asked(tmp_path):
     assert "conditioning" not in ja and jb["conditioning"] == "reference" and jb["filter"] == [1, 2, 3, 4]
     with pytest.raises(ValueError):
         ft.paraGen(96, 80, 10.0, 10.0, 100, 1e-3, 10.0, 10, 4, a, "s.json", str(tmp_path / "D"), conditioning="sometimes")
+
+
+def test_api_table_declares_every_function_of_the_header():
+    """sepfwi/_native.py API against include/sepfwi.h: every declared function has argtypes of the declaration's parameter count (also
+    the zero-argument ones) and the restype of its return type, on the loaded library."""
+    from sepfwi import _native
+    L = _native.lib()
+    hdr = open(os.path.join(ROOT, "include", "sepfwi.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    decls = re.findall(r"\b(sepfwi_[a-z_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(decls) == len({n for n, _ in decls}) >= 37
+    for name, params in decls:
+        f = getattr(L, name)
+        n = 0 if params.strip() == "void" else len(params.split(","))
+        assert f.argtypes is not None and len(f.argtypes) == n, (name, n, f.argtypes)
+        want = C.c_char_p if name == "sepfwi_last_error" else None if name in ("sepfwi_release_all", "sepfwi_invalidate_observed") else C.c_int
+        assert f.restype is want, (name, f.restype)
+
+
+def test_sources_are_the_translation_units_of_csrc():
+    from sepfwi import _native
+    assert len(_native.SOURCES) == len(set(_native.SOURCES))
+    assert set(_native.SOURCES) == {f for f in os.listdir(_native.CSRC) if f.endswith((".hip", ".cpp"))}
+
+
+def test_cached_file_reader_sees_a_rewrite(tmp_path):
+    """utils.read_para / read_survey_channels behind ops._para_dims / _nrec_per_shot: a rewritten survey is read again, a shot that is
+    not in it is a ValueError naming it, a missing parameter file gives None (the library then reports it)."""
+    from sepfwi import ops, utils as ft
+    nPml, nz, nx = 10, 40, 48
+    nPad = ft.nPad_for(nz, nPml)
+    pf, sf = str(tmp_path / "para.json"), str(tmp_path / "survey.json")
+    ft.paraGen(nz + 2 * nPml + nPad, nx + 2 * nPml, 10.0, 10.0, 64, 1e-3, 25.0, nPml, nPad, pf, sf, str(tmp_path / "Data"))
+    ft.surveyGen([2, 2], [6, 41], [3, 3, 3], [10, 20, 30], sf)
+    assert ops._para_dims(pf) == (nz + 2 * nPml + nPad, nx + 2 * nPml, 64)
+    assert ops._nrec_per_shot(pf, [0, 1]) == [3, 3] and ops._nrec_per_shot(pf, np.array([1], dtype=np.int32)) == [3]
+    ft.surveyGen([2, 2], [6, 41], [3] * 5, [10, 15, 20, 25, 30], sf)
+    assert ops._nrec_per_shot(pf, [0, 1]) == [5, 5]
+    with pytest.raises(ValueError, match="shot id 2 is not in the survey file"):
+        ops._nrec_per_shot(pf, [0, 2])
+    os.remove(sf)
+    with pytest.raises(FileNotFoundError):
+        ops._nrec_per_shot(pf, [0])
+    os.remove(pf)
+    assert ops._para_dims(pf) is None
+
+
+def test_shot_ids_normaliser_accepts_every_input_form():
+    from sepfwi import ops
+    forms = [torch.tensor([3, 0, 2], dtype=torch.int64), [3, 0, 2], np.array([3, 0, 2], dtype=np.int32), np.array([[3, 0, 2]], dtype=np.int64)[:, ::1],
+             torch.tensor([3, 0, 2], dtype=torch.int32)]
+    for x in forms + [[], torch.zeros(0, dtype=torch.int64)]:
+        a = ops._shot_ids(x)
+        assert isinstance(a, np.ndarray) and a.dtype == np.int32 and a.ndim == 1 and a.flags["C_CONTIGUOUS"], x
+        assert a.tolist() == ([3, 0, 2] if len(x) else []), x
+    assert ops._shot_ids(np.arange(6, dtype=np.int64)[::2]).tolist() == [0, 2, 4]      # a strided view: copied to a contiguous array
+
+
+def test_needs_build_sees_any_header(monkeypatch, tmp_path):
+    """needs_build compares the library with every file of csrc/ and with include/sepfwi.h: no list of headers to forget one in."""
+    import shutil
+    from sepfwi import _native
+    csrc, lib, hdr = str(tmp_path / "csrc"), str(tmp_path / "libsepfwi.so"), str(tmp_path / "sepfwi.h")
+    shutil.copytree(_native.CSRC, csrc)
+    shutil.copy(_native.HEADER, hdr)
+    open(lib, "w").close()
+    t = max(os.path.getmtime(f) for f in [os.path.join(csrc, f) for f in os.listdir(csrc)] + [hdr]) + 10
+    os.utime(lib, (t, t))
+    monkeypatch.setattr(_native, "CSRC", csrc)
+    monkeypatch.setattr(_native, "HEADER", hdr)
+    monkeypatch.setattr(_native, "VARIANTS", {"default": (lib, [])})
+    assert not _native.needs_build()
+    for touched in (os.path.join(csrc, "json_min.hpp"), os.path.join(csrc, "kernels_quiet.hpp"), hdr):
+        os.utime(touched, (t + 10, t + 10))
+        assert _native.needs_build(), touched
+        os.utime(touched, (t - 10, t - 10))
+    assert not _native.needs_build()
+    os.remove(lib)
+    assert _native.needs_build()
